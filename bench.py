@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- OCflow rollout throughput on MI355X (the metric BASELINE.json names).
 
-  python bench.py --gpus N --steps K --warmup W [--workload swarm50] [--scaling strong|weak] [--n ROWS]
+  python bench.py --gpus N --steps K --warmup W [--workload swarm50] [--scaling strong|weak] [--n ROWS] [--full] [--dump-outputs DIR]
 
 A "step" is one public `OCflow(x, Phi, prob, [0,1], nt, "rk4", alph)` call (non-intermediates: returns Jc and the 7
 costs) over a batch of synthetic states already resident in HBM.  Default workload = the configuration north_star
@@ -19,8 +19,15 @@ ranks wall time.  `--n` (N=1) with 512/256/128 rows is the single-GPU proxy for 
 trajectories and controls kept (neuraloc_amd.shock); it prints its own JSON line.
 
 One JSON line on stdout (rank 0), with `roofline` (rollout kernel, fp32-MFMA roof, duration from HIP events recorded
-around the kernel on its launch stream) and `cpu_baseline` (the oracle -- the op-for-op eager-PyTorch port of the
-reference -- timed on the host cores, rank 0, N=1).
+around the kernel on its launch stream).  A plain run does only that: set up, W warm-up steps, K timed steps, the line.
+
+`--full` adds what takes runs of its own: `cpu_baseline` (the oracle -- the op-for-op eager-PyTorch port of the
+reference -- timed on the host cores, rank 0, N=1; `--no-cpu-baseline` skips it) and, for the default swarm50
+configuration on one GPU, `config.other_workloads` (the other BASELINE configs, the shard-size proxies and the training
+iterations; `--no-other-workloads` skips them).
+
+`--dump-outputs DIR` writes what the last timed step returned (Jc and the 7 costs; for the shock sweep the costs of every
+segment and the trajectories / controls of a seeded sample of 512 rows) as DIR/<name>.npy after the timed steps.
 """
 import argparse
 import ctypes as C
@@ -146,6 +153,31 @@ def _cpu_model():
     return "unknown"
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: what the last timed step returned, one DIR/<name>.npy per array (float32 stays float32, everything else becomes
+    float64), so that two builds run with the same arguments can be compared output for output"""
+    conv = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        conv[name] = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def sample_rows(n, k, seed=0):
+    """a fixed, seeded, sorted sample of k of n rows (all of them when n <= k)"""
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
 def read_traffic(workload, kernel, n_local):
     """HBM bytes per launch from the PMC passes (tools/parse_pmc.py writes the file; rocprofv3 --pmc cannot run inside this
     process).  Used only when it was collected for the same kernel and per-GPU batch; its provenance travels with it."""
@@ -203,6 +235,17 @@ def bench_shock(args, dev, world=1, rank=0, dist=None):
                "config": {"workload": f"singlequad-shock d={meta['d']} m={meta['m']} nt={nt} n={n} x {len(times)} shock times, rk4, eval-mode, fp32, "
                                       "intermediates=True (zFull + ctrlFull written)", "rows_per_gpu": hi - lo,
                           "Jc_last_segment": float(res[-1]["costs2"][0])}}
+        if args.dump_outputs:
+            # trajectories and controls of every shock time on a seeded sample of 512 of rank 0's rows (all of them: ~125 MB), the
+            # costs of both segments in full: row k of costs1 / costs2 = [Jc, cs...] of shock time k
+            rows = torch.from_numpy(sample_rows(hi - lo, 512)).to(dev)
+            dump_outputs(args.dump_outputs, {
+                "traj": torch.stack([r["traj"].index_select(0, rows) for r in res]),
+                "ctrl": torch.stack([r["ctrl"].index_select(0, rows) for r in res]),
+                "x_shocked": torch.stack([r["x_shocked"].index_select(0, rows) for r in res]),
+                "costs1": torch.stack([torch.stack([torch.as_tensor(r["costs1"][0])] + [torch.as_tensor(c) for c in r["costs1"][1]]) for r in res]),
+                "costs2": torch.stack([torch.stack([torch.as_tensor(r["costs2"][0])] + [torch.as_tensor(c) for c in r["costs2"][1]]) for r in res]),
+                "nShock": np.array([r["nShock"] for r in res], dtype=np.float64)})
         print(json.dumps(out), flush=True)
     if dist:
         dist.destroy_process_group()
@@ -352,9 +395,18 @@ def main():
     ap.add_argument("--scaling", type=str, default="strong", choices=["strong", "weak"])
     ap.add_argument("--n", type=int, default=0, help="batch rows: the GLOBAL batch (strong) or rows per GPU (weak); default: BASELINE.json's n")
     ap.add_argument("--nt", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-workloads", action="store_true", help="skip the short runs of the other four BASELINE configs, the shock sweep and the training iterations")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline and (default swarm50 config) the other workloads, "
+                         "shard sizes and training iterations")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-other-workloads", action="store_true", help="with --full: skip the short runs of the other four BASELINE configs, the shock sweep and the training iterations")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
@@ -457,7 +509,9 @@ def main():
                          "hbm_peak_GBps": PEAK_HBM_GBS,
                          "note": "per launch on rank 0: its rows x nt state-steps x SURVEY 8(d) FLOPs, over the kernel's HIP-event time"},
         }
-        if world == 1 and args.workload == "swarm50" and not args.n and not args.nt and not args.no_other_workloads:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"Jc": Jc, "cs": torch.stack([torch.as_tensor(c) for c in cs])})
+        if args.full and world == 1 and args.workload == "swarm50" and not args.n and not args.nt and not args.no_other_workloads:
             others = []
             for name in ("swap2", "softcorridor", "swap12", "singlequad", "singlequad-shock"):
                 try:
@@ -479,7 +533,7 @@ def main():
                 except Exception as ex:
                     others.append({"workload": "train " + name, "error": repr(ex)[:200]})
             out["config"]["other_workloads"] = others
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(meta, sd, xtarget, x_cpu, nt)
             out["config"]["speedup_vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
         print(json.dumps(out), flush=True)

@@ -16,7 +16,7 @@ $T rocprofv3 --pmc WRITE_SIZE -d $O/pmc_write_1024 -o w --output-format csv -- p
 python tools/parse_pmc.py $O/pmc_fetch_1024 $O/pmc_write_1024 swarm50 $O/03_hbm_traffic_n1024_duo.json "rollout_duo_kernel" "rollout_duo_kernel" 1024 "profiles/r3/03_hbm_traffic_n1024_duo.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes" > $O/03_parse_1024.log 2>&1
 cp $O/03_hbm_traffic_n1024_duo.json profiles/hbm_traffic_swarm50.json 2>/dev/null
 # 3. the default bench line (with the CPU legs and the other workloads) and the strong-scaling proxy table
-$T python bench.py > $O/04_bench_default.json 2> $O/04_bench_default.err
+$T python bench.py --full > $O/04_bench_default.json 2> $O/04_bench_default.err
 : > $O/05_proxy_table.jsonl
 for n in 4096 2048 1024 512 256 128; do timeout 300 python bench.py --n $n --steps 50 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 >> $O/05_proxy_table.jsonl; done
 NOCF_DUO=0 timeout 300 python bench.py --n 1024 --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 >> $O/05_proxy_table.jsonl

@@ -18,7 +18,7 @@ $T rocprofv3 --pmc WRITE_SIZE -d $O/pmc_write_1024 -o w --output-format csv -- p
 python tools/parse_pmc.py $O/pmc_fetch_1024 $O/pmc_write_1024 swarm50 $O/03_hbm_traffic_n1024_duo.json "rollout_duo_kernel" "rollout_duo_kernel" 1024 "profiles/r4/03_hbm_traffic_n1024_duo.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes" > $O/03_parse_1024.log 2>&1
 cp $O/03_hbm_traffic_n1024_duo.json profiles/hbm_traffic_swarm50.json 2>/dev/null
 # 3. the default bench line (with the CPU legs, the other workloads and the training iterations) and the strong-scaling proxy table
-$T python bench.py > $O/04_bench_default.json 2> $O/04_bench_default.err
+$T python bench.py --full > $O/04_bench_default.json 2> $O/04_bench_default.err
 bash tools/proxy_table.sh $O > /dev/null 2>&1
 mv $O/proxy_table.txt $O/05_proxy_table.txt; mv $O/proxy_table.jsonl $O/05_proxy_table.jsonl
 # 4. timelines (diagnostic build), training times, double precision, memory-side writes by batch size, tests

@@ -22,7 +22,7 @@ $T rocprofv3 --pmc WRITE_SIZE -d $O/pmc_write_1024 -o w --output-format csv -- p
 python tools/parse_pmc.py $O/pmc_fetch_1024 $O/pmc_write_1024 swarm50 $O/03_hbm_traffic_n1024_duo.json "rollout_duo_kernel" "rollout_duo_kernel" 1024 "profiles/r5/03_hbm_traffic_n1024_duo.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes" > $O/03_parse_1024.log 2>&1
 cp $O/03_hbm_traffic_n1024_duo.json profiles/hbm_traffic_swarm50.json 2>/dev/null
 # 3. the default bench line (with the CPU legs, the other workloads, the proxy rows and the training iterations), the strong-scaling proxy table by geometry
-$T python bench.py > $O/04_bench_default.json 2> $O/04_bench_default.err
+$T python bench.py --full > $O/04_bench_default.json 2> $O/04_bench_default.err
 SKIP_TESTS=1 bash tools/r5_forms.sh $O/forms > /dev/null 2>&1
 cp $O/forms/proxy_table.txt $O/05_proxy_table_by_geometry.txt
 : > $O/05_proxy_table.jsonl

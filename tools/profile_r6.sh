@@ -23,7 +23,7 @@ $T rocprofv3 --pmc WRITE_SIZE -d $O/pmc_write_1024 -o w --output-format csv -- p
 python tools/parse_pmc.py $O/pmc_fetch_1024 $O/pmc_write_1024 swarm50 $O/03_hbm_traffic_n1024_duo.json "rollout_duo_kernel" "rollout_duo_kernel" 1024 "profiles/r6/03_hbm_traffic_n1024_duo.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes" > $O/03_parse_1024.log 2>&1
 cp $O/03_hbm_traffic_n1024_duo.json profiles/hbm_traffic_swarm50.json 2>/dev/null
 # 3. the default bench line (CPU leg, the other workloads, the shard rows, the training iterations), and the batch-row table
-$T python bench.py > $O/10_bench_default.json 2> $O/10_bench_default.err
+$T python bench.py --full > $O/10_bench_default.json 2> $O/10_bench_default.err
 : > $O/05_proxy_table.jsonl
 for n in 4096 2048 1024 512 256 128; do timeout 300 python bench.py --n $n --steps 50 --warmup 5 --no-cpu-baseline --no-other-workloads 2>/dev/null | tail -1 >> $O/05_proxy_table.jsonl; done
 python - "$O" <<'PY' > $O/05_proxy_table.txt
