@@ -467,6 +467,44 @@ int nocf_phi_f64(const NocfPhi64* phi, const double* s, int64_t n, double* value
 int nocf_prob_eval_f64(const NocfProb64* prob, int32_t d, const double* x, const double* p, int64_t n,
                        double* lhqw, double* gradpH, double* ctrls, void* stream);
 
+/*
+ * Direct-transcription baseline -- replaces baseline2D.py:42-107 (loss_fun, trainBaseline) and the report loop of
+ * baseline2D.py:136-150 / compareCorridor.py:95-113, for B independent initial points at once (one workgroup each).
+ * Point-agent problems only (Cross2D, SwarmTraj: z' = u); a Quadcopter returns NOCF_E_PROB.  h = 1/nt; prob->training selects
+ * the train / eval thresholds like every other entry point.  For one point z0 and controls U [nt, d]:
+ *     z_{i+1} = z_i + h U_i ,   J = sum_i h L(z_{i+1}, U_i) + alphG |z_nt - xtarget|^2 / 2        (L = calcLHQW(z, p = U_i))
+ * Limits: 1 <= nt <= 256 and U, z, dJ/dU of one point (and the Adam moments) in the 160 KiB of LDS:
+ *     (5 nt d + d + 3 nt) floats (eval: 3 nt d + ...) plus 3 KiB / 12 KiB of partial sums (256 / 1024 lanes, the latter when
+ *     nt * n_agents >= 512) -- swarm50 (d = 150) up to nt = 50.  Past the limits: NOCF_E_SHAPE.
+ * Deterministic: no atomics, no dependence between workgroups; a point's result does not depend on B.
+ *
+ * nocf_baseline_eval_f32: the objective of every point, optionally its gradient, the report and the trajectory.
+ *   z0       device [B, d]          initial states
+ *   U        device [B, nt, d]      controls
+ *   loss     device [B]             J
+ *   grad     device [B, nt, d]      dJ/dU                                                               (nullable)
+ *   report   device [B, 5]          L+G, L, G, Q, W of the report loop: L(z_j, U_j) at the state BEFORE
+ *                                   the step, sums of h L, h Q, h W, G = alphG |z_nt - xtarget|^2 / 2;
+ *                                   Q as calcLHQW returns it (scaled by alph_Q for Cross2D only)       (nullable)
+ *   traj     device [B, d, nt+1]    z_0 .. z_nt                                                         (nullable)
+ *
+ * nocf_baseline_adam_f32: niters iterations of trainBaseline in ONE launch: evaluate J(U); if J < best_loss keep U in Ubest;
+ * take torch's single-tensor Adam step (weight decay 0, constant lr; bias corrections formed in double from step0 + 1 on).
+ *   U, m, v      device [B, nt, d]  iterate and Adam moments, read and written back (fresh solve: m = v = 0, step0 = 0)
+ *   best_loss    device [B]         best J so far, read and written (fresh solve: +inf)
+ *   Ubest        device [B, nt, d]  the iterate that reached best_loss (written when J improves)
+ *   loss_hist    device [B, niters] J of every iteration                                                (nullable)
+ *   step0        Adam steps already taken: a solve split into launches of k and niters - k iterations
+ *                (the second with step0 = k) gives the bits of one launch
+ */
+int nocf_baseline_eval_f32(const NocfProb* prob, int32_t d, int64_t B, int32_t nt, double alphG,
+                           const float* z0, const float* U, float* loss, float* grad, float* report, float* traj,
+                           void* stream);
+int nocf_baseline_adam_f32(const NocfProb* prob, int32_t d, int64_t B, int32_t nt, double alphG,
+                           double lr, double beta1, double beta2, double eps, int32_t step0, int32_t niters,
+                           const float* z0, float* U, float* m, float* v, float* best_loss, float* Ubest,
+                           float* loss_hist, void* stream);
+
 /* Measurement hooks (bench.py): between begin and end every nocf_rollout_f32 call records a pair
  * of HIP events on its launch stream immediately around the rollout kernel; end synchronises on
  * them and returns the summed kernel time and the number of launches.  Not thread-safe. */

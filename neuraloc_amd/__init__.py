@@ -7,6 +7,8 @@ from .problem import Cross2D, SwarmTraj, Quadcopter
 from .initProb import initProb, resample
 from .distributed import OCflow_sharded, shard_rows, reduce_cost_sums
 from ._lib import check_errors
+from .baseline import baseline_loss, baseline_report, baseline_adam_steps, solve_baseline
 
 __all__ = ["Phi", "ResNN", "antiderivTanh", "derivTanh", "OCflow", "ocG", "Cross2D", "SwarmTraj",
-           "Quadcopter", "initProb", "resample", "OCflow_sharded", "shard_rows", "reduce_cost_sums", "check_errors"]
+           "Quadcopter", "initProb", "resample", "OCflow_sharded", "shard_rows", "reduce_cost_sums", "check_errors",
+           "baseline_loss", "baseline_report", "baseline_adam_steps", "solve_baseline"]

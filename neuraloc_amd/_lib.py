@@ -321,6 +321,14 @@ def _bind(L):
     L.nocf_prob_eval_f32.restype = C.c_int
     L.nocf_prob_eval_f32.argtypes = [C.POINTER(NocfProb), C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "nocf_baseline_eval_f32"):
+        L.nocf_baseline_eval_f32.restype = C.c_int
+        L.nocf_baseline_eval_f32.argtypes = [C.POINTER(NocfProb), C.c_int32, C.c_int64, C.c_int32, C.c_double] + [C.c_void_p] * 6 + \
+                                            [C.c_void_p]
+        L.nocf_baseline_adam_f32.restype = C.c_int
+        L.nocf_baseline_adam_f32.argtypes = [C.POINTER(NocfProb), C.c_int32, C.c_int64, C.c_int32, C.c_double,
+                                             C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32] + \
+                                            [C.c_void_p] * 7 + [C.c_void_p]
     L.nocf_profile_begin.restype = C.c_int
     L.nocf_profile_end.restype = C.c_int
     L.nocf_profile_end.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int32)]

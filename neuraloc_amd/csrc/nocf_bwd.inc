@@ -46,6 +46,49 @@ struct BwdArgs {
     const float* gbar_in; float* sbar_out;
 };
 
+// d(raw obstacle cost of agent a)/dx at the sample x, added into gq[3]: the per-agent math of physics_xgrad's obstacle part
+// (Cross2D.py:89-125, SwarmTraj.py:89-125), shared with the baseline kernels (nocf_baseline.inc).  The caller decides when the
+// train-mode masks apply (treated as constants, like autograd does): the baseline also calls it for eval-mode softcorridor, whose
+// cost does not depend on the mode.  A macro, not an inline function: physics_xgrad then compiles token for token as before (an
+// inlined call changed the register allocation of the adjoint kernels).
+#define NOCF_OBSTACLE_XGRAD(pb, x, a, gq) \
+{ \
+    if (pb.kind == NOCF_PROB_CROSS2D) { \
+        const float x0 = x[2 * a], x1 = x[2 * a + 1]; \
+        if (pb.obstacle == NOCF_OBS_SOFTCORRIDOR) { \
+            const float cov = 0.2f, denom = (float)TWO_PI_D * sqrtf(cov * cov); \
+            const float mus[4] = {-2.5f, 2.5f, -1.5f, 1.5f}; \
+            _Pragma("unroll") \
+            for (int k = 0; k < 4; ++k) { \
+                const float pdf = gauss2(x0, x1, mus[k], 0.f, cov, denom); \
+                gq[0] -= pdf * (x0 - mus[k]) / cov; \
+                gq[1] -= pdf * x1 / cov; \
+            } \
+        } else if (pb.obstacle == NOCF_OBS_HARDCORRIDOR) { \
+            const float denom = (float)TWO_PI_D; \
+            const float n1 = sqrtf(x0 * x0 + (x1 - 4.f) * (x1 - 4.f)), n2 = sqrtf(x0 * x0 + (x1 + 3.5f) * (x1 + 3.5f)); \
+            const float th2 = (float)(2.0 + pb.r); \
+            if (n1 < th2 || n2 < th2) { \
+                const float p1 = gauss2(x0, x1, 0.f, 4.f, 1.f, denom), p2 = gauss2(x0, x1, 0.f, -3.5f, 1.f, denom); \
+                gq[0] = -(p1 + p2) * x0; \
+                gq[1] = -p1 * (x1 - 4.f) - p2 * (x1 + 3.5f); \
+            } \
+        } \
+    } else if (pb.kind == NOCF_PROB_SWARMTRAJ && pb.obstacle == NOCF_OBS_BLOCKS && pb.alphQ > 0.0) { \
+        const float x0 = x[3 * a], x1 = x[3 * a + 1], x2 = x[3 * a + 2]; \
+        if (obstacle_swarm(pb, x0, x1, x2) != 0.f) {      /* inside an inflated block (the +999 offset has no gradient) */ \
+            const float c15 = (float)15.749609945722419; \
+            const float den1 = c15 * sqrtf(243.f), den2 = c15 * sqrtf(81.f); \
+            const float e2 = x2 - 2.f, f0 = x0 - 2.5f; \
+            const float q1 = expf(-0.5f * (((x0 * x0) / 9.f + (x1 * x1) / 3.f) + (e2 * e2) / 9.f)) / den1; \
+            const float q2 = expf(-0.5f * (((f0 * f0) / 9.f + (x1 * x1) / 3.f) + (e2 * e2) / 3.f)) / den2; \
+            gq[0] = -q1 * x0 / 9.f - q2 * f0 / 9.f; \
+            gq[1] = -q1 * x1 / 3.f - q2 * x1 / 3.f; \
+            gq[2] = -q1 * e2 / 9.f - q2 * e2 / 3.f; \
+        } \
+    } \
+}
+
 // d(alphQ*Q + alphW*W)/dx of the point-agent problems for the T samples in SB, scaled per sample by coef[t],
 // into XD[t][0..d).  Train-mode masks are treated as constants, like autograd does with the reference.
 // The interaction part walks all (a, b) pairs: PD (coordinates per agent) is a template parameter so the
@@ -103,42 +146,7 @@ __device__ void physics_xgrad(const Ctx& c, const DevPlan& pl, const DevProb& pb
     // obstacle part (one thread per agent) seeds XD; the barrier orders it before the interaction part adds to it
     for (int a = j0; a < N; a += Gsz) {
         float gq[3] = {0.f, 0.f, 0.f};
-        if (pb.training && pb.obstacle != NOCF_OBS_NONE) {
-            if (pb.kind == NOCF_PROB_CROSS2D) {
-                const float x0 = x[2 * a], x1 = x[2 * a + 1];
-                if (pb.obstacle == NOCF_OBS_SOFTCORRIDOR) {
-                    const float cov = 0.2f, denom = (float)TWO_PI_D * sqrtf(cov * cov);
-                    const float mus[4] = {-2.5f, 2.5f, -1.5f, 1.5f};
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const float pdf = gauss2(x0, x1, mus[k], 0.f, cov, denom);
-                        gq[0] -= pdf * (x0 - mus[k]) / cov;
-                        gq[1] -= pdf * x1 / cov;
-                    }
-                } else if (pb.obstacle == NOCF_OBS_HARDCORRIDOR) {
-                    const float denom = (float)TWO_PI_D;
-                    const float n1 = sqrtf(x0 * x0 + (x1 - 4.f) * (x1 - 4.f)), n2 = sqrtf(x0 * x0 + (x1 + 3.5f) * (x1 + 3.5f));
-                    const float th2 = (float)(2.0 + pb.r);
-                    if (n1 < th2 || n2 < th2) {
-                        const float p1 = gauss2(x0, x1, 0.f, 4.f, 1.f, denom), p2 = gauss2(x0, x1, 0.f, -3.5f, 1.f, denom);
-                        gq[0] = -(p1 + p2) * x0;
-                        gq[1] = -p1 * (x1 - 4.f) - p2 * (x1 + 3.5f);
-                    }
-                }
-            } else if (pb.kind == NOCF_PROB_SWARMTRAJ && pb.obstacle == NOCF_OBS_BLOCKS && pb.alphQ > 0.0) {
-                const float x0 = x[3 * a], x1 = x[3 * a + 1], x2 = x[3 * a + 2];
-                if (obstacle_swarm(pb, x0, x1, x2) != 0.f) {      // inside an inflated block (the +999 offset has no gradient)
-                    const float c15 = (float)15.749609945722419;
-                    const float den1 = c15 * sqrtf(243.f), den2 = c15 * sqrtf(81.f);
-                    const float e2 = x2 - 2.f, f0 = x0 - 2.5f;
-                    const float q1 = expf(-0.5f * (((x0 * x0) / 9.f + (x1 * x1) / 3.f) + (e2 * e2) / 9.f)) / den1;
-                    const float q2 = expf(-0.5f * (((f0 * f0) / 9.f + (x1 * x1) / 3.f) + (e2 * e2) / 3.f)) / den2;
-                    gq[0] = -q1 * x0 / 9.f - q2 * f0 / 9.f;
-                    gq[1] = -q1 * x1 / 3.f - q2 * x1 / 3.f;
-                    gq[2] = -q1 * e2 / 9.f - q2 * e2 / 3.f;
-                }
-            }
-        }
+        if (pb.training && pb.obstacle != NOCF_OBS_NONE) NOCF_OBSTACLE_XGRAD(pb, x, a, gq)
         if (ad == 2) { xd[2 * a] = cf * aQ * gq[0]; xd[2 * a + 1] = cf * aQ * gq[1]; }
         else { xd[3 * a] = cf * aQ * gq[0]; xd[3 * a + 1] = cf * aQ * gq[1]; xd[3 * a + 2] = cf * aQ * gq[2]; }
     }

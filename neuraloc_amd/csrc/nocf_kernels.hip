@@ -1539,6 +1539,7 @@ __global__ void mfma_selftest_kernel(const float* __restrict__ a, const float* _
 #include "nocf_f64_bwd.inc"
 #include "nocf_lane.inc"
 #include "nocf_bwd.inc"
+#include "nocf_baseline.inc"
 #include "nocf_lane_bwd.inc"
 #include "nocf_mono_bwd.inc"
 
@@ -2600,6 +2601,63 @@ int nocf_prob_eval_f32(const NocfProb* prob, int32_t d, const float* x, const fl
     if (e) return (int)e;
     hipLaunchKernelGGL(prob_kernel, dim3(grid), dim3(pl.nwaves * 64), ldsBytes, (hipStream_t)stream, pl, pb, x, p, (long)n,
                        lhqw, gradpH, ctrls, nocf_ctrl_dim(prob, d));
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// the direct-transcription baseline (nocf_baseline.inc)
+// ------------------------------------------------------------------------------------------
+static int baseline_setup(const NocfProb* prob, int32_t d, int64_t B, int32_t nt, bool adam, DevProb* pb, int* nth, int* G,
+                          size_t* lds_bytes) {
+    int rc = fill_prob(prob, d, pb);
+    if (rc) return rc;
+    if (pb->kind == NOCF_PROB_QUADCOPTER) return NOCF_E_PROB;           // baselineQuad.py (L-BFGS, other dynamics) is not this method
+    if (B < 1 || B > 0x7fffffffL || nt < 1 || nt > NOCF_BL_MAX_NT) return NOCF_E_SHAPE;
+    *nth = (nt * pb->nAgents >= 512) ? 1024 : 256;                      // enough lanes for every (step, agent) of the larger swarms
+    int g = 64;
+    while (g > 1 && g * nt > *nth) g >>= 1;
+    *G = g;
+    const BaseLay ly = bl_layout(nt, d, *nth, adam);
+    *lds_bytes = (size_t)ly.total * sizeof(float);
+    if (*lds_bytes > 160 * 1024) return NOCF_E_SHAPE;
+    return 0;
+}
+
+int nocf_baseline_eval_f32(const NocfProb* prob, int32_t d, int64_t B, int32_t nt, double alphG, const float* z0, const float* U,
+                           float* loss, float* grad, float* report, float* traj, void* stream) {
+    if (!z0 || !U || !loss) return NOCF_E_NULL;
+    DevProb pb;
+    int nth, G;
+    size_t ldsBytes;
+    int rc = baseline_setup(prob, d, B, nt, false, &pb, &nth, &G, &ldsBytes);
+    if (rc) return rc;
+    BaseArgs ba = {};
+    ba.z0 = z0; ba.U = const_cast<float*>(U); ba.loss = loss; ba.grad = grad; ba.report = report; ba.traj = traj;
+    ba.d = d; ba.nt = nt; ba.G = G; ba.h = (float)(1.0 / nt); ba.aG = (float)alphG;
+    hipError_t e = set_lds(baseline_eval_kernel, ldsBytes);
+    if (e) return (int)e;
+    hipLaunchKernelGGL(baseline_eval_kernel, dim3((unsigned)B), dim3(nth), ldsBytes, (hipStream_t)stream, pb, ba);
+    return (int)hipGetLastError();
+}
+
+int nocf_baseline_adam_f32(const NocfProb* prob, int32_t d, int64_t B, int32_t nt, double alphG, double lr, double beta1, double beta2,
+                           double eps, int32_t step0, int32_t niters, const float* z0, float* U, float* m, float* v, float* best_loss,
+                           float* Ubest, float* loss_hist, void* stream) {
+    if (!z0 || !U || !m || !v || !best_loss || !Ubest) return NOCF_E_NULL;
+    if (niters < 0 || step0 < 0) return NOCF_E_SHAPE;
+    DevProb pb;
+    int nth, G;
+    size_t ldsBytes;
+    int rc = baseline_setup(prob, d, B, nt, true, &pb, &nth, &G, &ldsBytes);
+    if (rc) return rc;
+    if (niters == 0) return 0;
+    BaseArgs ba = {};
+    ba.z0 = z0; ba.U = U; ba.M = m; ba.V = v; ba.best = best_loss; ba.Ubest = Ubest; ba.hist = loss_hist;
+    ba.d = d; ba.nt = nt; ba.G = G; ba.h = (float)(1.0 / nt); ba.aG = (float)alphG;
+    ba.lr = lr; ba.b1 = beta1; ba.b2 = beta2; ba.eps = eps; ba.step0 = step0; ba.niters = niters;
+    hipError_t e = set_lds(baseline_adam_kernel, ldsBytes);
+    if (e) return (int)e;
+    hipLaunchKernelGGL(baseline_adam_kernel, dim3((unsigned)B), dim3(nth), ldsBytes, (hipStream_t)stream, pb, ba);
     return (int)hipGetLastError();
 }
 
