@@ -117,7 +117,8 @@ __device__ void bl_costs(const DevProb& pb, const BaseLay& ly, int d, int nt, in
                     if (ad == 2) pair_force<2>(x, a, 0, N, thr, den, inv_r2, N > 2, gw);
                     else pair_force<3>(x, a, 0, N, thr, den, inv_r2, N > 2, gw);
                 }
-                for (int k = 0; k < ad; ++k) xd[ad * a + k] = cq * gq[k] + cw * gw[k];
+                // written out: a contractible a * b + c * d may fuse either product, differently in the two kernels that inline this
+                for (int k = 0; k < ad; ++k) xd[ad * a + k] = fmaf(cq, gq[k], cw * gw[k]);
             }
         }
     }
@@ -163,11 +164,12 @@ __device__ __forceinline__ float bl_objective(const BaseLay& ly, int nt, float h
 // dJ/dU_i = h U_i + h lam_{i+1}, lam_{i+1} = alphG (z_nt - xtarget) + sum_{j >= i} XD_j: a suffix sum per coordinate.  Into XD (in place)
 // and, when out != null, to out [nt][d].
 __device__ __forceinline__ void bl_adjoint(const DevProb& pb, const BaseLay& ly, int d, int nt, float h, float aG, float* out) {
+#pragma clang fp contract(off)
     for (int k = threadIdx.x; k < d; k += blockDim.x) {
         float lam = aG * (lds[ly.oZ + nt * d + k] - pb.xtarget[k]);
         for (int i = nt - 1; i >= 0; --i) {
             lam += lds[ly.oXD + i * d + k];
-            const float g = h * lds[ly.oU + i * d + k] + h * lam;
+            const float g = fmaf(h, lds[ly.oU + i * d + k], h * lam);   // one fixed rounding: the eval and the Adam kernel agree
             lds[ly.oXD + i * d + k] = g;
             if (out) out[i * d + k] = g;
         }
@@ -244,8 +246,8 @@ __global__ void __launch_bounds__(1024) baseline_adam_kernel(DevProb pb, BaseArg
             best = J;
             for (int e = tid; e < nd; e += nth) Ub[e] = lds[ly.oU + e];
         }
-        // torch single-tensor Adam: m.lerp_(g, 1-b1); v.mul_(b2).addcmul_(g, g, 1-b2); bias corrections in double;
-        // denom = sqrt(v) / sqrt(bc2) + eps; U.addcdiv_(m, denom, -lr / bc1)
+        // torch single-tensor Adam (CPU): m.lerp_(g, 1-b1); v.mul_(b2).addcmul_(g, g, 1-b2); bias corrections in double;
+        // denom = sqrt(v) / sqrt(bc2) + eps; U.addcdiv_(m, denom, -lr / bc1), in that op order with a correctly rounded sqrt
         const double step = (double)(ba.step0 + it + 1);
         const float nss = (float)(-(ba.lr / (1.0 - pow(ba.b1, step))));
         const float bc2s = (float)sqrt(1.0 - pow(ba.b2, step));
@@ -253,9 +255,10 @@ __global__ void __launch_bounds__(1024) baseline_adam_kernel(DevProb pb, BaseArg
 #pragma clang fp contract(off)
             const float g = lds[ly.oXD + e];
             float m = lds[ly.oM + e], v = lds[ly.oV + e];
-            m = fmaf(w1, g - m, m);                       // ATen's vectorised lerp (weight < 0.5): fmadd(w, end - start, start)
+            // ATen's vectorised lerp: fmadd(w, end - start, start) for |w| < 0.5, else fmadd(w - 1, end - start, end)
+            m = fabsf(w1) < 0.5f ? fmaf(w1, g - m, m) : fmaf(w1 - 1.f, g - m, g);
             v = v * b2;
-            v = v + c2 * g * g;
+            v = fmaf(c2 * g, g, v);                       // ATen's vectorised addcmul: fmadd(value * t1, t2, self)
             const float den = sqrtf(v) / bc2s + eps;
             lds[ly.oM + e] = m;
             lds[ly.oV + e] = v;

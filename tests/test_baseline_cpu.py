@@ -10,6 +10,8 @@ import torch
 import neuraloc_amd as na
 from neuraloc_amd import _lib
 from oracle import ocflow_oracle as orc
+import util_oracle as uo
+from util_oracle import oracle_objective
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIX = np.load(os.path.join(REPO, "tests", "golden", "baseline.npz"))
@@ -21,17 +23,6 @@ def make_prob(name, alph, device="cpu"):
     prob, _, _, xInit = na.initProb(name, 10, 10, var0=1.0, cvt=lambda t: t.float().to(device),
                                     alph=[alph[0], alph[1], alph[2], 0.0, 0.0, 0.0])
     return prob, xInit.reshape(-1)
-
-
-def oracle_objective(S, U, z0, nt, alphG):
-    """baseline2D.py:42-63 restated on the oracle's calcLHQW (oracle.prob_LHQW)"""
-    h = 1. / nt
-    Z, loss = z0, 0
-    for i in range(nt):
-        Z = Z + h * U[i]
-        L, _, _, _ = orc.prob_LHQW(S, Z.view(1, -1), U[i].view(1, -1))
-        loss = loss + h * L
-    return (loss + alphG * 0.5 * torch.sum((Z - S.xtarget) ** 2)).reshape(())
 
 
 @pytest.mark.parametrize("name,nt,mode", CASES)
@@ -132,3 +123,64 @@ def test_driver_flags_parse():
         baseline2D.parse_args(["--data", "singlequad"])
     with pytest.raises(SystemExit, match="double"):
         baseline2D.main(["--prec", "double"])
+
+
+@pytest.mark.parametrize("name", sorted(uo.BASE_ALPH))
+def test_abi_nt_limits(name):
+    """the largest nt each entry point accepts (bl_layout in 160 KiB of LDS, NOCF_BL_MAX_NT), refused one past it on the host before
+    any launch; the GPU sweep launches at these limits"""
+    import __graft_entry__ as entry
+    entry.build()
+    L = _lib.lib()
+    fake = C.c_void_p(16)
+    N = uo.N_AGENTS[name]
+    swarm = name.startswith("swarm")
+    st = _struct(_lib.PROB_SWARMTRAJ if swarm else _lib.PROB_CROSS2D, 0, N)
+    d = (3 if swarm else 2) * N
+    ev, ad = uo.nt_limits(name)
+    assert L.nocf_baseline_eval_f32(C.byref(st), d, 1, ev + 1, 100.0, fake, fake, fake, None, None, None, None) == -2
+    args = (0.1, 0.9, 0.999, 1e-8, 0, 0, fake, fake, fake, fake, fake, fake, None, None)     # niters = 0: nothing to launch
+    assert L.nocf_baseline_adam_f32(C.byref(st), d, 1, ad, 100.0, *args) == 0
+    assert L.nocf_baseline_adam_f32(C.byref(st), d, 1, ad + 1, 100.0, *args) == -2
+    if ad < ev:                                         # the eval layout has room for more
+        assert L.nocf_baseline_adam_f32(C.byref(st), d, 1, ev, 100.0, *args) == -2
+
+
+def test_sweep_cases_cover_every_launch_shape():
+    """the shared case list: every point-agent problem, both modes, every (threads, lanes) pair of baseline_setup in both modes"""
+    names = {c.name for c in uo.SWEEP}
+    assert names == set(na.initProb.__globals__["PROBLEM_NAMES"]) - {"singlequad"}
+    for name in names:
+        assert {c.mode for c in uo.SWEEP if c.name == name} == {"train", "eval"}
+        assert {c.nt for c in uo.SWEEP if c.name == name} >= {1, 7, 9, *uo.nt_limits(name)}
+    seen = {}
+    for c in uo.SWEEP:
+        seen.setdefault(uo.launch_shape(uo.N_AGENTS[c.name], c.nt), set()).add(c.mode)
+    assert set(seen) == {(256, g) for g in (1, 2, 4, 8, 16, 32, 64)} | {(1024, g) for g in (4, 8, 16, 32, 64)}
+    assert all(m == {"train", "eval"} for m in seen.values()), seen
+    assert len({c.id for c in uo.SWEEP}) == len(uo.SWEEP)
+
+
+def test_comparator_has_teeth():
+    """the comparator of the GPU sweep rejects each deliberately wrong fp32 restatement on at least one case: L at the state before the
+    step, h = 1/(nt+1), the train threshold in eval mode, the last step's state detached.  (That it accepts the right fp32 restatement
+    holds by construction, its error being what calibrates the tolerance; what the loop checks besides is that every case passes the
+    physics guard.)"""
+    caught = {m: [] for m in uo.MUTATIONS}
+    for case in uo.SWEEP:
+        S, z0, U, traj = uo.case_data(case)
+        aG = case.alph[0]
+        r64 = uo.restate(S, z0, U, aG, torch.float64, traj)
+        r32 = uo.restate(S, z0, U, aG, torch.float32, traj)
+        res = uo.compare_all(r32, r64, r32)
+        assert all(v[0] for v in res.values()), (case.id, res)
+        assert not uo.physics_gaps(case, S, r64), case.id
+        for m in uo.MUTATIONS:
+            if m == "train_threshold_in_eval" and S.training:
+                continue
+            bad = uo.restate(S, z0, U, aG, torch.float32, traj, mutation=m)
+            if not all(v[0] for v in uo.compare_all(bad, r64, r32).values()):
+                caught[m].append(case.id)
+    print("[teeth] " + ", ".join(f"{m}: {len(ids)} of {len(uo.SWEEP)} cases" for m, ids in caught.items()))
+    missed = [m for m, ids in caught.items() if not ids]
+    assert not missed, f"mutations no sweep case rejects: {missed}"
