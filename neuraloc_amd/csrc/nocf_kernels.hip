@@ -1770,7 +1770,8 @@ int nocf_rollout_bwd_small_f32(const NocfPhi* phi, const NocfProb* prob, int64_t
     DevProb pb;
     rc = fill_prob(prob, phi->d, &pb);
     if (rc) return rc;
-    // eligibility = the forward lane kernel's, Cross2D agents only
+    // eligibility = the forward lane kernel's (whose plan refuses a rank above ZQLD), Cross2D agents only
+    if (phi->r < 1 || phi->r > phi->d + 1 || phi->r > ZQLD) return NOCF_E_SHAPE;
     if (!(phi->nTh == 2 && phi->m <= 32 && phi->d + 1 <= 32 && pb.kind == NOCF_PROB_CROSS2D && pb.agentDim == 2 &&
           pb.nAgents * 2 == phi->d && env_int("NOCF_LANE", 1) != 0))
         return NOCF_E_SHAPE;
@@ -1878,17 +1879,24 @@ size_t nocf_workspace_bytes(int32_t d, int32_t m, int32_t nTh) {
 }
 
 size_t nocf_rollout_workspace_bytes(int32_t d, int32_t m, int32_t nTh, int64_t n) {
-    DevPlan pl;
-    const int r = std::min(10, d + 1);
-    if (make_plan(d, m, nTh, r, 1, &pl) != 0) return 0;
-    size_t b = plan_ws_bytes(pl);
-    MonoPlan mpl;
-    if (make_mono_plan(pl, 1, &mpl) == 0) b = std::max(b, mono_ws_bytes(mpl));
+    // the query knows the network's shape, not the rank of A (whose image of r (d+1) floats is part of every plan): sized for r = 10 and for
+    // the largest rank a plan accepts, so that a Phi of any rank fits (sized for r = 10 alone, ranks 11 ... 16 were refused with
+    // NOCF_E_WORKSPACE, even by the lane kernel, which uses no workspace)
+    size_t b = 0;
+    bool any = false;
+    for (const int r : {std::min(10, d + 1), std::min(ZQLD, d + 1)}) {
+        DevPlan pl;
+        if (make_plan(d, m, nTh, r, 1, &pl) != 0) continue;
+        any = true;
+        b = std::max(b, plan_ws_bytes(pl));
+        MonoPlan mpl;
+        if (make_mono_plan(pl, 1, &mpl) == 0) b = std::max(b, mono_ws_bytes(mpl));
 #ifndef NOCF_JIT_ONLY
-    size_t db = 0;
-    if (n > 0 && duo_workspace_bytes(d, m, nTh, r, 1, n, &db) == 0) b = std::max(b, db);
+        size_t db = 0;
+        if (n > 0 && duo_workspace_bytes(d, m, nTh, r, 1, n, &db) == 0) b = std::max(b, db);
 #endif
-    return b;
+    }
+    return any ? b : 0;
 }
 
 int nocf_ctrl_dim(const NocfProb* prob, int32_t d) {
@@ -1918,13 +1926,16 @@ static unsigned* lane_ticket(hipStream_t st) {
     if (hipGetDevice(&dev)) return nullptr;
     std::lock_guard<std::mutex> lk(mu);
     if (!base.count(dev)) {
+        // zeroed on the launch stream and waited for: a null-stream hipMemset is not ordered before a non-blocking stream (torch's side
+        // streams), whose first launch could otherwise read a garbage ticket.  A failure is not remembered: the next call tries again.
         unsigned* p = nullptr;
-        if (hipMalloc((void**)&p, 64 * sizeof(unsigned)) != hipSuccess) { (void)hipGetLastError(); base[dev] = nullptr; }
-        else if (hipMemset(p, 0, 64 * sizeof(unsigned)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(p); base[dev] = nullptr; }
-        else base[dev] = p;
+        if (hipMalloc((void**)&p, 64 * sizeof(unsigned)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        if (hipMemsetAsync(p, 0, 64 * sizeof(unsigned), st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+            (void)hipGetLastError(); (void)hipFree(p); return nullptr;
+        }
+        base[dev] = p;
     }
     unsigned* b = base[dev];
-    if (!b) return nullptr;
     const auto key = std::make_pair(dev, st);
     auto it = slot.find(key);
     if (it == slot.end()) {

@@ -18,6 +18,7 @@ import neuraloc_amd as na
 from neuraloc_amd import _lib
 from oracle import ocflow_oracle as orc
 from util_hip import count_off, full_states, make_net, make_oracle, make_prob, poison_allocator
+from util_lane import oracle_grads64 as _oracle_grads64
 
 pytestmark = pytest.mark.gpu
 def load_golden_by_name(name):
@@ -438,20 +439,6 @@ def test_backward_at_training_size_matches_reference_parameter_gradients(name, b
         gap = (ref32 - ref64).abs().max().item()
         err = (got - ref64).abs().max().item()
         assert err <= 4 * gap + 2e-5 * scale + 1e-7, f"{name} {k}: err {err:g}, reference gap {gap:g}, scale {scale:g}"
-
-
-def _oracle_grads64(x, sd, prob, nt, stepper, alph, nTh):
-    P = orc.PhiParams.from_state_dict({k: v.clone() for k, v in sd.items()}, dtype=torch.float64)
-    for t in [*P.K, *P.b, P.w, P.A, P.cw, P.cb]:
-        t.requires_grad_(True)
-    S = orc.ProbSpec.from_object(prob)
-    S.xtarget = S.xtarget.cpu()
-    J, _ = orc.rollout(x.double().cpu(), P, S.to(torch.float64), [0.0, 1.0], nt, stepper, alph)
-    J.backward()
-    out = {"A": P.A.grad, "c.weight": P.cw.grad, "c.bias": P.cb.grad, "w.weight": P.w.grad}
-    for i in range(nTh):
-        out[f"N.layers.{i}.weight"], out[f"N.layers.{i}.bias"] = P.K[i].grad, P.b[i].grad
-    return float(J), out
 
 
 @pytest.mark.parametrize("name,n,stepper,training,nTh", [(a, b, c_, e, 2) for a, b, c_, e in [
