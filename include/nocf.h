@@ -505,6 +505,55 @@ int nocf_baseline_adam_f32(const NocfProb* prob, int32_t d, int64_t B, int32_t n
                            const float* z0, float* U, float* m, float* v, float* best_loss, float* Ubest,
                            float* loss_hist, void* stream);
 
+/*
+ * Quadcopter baseline -- replaces baselineQuad.py (compute_loss, trainBaseline: torch.optim.LBFGS with the strong-Wolfe line
+ * search, and the report loop that follows it) for B independent starts of ONE quadcopter (d = 12) at once, one 64-lane workgroup
+ * each.  prob must be a Quadcopter (else NOCF_E_PROB) with d = 12 (else NOCF_E_SHAPE); mass, grav and xtarget come from it, alph_Q
+ * and alph_W are ignored as the reference ignores them.  h = 1/nt.  For one start x0 and controls U [nt, 4]:
+ *     x_{i+1} = x_i + h [v, w, (u0/mass) f7(a), (u0/mass) f8(a), (u0/mass) f9(a) - grav, u1:4]   (x = [p, a, v, w], Quadcopter.f)
+ *     J = sum_i h (2 + |U_i|^2) + alphG |x_nt - xtarget|^2 / 2
+ * Limits: 1 <= nt <= NOCF_BLQ_MAX_NT and 1 <= history_size <= NOCF_BLQ_MAX_HISTORY (the L-BFGS vectors are held in registers,
+ * ceil(4 nt / 64) floats per lane each; LDS (4 nt + 4 nt + 12 (nt+1) + 6 nt + 3 nt + 3 nt + 3 (nt+1) + nt + 8 + 2 history) floats,
+ * at most 45 KiB); past them, or B < 1: NOCF_E_SHAPE before any launch.  Deterministic: no atomics, no dependence between
+ * workgroups; a start's result does not depend on B.
+ *
+ * nocf_baseline_quad_eval_f32: the objective of every start, optionally its gradient, the report and the trajectory.
+ *   z0       device [B, 12]          initial states
+ *   U        device [B, nt, 4]       controls
+ *   loss     device [B]              J
+ *   grad     device [B, nt, 4]       dJ/dU (the adjoint of the Euler scheme)                               (nullable)
+ *   report   device [B, 3]           L+G, L, G as the reference's final loop prints them                  (nullable)
+ *   traj     device [B, 12, nt+1]    x_0 .. x_nt                                                          (nullable)
+ *
+ * nocf_baseline_quad_lbfgs_f32: one whole torch.optim.LBFGS.step(closure) per start in ONE launch (line_search_fn
+ * "strong_wolfe", lbfgs.py of torch 2.x mirrored step for step), from U.  max_iter = 0: a no-op returning 0.  max_eval >= 1.
+ *   U           device [B, nt, 4]    in: the initial controls; out: the final iterate (torch leaves the last accepted point)
+ *   loss        device [B]           J of the final iterate
+ *   n_iter      device int32 [B]     iterations taken (torch's state["n_iter"] after one step)
+ *   n_evals     device int32 [B]     objective evaluations (torch's state["func_evals"])
+ *   reason      device int32 [B]     the exit that fired: NOCF_LB_*
+ *   workspace   device, >= nocf_baseline_quad_workspace_bytes(B, nt, history_size) bytes (the history pairs), given in
+ *               workspace_bytes (too small: NOCF_E_WORKSPACE)
+ */
+#define NOCF_BLQ_MAX_NT 256
+#define NOCF_BLQ_MAX_HISTORY 1024
+#define NOCF_LB_GRAD_AT_START 1     /* max |g| <= tolerance_grad at the initial point (n_iter = 0) */
+#define NOCF_LB_GTD           2     /* directional derivative > -tolerance_change                   */
+#define NOCF_LB_MAX_ITER      3     /* n_iter == max_iter                                           */
+#define NOCF_LB_MAX_EVAL      4     /* func_evals >= max_eval                                       */
+#define NOCF_LB_GRAD          5     /* max |g| <= tolerance_grad                                    */
+#define NOCF_LB_STEP          6     /* max |t d| <= tolerance_change                                */
+#define NOCF_LB_LOSS          7     /* |loss - prev_loss| < tolerance_change                        */
+/* bytes of the L-BFGS workspace: 2 history_size 4 nt floats per start; 0 when an argument is out of range */
+size_t nocf_baseline_quad_workspace_bytes(int64_t B, int32_t nt, int32_t history_size);
+int nocf_baseline_quad_eval_f32(const NocfProb* prob, int32_t d, int64_t B, int32_t nt, double alphG,
+                                const float* z0, const float* U, float* loss, float* grad, float* report, float* traj,
+                                void* stream);
+int nocf_baseline_quad_lbfgs_f32(const NocfProb* prob, int32_t d, int64_t B, int32_t nt, double alphG, double lr,
+                                 int32_t max_iter, int32_t max_eval, double tolerance_grad, double tolerance_change,
+                                 int32_t history_size, const float* z0, float* U, float* loss, int32_t* n_iter,
+                                 int32_t* n_evals, int32_t* reason, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Measurement hooks (bench.py): between begin and end every nocf_rollout_f32 call records a pair
  * of HIP events on its launch stream immediately around the rollout kernel; end synchronises on
  * them and returns the summed kernel time and the number of launches.  Not thread-safe. */

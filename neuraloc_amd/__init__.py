@@ -8,7 +8,9 @@ from .initProb import initProb, resample
 from .distributed import OCflow_sharded, shard_rows, reduce_cost_sums
 from ._lib import check_errors
 from .baseline import baseline_loss, baseline_report, baseline_adam_steps, solve_baseline
+from .baseline_quad import quad_baseline_loss, quad_baseline_report, quad_initial_guess, solve_baseline_quad
 
 __all__ = ["Phi", "ResNN", "antiderivTanh", "derivTanh", "OCflow", "ocG", "Cross2D", "SwarmTraj",
            "Quadcopter", "initProb", "resample", "OCflow_sharded", "shard_rows", "reduce_cost_sums", "check_errors",
-           "baseline_loss", "baseline_report", "baseline_adam_steps", "solve_baseline"]
+           "baseline_loss", "baseline_report", "baseline_adam_steps", "solve_baseline",
+           "quad_baseline_loss", "quad_baseline_report", "quad_initial_guess", "solve_baseline_quad"]

@@ -329,6 +329,16 @@ def _bind(L):
         L.nocf_baseline_adam_f32.argtypes = [C.POINTER(NocfProb), C.c_int32, C.c_int64, C.c_int32, C.c_double,
                                              C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32] + \
                                             [C.c_void_p] * 7 + [C.c_void_p]
+    if hasattr(L, "nocf_baseline_quad_eval_f32"):
+        L.nocf_baseline_quad_workspace_bytes.restype = C.c_size_t
+        L.nocf_baseline_quad_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
+        L.nocf_baseline_quad_eval_f32.restype = C.c_int
+        L.nocf_baseline_quad_eval_f32.argtypes = [C.POINTER(NocfProb), C.c_int32, C.c_int64, C.c_int32, C.c_double] + \
+                                                 [C.c_void_p] * 6 + [C.c_void_p]
+        L.nocf_baseline_quad_lbfgs_f32.restype = C.c_int
+        L.nocf_baseline_quad_lbfgs_f32.argtypes = [C.POINTER(NocfProb), C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_double,
+                                                   C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32] + \
+                                                  [C.c_void_p] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p]
     L.nocf_profile_begin.restype = C.c_int
     L.nocf_profile_end.restype = C.c_int
     L.nocf_profile_end.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int32)]

@@ -21,7 +21,7 @@ def _check_prob(prob):
     kind = getattr(prob, "KIND", None)
     if kind == _lib.PROB_QUADCOPTER:
         raise ValueError("the direct-transcription baseline covers the point-agent problems (Cross2D, SwarmTraj); the quadcopter "
-                         "baseline (baselineQuad.py: other dynamics, L-BFGS) is not implemented")
+                         "baseline (baselineQuad.py: other dynamics, L-BFGS) is not this method: use solve_baseline_quad")
     if kind not in (_lib.PROB_CROSS2D, _lib.PROB_SWARMTRAJ) or not hasattr(prob, "_c_struct"):
         raise TypeError(f"prob must be a neuraloc_amd Cross2D or SwarmTraj object, got {type(prob).__name__}")
 

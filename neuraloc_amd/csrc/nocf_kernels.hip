@@ -1540,6 +1540,7 @@ __global__ void mfma_selftest_kernel(const float* __restrict__ a, const float* _
 #include "nocf_lane.inc"
 #include "nocf_bwd.inc"
 #include "nocf_baseline.inc"
+#include "nocf_baseline_quad.inc"
 #include "nocf_lane_bwd.inc"
 #include "nocf_mono_bwd.inc"
 
@@ -2670,6 +2671,79 @@ int nocf_baseline_adam_f32(const NocfProb* prob, int32_t d, int64_t B, int32_t n
     if (e) return (int)e;
     hipLaunchKernelGGL(baseline_adam_kernel, dim3((unsigned)B), dim3(nth), ldsBytes, (hipStream_t)stream, pb, ba);
     return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// the quadcopter baseline (nocf_baseline_quad.inc)
+// ------------------------------------------------------------------------------------------
+static int baseline_quad_setup(const NocfProb* prob, int32_t d, int64_t B, int32_t nt, int32_t hist, DevProb* pb, QuadArgs* qa) {
+    if (!prob) return NOCF_E_NULL;
+    if (prob->kind != NOCF_PROB_QUADCOPTER) return NOCF_E_PROB;         // the point agents' baseline is nocf_baseline_*_f32
+    if (d != 12) return NOCF_E_SHAPE;                                   // baselineQuad.py's dynamics are single-agent
+    int rc = fill_prob(prob, d, pb);
+    if (rc) return rc;
+    if (B < 1 || B > 0x7fffffffL || nt < 1 || nt > NOCF_BLQ_MAX_NT || hist < 0 || hist > NOCF_BLQ_MAX_HISTORY) return NOCF_E_SHAPE;
+    *qa = QuadArgs{};
+    qa->xt = pb->xtarget;
+    qa->nt = nt; qa->hist = hist;
+    qa->h = (float)(1.0 / nt); qa->mass = (float)pb->mass; qa->grav = (float)pb->grav;
+    return 0;
+}
+
+size_t nocf_baseline_quad_workspace_bytes(int64_t B, int32_t nt, int32_t history_size) {
+    if (B < 1 || B > 0x7fffffffL || nt < 1 || nt > NOCF_BLQ_MAX_NT || history_size < 1 || history_size > NOCF_BLQ_MAX_HISTORY) return 0;
+    return (size_t)B * 2 * (size_t)history_size * 4 * (size_t)nt * sizeof(float);
+}
+
+int nocf_baseline_quad_eval_f32(const NocfProb* prob, int32_t d, int64_t B, int32_t nt, double alphG, const float* z0, const float* U,
+                                float* loss, float* grad, float* report, float* traj, void* stream) {
+    if (!z0 || !U || !loss) return NOCF_E_NULL;
+    DevProb pb;
+    QuadArgs qa;
+    int rc = baseline_quad_setup(prob, d, B, nt, 0, &pb, &qa);
+    if (rc) return rc;
+    qa.z0 = z0; qa.U = const_cast<float*>(U); qa.loss = loss; qa.grad = grad; qa.report = report; qa.traj = traj;
+    qa.aG = (float)alphG; qa.aGh = (float)(alphG * 0.5);
+    const size_t ldsBytes = (size_t)blq_layout(nt, 0).total * sizeof(float);
+    hipLaunchKernelGGL(baseline_quad_eval_kernel, dim3((unsigned)B), dim3(NOCF_BLQ_WAVE), ldsBytes, (hipStream_t)stream, qa);
+    return (int)hipGetLastError();
+}
+
+extern "C++" {
+template <int E>
+static int launch_quad_lbfgs(const QuadArgs& qa, int64_t B, size_t ldsBytes, hipStream_t st) {
+    hipError_t e = set_lds(baseline_quad_lbfgs_kernel<E>, ldsBytes);
+    if (e) return (int)e;
+    hipLaunchKernelGGL(baseline_quad_lbfgs_kernel<E>, dim3((unsigned)B), dim3(NOCF_BLQ_WAVE), ldsBytes, st, qa);
+    return (int)hipGetLastError();
+}
+}
+
+int nocf_baseline_quad_lbfgs_f32(const NocfProb* prob, int32_t d, int64_t B, int32_t nt, double alphG, double lr, int32_t max_iter,
+                                 int32_t max_eval, double tolerance_grad, double tolerance_change, int32_t history_size,
+                                 const float* z0, float* U, float* loss, int32_t* n_iter, int32_t* n_evals, int32_t* reason,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    if (!z0 || !U || !loss || !n_iter || !n_evals || !reason || !workspace) return NOCF_E_NULL;
+    if (history_size < 1 || max_iter < 0 || max_eval < 1) return NOCF_E_SHAPE;
+    DevProb pb;
+    QuadArgs qa;
+    int rc = baseline_quad_setup(prob, d, B, nt, history_size, &pb, &qa);
+    if (rc) return rc;
+    if (workspace_bytes < nocf_baseline_quad_workspace_bytes(B, nt, history_size)) return NOCF_E_WORKSPACE;
+    if (max_iter == 0) return 0;
+    qa.z0 = z0; qa.U = U; qa.loss = loss; qa.n_iter = n_iter; qa.n_evals = n_evals; qa.reason = reason;
+    qa.ws = (float*)workspace;
+    qa.aG = (float)alphG; qa.aGh = (float)(alphG * 0.5);
+    qa.max_iter = max_iter; qa.max_eval = max_eval;
+    qa.lr = lr; qa.tol_grad = tolerance_grad; qa.tol_change = tolerance_change;
+    const size_t ldsBytes = (size_t)blq_layout(nt, history_size).total * sizeof(float);
+    const int per_lane = (4 * nt + NOCF_BLQ_WAVE - 1) / NOCF_BLQ_WAVE;  // L-BFGS vector elements per lane
+    hipStream_t st = (hipStream_t)stream;
+    if (per_lane <= 1) return launch_quad_lbfgs<1>(qa, B, ldsBytes, st);
+    if (per_lane <= 2) return launch_quad_lbfgs<2>(qa, B, ldsBytes, st);
+    if (per_lane <= 4) return launch_quad_lbfgs<4>(qa, B, ldsBytes, st);
+    if (per_lane <= 8) return launch_quad_lbfgs<8>(qa, B, ldsBytes, st);
+    return launch_quad_lbfgs<16>(qa, B, ldsBytes, st);
 }
 
 int nocf_selftest_mfma(const float* a, const float* b, int32_t K, float* out, void* stream) {
