@@ -236,11 +236,12 @@ int nocf_rollout_bwd_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, in
                          float* PHIb, float* lam0, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
- * Activation record (optional, training of two-layer networks that the split-role kernel takes: m = 512, point-agent problems).
+ * Activation record (optional, training of two-layer networks that the split-role kernel takes: m = 512, point-agent problems; and that the
+ * one-CU kernel takes: 32 < m <= 128 in whole 16-blocks, d+1 <= 32, every problem class).
  * nocf_rollout_record_act_f32 = nocf_rollout_record_f32 that also stores, for every RK evaluation and sample, the activations of
  * grad Phi -- u0 = sigma(o), tanh(o), tanh(q), a = w + hN K1' v ([nt*nstage, n, m] each) and grad Phi ([nt*nstage, n, d+1]) -- into
  *   act_rec  device [nocf_activation_record_floats(...)] floats (four sections of nt*nstage*n*m, one of nt*nstage*n*(d+1)); NULL: no record
- *   recorded host int32: 1 when the kernel this call launched wrote the record (only the split-role kernel does), else 0
+ *   recorded host int32: 1 when the kernel this call launched wrote the record (the split-role and the one-CU kernel do), else 0
  * nocf_rollout_bwd_act_f32 = nocf_rollout_bwd_f32 that, given a record the forward launch WROTE (recorded == 1), loads these
  * activations instead of re-running grad Phi's forward sweep at every evaluation (four of its eight GEMM phases and the weights they
  * stream; the terminal evaluation is still recomputed).  act_rec NULL: exactly nocf_rollout_bwd_f32.

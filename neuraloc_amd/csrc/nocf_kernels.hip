@@ -2085,7 +2085,8 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
             (void)hipEventRecord(ev0, st);
         }
         const MonoPlan* mpp = reinterpret_cast<const MonoPlan*>(ws + mpl.pp.oPlan);
-        const bool mono_rec = act && s_all && !tapeSc && (phi->m % 16) == 0;   // activation record: the one-CU kernel writes it too
+        // activation record: the one-CU kernel writes it too, for the widths nocf_activation_record_floats sizes a record for
+        const bool mono_rec = act && s_all && !tapeSc && (phi->m % 16) == 0 && phi->m > 32;
         if (mono_rec) { ra.act = act; ra.actRows = (long)nt * ((stepper == NOCF_RK4) ? 4 : 1) * n; }
         void* args[] = {(void*)&mpp, (void*)&pb, (void*)&ws, (void*)&ra};
         e = hipLaunchKernel(fk, dim3((int)((n + 15) / 16)), dim3(256), args, ldsBytes, st); if (e) return (int)e;
@@ -2214,7 +2215,7 @@ size_t nocf_activation_record_floats(int32_t d, int32_t m, int32_t nTh, int64_t 
 #else
     size_t dummy = 0;
     if (nTh != 2 || n < 1 || nt < 1 || (stepper != NOCF_RK4 && stepper != NOCF_RK1)) return 0;
-    // shapes with a recording kernel: the split-role kernel's (m = 512) and the one-CU kernel's (m <= 128 in whole 16-blocks, d+1 <= 16;
+    // shapes with a recording kernel: the split-role kernel's (m = 512) and the one-CU kernel's (32 < m <= 128 in whole 16-blocks, d+1 <= 32;
     // whether that kernel is taken also depends on the problem: `recorded` of the record call says so)
     const bool duo = (m == 512 || m == 256) && env_int("NOCF_DUO", 1) != 0 &&
                      duo_workspace_bytes(d, m, nTh, d + 1 < 10 ? d + 1 : 10, 1, n, &dummy) == 0;   // (zero-padded widths: no record, its rows have the real width)

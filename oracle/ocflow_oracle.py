@@ -143,10 +143,12 @@ def phi_value(P: PhiParams, s):
     return F.linear(resnet(P, s), P.w) + quad + F.linear(s, P.cw, P.cb)
 
 
-def phi_grad(P: PhiParams, s):
+def phi_grad(P: PhiParams, s, parts=None):
     """Analytic gradient of Phi wrt s=(x,t), n-by-(d+1)   (src/Phi.py:99-138).
     Works feature-major inside, like the reference, so the GEMM shapes (and
-    hence the CPU summation order) are identical."""
+    hence the CPU summation order) are identical.
+    parts: a dict that receives the intermediates of this evaluation, sample-major
+    (u0, tanh_o, tanh_q, a: n-by-m of the opening and the first residual layer; grad)."""
     hN = 1.0 / (P.nTh - 1)
     AtA = torch.matmul(P.A.t(), P.A)
     pre0 = F.linear(s, P.K[0], P.b[0])
@@ -161,8 +163,13 @@ def phi_grad(P: PhiParams, s):
         gate = torch.tanh(F.linear(states[i - 1], P.K[i], P.b[i])).t()
         back = seed + hN * torch.mm(P.K[i].t(), gate * seed)
     gate0 = torch.tanh(pre0)
+    if parts is not None:
+        # what a recording kernel keeps of this evaluation (two-layer networks: u0 = sigma(o), tanh(o), tanh(q), a = w + hN K1'(tanh(q) w))
+        parts.update(u0=states[0], tanh_o=gate0, tanh_q=gate.t() if P.nTh > 1 else None, a=back.t())
     back = torch.mm(P.K[0].t(), gate0.t() * back)
     g = back + torch.mm(AtA, s.t()) + P.cw.t()
+    if parts is not None:
+        parts["grad"] = g.t()
     return g.t()
 
 
