@@ -555,6 +555,36 @@ int nocf_baseline_quad_lbfgs_f32(const NocfProb* prob, int32_t d, int64_t B, int
                                  int32_t history_size, const float* z0, float* U, float* loss, int32_t* n_iter,
                                  int32_t* n_evals, int32_t* reason, void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * The two baselines in double precision (the reference's --prec double): the argument lists of the _f32 functions with double
+ * buffers and a NocfProb64 (xtarget as doubles), the same semantics, error codes, NOCF_LB_* reasons and determinism.  What differs:
+ *   - direct transcription: U, z and dJ/dU of one point live in LDS as doubles, (3 nt d + d + 3 nt + 8) doubles plus 6 KiB / 24 KiB of
+ *     partial sums; the Adam moments do not (registers, or the m / v arrays themselves), so both entry points share one limit:
+ *     nocf_baseline_max_nt(prob, d, adam, 8) -- swarm (d = 96) up to nt = 59, swarm50 (d = 150) up to nt = 38.
+ *   - quadcopter: every scalar of torch.optim.LBFGS is a double; the workspace holds doubles (twice the bytes).
+ *
+ * nocf_baseline_max_nt: the largest nt nocf_baseline_eval_* (adam = 0) / nocf_baseline_adam_* (adam != 0) accept for this problem,
+ * for elem_bytes = 4 (the _f32 entry points) or 8 (_f64); every nt from 1 to it is accepted, every larger one returns NOCF_E_SHAPE
+ * before any launch.  Only kind and n_agents of prob are read.  < 0: NOCF_E_* (a quadcopter: NOCF_E_PROB; elem_bytes: NOCF_E_SHAPE).
+ */
+int nocf_baseline_max_nt(const NocfProb* prob, int32_t d, int32_t adam, int32_t elem_bytes);
+int nocf_baseline_eval_f64(const NocfProb64* prob, int32_t d, int64_t B, int32_t nt, double alphG,
+                           const double* z0, const double* U, double* loss, double* grad, double* report, double* traj,
+                           void* stream);
+int nocf_baseline_adam_f64(const NocfProb64* prob, int32_t d, int64_t B, int32_t nt, double alphG,
+                           double lr, double beta1, double beta2, double eps, int32_t step0, int32_t niters,
+                           const double* z0, double* U, double* m, double* v, double* best_loss, double* Ubest,
+                           double* loss_hist, void* stream);
+/* bytes of the double-precision L-BFGS workspace: 2 history_size 4 nt doubles per start; 0 when an argument is out of range */
+size_t nocf_baseline_quad_workspace_bytes_f64(int64_t B, int32_t nt, int32_t history_size);
+int nocf_baseline_quad_eval_f64(const NocfProb64* prob, int32_t d, int64_t B, int32_t nt, double alphG,
+                                const double* z0, const double* U, double* loss, double* grad, double* report, double* traj,
+                                void* stream);
+int nocf_baseline_quad_lbfgs_f64(const NocfProb64* prob, int32_t d, int64_t B, int32_t nt, double alphG, double lr,
+                                 int32_t max_iter, int32_t max_eval, double tolerance_grad, double tolerance_change,
+                                 int32_t history_size, const double* z0, double* U, double* loss, int32_t* n_iter,
+                                 int32_t* n_evals, int32_t* reason, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Measurement hooks (bench.py): between begin and end every nocf_rollout_f32 call records a pair
  * of HIP events on its launch stream immediately around the rollout kernel; end synchronises on
  * them and returns the summed kernel time and the number of launches.  Not thread-safe. */

@@ -339,6 +339,25 @@ def _bind(L):
         L.nocf_baseline_quad_lbfgs_f32.argtypes = [C.POINTER(NocfProb), C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_double,
                                                    C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32] + \
                                                   [C.c_void_p] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p]
+    if hasattr(L, "nocf_baseline_eval_f64"):
+        L.nocf_baseline_max_nt.restype = C.c_int
+        L.nocf_baseline_max_nt.argtypes = [C.POINTER(NocfProb), C.c_int32, C.c_int32, C.c_int32]
+        L.nocf_baseline_eval_f64.restype = C.c_int
+        L.nocf_baseline_eval_f64.argtypes = [C.POINTER(NocfProb64), C.c_int32, C.c_int64, C.c_int32, C.c_double] + [C.c_void_p] * 6 + \
+                                            [C.c_void_p]
+        L.nocf_baseline_adam_f64.restype = C.c_int
+        L.nocf_baseline_adam_f64.argtypes = [C.POINTER(NocfProb64), C.c_int32, C.c_int64, C.c_int32, C.c_double,
+                                             C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32] + \
+                                            [C.c_void_p] * 7 + [C.c_void_p]
+        L.nocf_baseline_quad_workspace_bytes_f64.restype = C.c_size_t
+        L.nocf_baseline_quad_workspace_bytes_f64.argtypes = [C.c_int64, C.c_int32, C.c_int32]
+        L.nocf_baseline_quad_eval_f64.restype = C.c_int
+        L.nocf_baseline_quad_eval_f64.argtypes = [C.POINTER(NocfProb64), C.c_int32, C.c_int64, C.c_int32, C.c_double] + \
+                                                 [C.c_void_p] * 6 + [C.c_void_p]
+        L.nocf_baseline_quad_lbfgs_f64.restype = C.c_int
+        L.nocf_baseline_quad_lbfgs_f64.argtypes = [C.POINTER(NocfProb64), C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_double,
+                                                   C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32] + \
+                                                  [C.c_void_p] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p]
     L.nocf_profile_begin.restype = C.c_int
     L.nocf_profile_end.restype = C.c_int
     L.nocf_profile_end.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int32)]
@@ -507,6 +526,19 @@ def require_device_f64(t, name):
         raise RuntimeError(f"{name} has dtype {t.dtype} in a double-precision call: convert the network, the problem and the "
                            "states together (net.to(torch.float64), initProb(..., cvt) with a float64 cvt), like the reference's --prec double")
     return t.contiguous()
+
+
+def require_device(t, name, double):
+    """the dtype check of a call that dispatches on precision: require_device_f64 when the call is a double-precision one"""
+    return require_device_f64(t, name) if double else require_device_f32(t, name)
+
+
+def is_double(*tensors):
+    """a call computes in double when its first tensor argument is float64 (as Phi.forward / OCflow decide it); the others must match"""
+    for t in tensors:
+        if isinstance(t, torch.Tensor):
+            return t.dtype == torch.float64
+    return False
 
 
 def ptr(t):

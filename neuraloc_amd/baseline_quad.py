@@ -3,8 +3,12 @@ the unknowns, forward Euler with h = 1/nt, torch.optim.LBFGS with the strong-Wol
 are solved at once, one 64-lane workgroup each, and a whole LBFGS.step is one kernel launch (include/nocf.h:
 nocf_baseline_quad_eval_f32, nocf_baseline_quad_lbfgs_f32; neuraloc_amd/csrc/nocf_baseline_quad.inc).
 
-Single-agent Quadcopter only (d = 12); fp32 on the GPU only.  mass, grav and xtarget come from the problem; alph_Q and alph_W are
-ignored, as the reference ignores them.
+Single-agent Quadcopter only (d = 12), on the GPU only.  mass, grav and xtarget come from the problem; alph_Q and alph_W are
+ignored, as the reference ignores them.  The precision follows the tensors, as in Phi.forward / OCflow: float32 z0 / U take the fp32
+kernels, float64 ones (the reference's --prec double; every tensor of the call float64) the double-precision kernels
+(nocf_baseline_quad_eval_f64, nocf_baseline_quad_lbfgs_f64; nocf_baseline_quad_f64.inc) and give float64 results.  With the
+reference's tolerances (tolerance_change = 1e-6 on a loss of about 2182) only the double solve runs to the optimum: the fp32 one
+stops where the loss stalls at fp32 resolution.
 
 Shapes: z0 is [12] or [B, 12]; controls are [nt, 4] or [B, nt, 4] (a single set of controls or a single start is broadcast against
 a batch).  When neither argument has a batch dimension, the results have none either."""
@@ -59,25 +63,29 @@ def _check_shapes(z0, U, prob, nt=None):
     return B, int(nt), single
 
 
-def _batch(z0, U, B, nt):
-    z = _lib.require_device_f32(z0, "z0").reshape(-1, D).expand(B, D).contiguous()
-    u = None if U is None else _lib.require_device_f32(U, "U").reshape(-1, nt, NU).expand(B, nt, NU).contiguous()
+def _batch(z0, U, B, nt, double=False):
+    z = _lib.require_device(z0, "z0", double).reshape(-1, D).expand(B, D).contiguous()
+    u = None if U is None else _lib.require_device(U, "U", double).reshape(-1, nt, NU).expand(B, nt, NU).contiguous()
     return z, u
 
 
 def _eval(z0, U, prob, alphG, grad, report):
     B, nt, single = _check_shapes(z0, U, prob)
-    z, u = _batch(z0, U, B, nt)
+    double = _lib.is_double(z0, U)
+    z, u = _batch(z0, U, B, nt, double)
     dev = z.device
-    st, keep = prob._c_struct(dev)
-    loss = torch.empty(B, dtype=torch.float32, device=dev)
-    g = torch.empty(B, nt, NU, dtype=torch.float32, device=dev) if grad else None
-    rep = torch.empty(B, 3, dtype=torch.float32, device=dev) if report else None
-    traj = torch.empty(B, D, nt + 1, dtype=torch.float32, device=dev) if report else None
+    st, keep = prob._c_struct64(dev) if double else prob._c_struct(dev)
+    dt = torch.float64 if double else torch.float32
+    loss = torch.empty(B, dtype=dt, device=dev)
+    g = torch.empty(B, nt, NU, dtype=dt, device=dev) if grad else None
+    rep = torch.empty(B, 3, dtype=dt, device=dev) if report else None
+    traj = torch.empty(B, D, nt + 1, dtype=dt, device=dev) if report else None
+    L = _lib.lib()
     with torch.cuda.device(dev):
-        rc = _lib.lib().nocf_baseline_quad_eval_f32(C.byref(st), D, B, nt, float(alphG), _lib.ptr(z), _lib.ptr(u), _lib.ptr(loss),
-                                                    _lib.ptr(g), _lib.ptr(rep), _lib.ptr(traj), _lib.stream_ptr(dev))
-    _lib.check(rc, "nocf_baseline_quad_eval_f32")
+        rc = (L.nocf_baseline_quad_eval_f64 if double else L.nocf_baseline_quad_eval_f32)(
+            C.byref(st), D, B, nt, float(alphG), _lib.ptr(z), _lib.ptr(u), _lib.ptr(loss), _lib.ptr(g), _lib.ptr(rep), _lib.ptr(traj),
+            _lib.stream_ptr(dev))
+    _lib.check(rc, "nocf_baseline_quad_eval_f64" if double else "nocf_baseline_quad_eval_f32")
     if single:
         loss = loss[0]
         g = None if g is None else g[0]
@@ -99,11 +107,12 @@ def quad_baseline_report(z0, U, prob, alphG):
     return rep, traj
 
 
-def quad_initial_guess(nt, B=None, generator=None):
-    """baselineQuad.py:75: 1e-2 randn(nt, 4) on the CPU generator, start by start ([nt, 4] when B is None, else [B, nt, 4])"""
+def quad_initial_guess(nt, B=None, generator=None, dtype=torch.float32):
+    """baselineQuad.py:75: 1e-2 randn(nt, 4) on the CPU generator, start by start ([nt, 4] when B is None, else [B, nt, 4]); the
+    reference draws in the default dtype and converts (cvt), so a double guess is the fp32 draw widened"""
     if B is None:
-        return 1.e-2 * torch.randn(int(nt), NU, generator=generator)
-    return torch.stack([1.e-2 * torch.randn(int(nt), NU, generator=generator) for _ in range(int(B))])
+        return (1.e-2 * torch.randn(int(nt), NU, generator=generator)).to(dtype)
+    return torch.stack([1.e-2 * torch.randn(int(nt), NU, generator=generator) for _ in range(int(B))]).to(dtype)
 
 
 def solve_baseline_quad(z0, prob, nt=50, alphG=5000., U0=None, generator=None, lr=1., max_iter=16000, max_eval=10000,
@@ -123,26 +132,28 @@ def solve_baseline_quad(z0, prob, nt=50, alphG=5000., U0=None, generator=None, l
         raise ValueError(f"history_size must be in [1, {MAX_HISTORY}]")
     if U0 is None:
         B, nt, single = _check_shapes(z0, None, prob, nt)
-        _lib.require_device_f32(z0, "z0")
-        U0 = quad_initial_guess(nt, None if single else B, generator).to(z0.device)
+        double = _lib.is_double(z0)
+        _lib.require_device(z0, "z0", double)
+        U0 = quad_initial_guess(nt, None if single else B, generator, torch.float64 if double else torch.float32).to(z0.device)
     B, nt, single = _check_shapes(z0, U0, prob)
-    z, U = _batch(z0, U0, B, nt)
+    double = _lib.is_double(z0, U0)
+    z, U = _batch(z0, U0, B, nt, double)
     U = U.clone()
     dev = U.device
-    loss = torch.empty(B, dtype=torch.float32, device=dev)
+    loss = torch.empty(B, dtype=U.dtype, device=dev)
     info = {k: torch.zeros(B, dtype=torch.int32, device=dev) for k in ("n_iter", "n_evals", "reason")}
     L = _lib.lib()
-    nbytes = L.nocf_baseline_quad_workspace_bytes(B, nt, int(history_size))
+    nbytes = (L.nocf_baseline_quad_workspace_bytes_f64 if double else L.nocf_baseline_quad_workspace_bytes)(B, nt, int(history_size))
     if nbytes == 0:
         raise ValueError(f"no workspace for B = {B}, nt = {nt}, history_size = {history_size}")
-    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-    st, keep = prob._c_struct(dev)
+    ws = torch.empty(nbytes // U.element_size(), dtype=U.dtype, device=dev)
+    st, keep = prob._c_struct64(dev) if double else prob._c_struct(dev)
     with torch.cuda.device(dev):
-        rc = L.nocf_baseline_quad_lbfgs_f32(C.byref(st), D, B, nt, float(alphG), float(lr), int(max_iter), int(max_eval),
-                                            float(tolerance_grad), float(tolerance_change), int(history_size), _lib.ptr(z),
-                                            _lib.ptr(U), _lib.ptr(loss), _lib.ptr(info["n_iter"]), _lib.ptr(info["n_evals"]),
-                                            _lib.ptr(info["reason"]), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
-    _lib.check(rc, "nocf_baseline_quad_lbfgs_f32")
+        rc = (L.nocf_baseline_quad_lbfgs_f64 if double else L.nocf_baseline_quad_lbfgs_f32)(
+            C.byref(st), D, B, nt, float(alphG), float(lr), int(max_iter), int(max_eval), float(tolerance_grad), float(tolerance_change),
+            int(history_size), _lib.ptr(z), _lib.ptr(U), _lib.ptr(loss), _lib.ptr(info["n_iter"]), _lib.ptr(info["n_evals"]),
+            _lib.ptr(info["reason"]), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
+    _lib.check(rc, "nocf_baseline_quad_lbfgs_f64" if double else "nocf_baseline_quad_lbfgs_f32")
     if int(max_iter) == 0:
         loss = quad_baseline_loss(z, U, prob, alphG)
     if single:

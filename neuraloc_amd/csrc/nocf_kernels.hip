@@ -1541,6 +1541,8 @@ __global__ void mfma_selftest_kernel(const float* __restrict__ a, const float* _
 #include "nocf_bwd.inc"
 #include "nocf_baseline.inc"
 #include "nocf_baseline_quad.inc"
+#include "nocf_baseline_f64.inc"
+#include "nocf_baseline_quad_f64.inc"
 #include "nocf_lane_bwd.inc"
 #include "nocf_mono_bwd.inc"
 
@@ -2620,19 +2622,38 @@ int nocf_prob_eval_f32(const NocfProb* prob, int32_t d, const float* x, const fl
 // ------------------------------------------------------------------------------------------
 // the direct-transcription baseline (nocf_baseline.inc)
 // ------------------------------------------------------------------------------------------
+// The launch shape and the LDS bytes of one point for nt steps: the ONE statement of the baselines' nt limit (both precisions, both entry
+// points; nocf_baseline_max_nt reports it).  elem_bytes 4: bl_layout (the Adam moments in LDS); 8: bl64_layout (they are not).
+static bool baseline_fits(int nAgents, int32_t d, int32_t nt, bool adam, int elem_bytes, int* nth, int* G, size_t* lds_bytes) {
+    if (nt < 1 || nt > NOCF_BL_MAX_NT) return false;
+    *nth = (nt * nAgents >= 512) ? 1024 : 256;                          // enough lanes for every (step, agent) of the larger swarms
+    int g = 64;
+    while (g > 1 && g * nt > *nth) g >>= 1;
+    *G = g;
+    *lds_bytes = elem_bytes == 8 ? (size_t)bl64_layout(nt, d, *nth).total * sizeof(double) : (size_t)bl_layout(nt, d, *nth, adam).total * sizeof(float);
+    return *lds_bytes <= 160 * 1024;
+}
+
+int nocf_baseline_max_nt(const NocfProb* prob, int32_t d, int32_t adam, int32_t elem_bytes) {
+    DevProb pb;
+    int rc = fill_prob(prob, d, &pb);
+    if (rc) return rc;
+    if (pb.kind == NOCF_PROB_QUADCOPTER) return NOCF_E_PROB;
+    if (elem_bytes != 4 && elem_bytes != 8) return NOCF_E_SHAPE;
+    int nth, G;
+    size_t bytes;
+    for (int nt = NOCF_BL_MAX_NT; nt >= 1; --nt)                        // (the bytes grow with nt: the first fit from above is the limit)
+        if (baseline_fits(pb.nAgents, d, nt, adam != 0, elem_bytes, &nth, &G, &bytes)) return nt;
+    return NOCF_E_SHAPE;
+}
+
 static int baseline_setup(const NocfProb* prob, int32_t d, int64_t B, int32_t nt, bool adam, DevProb* pb, int* nth, int* G,
                           size_t* lds_bytes) {
     int rc = fill_prob(prob, d, pb);
     if (rc) return rc;
     if (pb->kind == NOCF_PROB_QUADCOPTER) return NOCF_E_PROB;           // baselineQuad.py (L-BFGS, other dynamics) is not this method
-    if (B < 1 || B > 0x7fffffffL || nt < 1 || nt > NOCF_BL_MAX_NT) return NOCF_E_SHAPE;
-    *nth = (nt * pb->nAgents >= 512) ? 1024 : 256;                      // enough lanes for every (step, agent) of the larger swarms
-    int g = 64;
-    while (g > 1 && g * nt > *nth) g >>= 1;
-    *G = g;
-    const BaseLay ly = bl_layout(nt, d, *nth, adam);
-    *lds_bytes = (size_t)ly.total * sizeof(float);
-    if (*lds_bytes > 160 * 1024) return NOCF_E_SHAPE;
+    if (B < 1 || B > 0x7fffffffL) return NOCF_E_SHAPE;
+    if (!baseline_fits(pb->nAgents, d, nt, adam, 4, nth, G, lds_bytes)) return NOCF_E_SHAPE;
     return 0;
 }
 
@@ -2745,6 +2766,149 @@ int nocf_baseline_quad_lbfgs_f32(const NocfProb* prob, int32_t d, int64_t B, int
     if (per_lane <= 4) return launch_quad_lbfgs<4>(qa, B, ldsBytes, st);
     if (per_lane <= 8) return launch_quad_lbfgs<8>(qa, B, ldsBytes, st);
     return launch_quad_lbfgs<16>(qa, B, ldsBytes, st);
+}
+
+// ------------------------------------------------------------------------------------------
+// the two baselines in double precision (nocf_baseline_f64.inc, nocf_baseline_quad_f64.inc)
+// ------------------------------------------------------------------------------------------
+static int prob64_to_dev(const NocfProb64* prob, int32_t d, F64Prob* pb) {
+    if (!prob) return NOCF_E_NULL;
+    NocfProb p32;                                    // the same checks as the fp32 entry (kind / obstacle / agent count)
+    p32.kind = prob->kind; p32.obstacle = prob->obstacle; p32.n_agents = prob->n_agents; p32.training = prob->training;
+    p32.r = prob->r; p32.alph_Q = prob->alph_Q; p32.alph_W = prob->alph_W; p32.mass = prob->mass; p32.grav = prob->grav; p32.xtarget = nullptr;
+    DevProb pb32;
+    int rc = fill_prob(&p32, d, &pb32);
+    if (rc) return rc;
+    *pb = F64Prob{pb32.kind, pb32.obstacle, pb32.nAgents, pb32.training, pb32.agentDim, prob->r, prob->alph_Q, prob->alph_W, prob->mass, prob->grav, prob->xtarget};
+    return 0;
+}
+
+static int baseline_setup_f64(const NocfProb64* prob, int32_t d, int64_t B, int32_t nt, F64Prob* pb, int* nth, int* G, size_t* lds_bytes) {
+    int rc = prob64_to_dev(prob, d, pb);
+    if (rc) return rc;
+    if (pb->kind == NOCF_PROB_QUADCOPTER) return NOCF_E_PROB;
+    if (B < 1 || B > 0x7fffffffL) return NOCF_E_SHAPE;
+    if (!baseline_fits(pb->nAgents, d, nt, false, 8, nth, G, lds_bytes)) return NOCF_E_SHAPE;
+    if (!prob->xtarget) return NOCF_E_NULL;
+    return 0;
+}
+
+int nocf_baseline_eval_f64(const NocfProb64* prob, int32_t d, int64_t B, int32_t nt, double alphG, const double* z0, const double* U,
+                           double* loss, double* grad, double* report, double* traj, void* stream) {
+    if (!z0 || !U || !loss) return NOCF_E_NULL;
+    F64Prob pb;
+    int nth, G;
+    size_t ldsBytes;
+    int rc = baseline_setup_f64(prob, d, B, nt, &pb, &nth, &G, &ldsBytes);
+    if (rc) return rc;
+    Base64Args ba = {};
+    ba.z0 = z0; ba.U = const_cast<double*>(U); ba.loss = loss; ba.grad = grad; ba.report = report; ba.traj = traj;
+    ba.d = d; ba.nt = nt; ba.G = G; ba.h = 1.0 / nt; ba.aG = alphG;
+    hipError_t e = set_lds(baseline_eval_f64_kernel, ldsBytes);
+    if (e) return (int)e;
+    hipLaunchKernelGGL(baseline_eval_f64_kernel, dim3((unsigned)B), dim3(nth), ldsBytes, (hipStream_t)stream, pb, ba);
+    return (int)hipGetLastError();
+}
+
+int nocf_baseline_adam_f64(const NocfProb64* prob, int32_t d, int64_t B, int32_t nt, double alphG, double lr, double beta1, double beta2,
+                           double eps, int32_t step0, int32_t niters, const double* z0, double* U, double* m, double* v, double* best_loss,
+                           double* Ubest, double* loss_hist, void* stream) {
+    if (!z0 || !U || !m || !v || !best_loss || !Ubest) return NOCF_E_NULL;
+    if (niters < 0 || step0 < 0) return NOCF_E_SHAPE;
+    F64Prob pb;
+    int nth, G;
+    size_t ldsBytes;
+    int rc = baseline_setup_f64(prob, d, B, nt, &pb, &nth, &G, &ldsBytes);
+    if (rc) return rc;
+    if (niters == 0) return 0;
+    Base64Args ba = {};
+    ba.z0 = z0; ba.U = U; ba.M = m; ba.V = v; ba.best = best_loss; ba.Ubest = Ubest; ba.hist = loss_hist;
+    ba.d = d; ba.nt = nt; ba.G = G; ba.h = 1.0 / nt; ba.aG = alphG;
+    ba.lr = lr; ba.b1 = beta1; ba.b2 = beta2; ba.eps = eps; ba.step0 = step0; ba.niters = niters;
+    hipError_t e;
+    if (nth == 256 && (long)nt * d <= (long)NOCF_BL64_KR * nth) {       // (every 256-thread launch: nt * agents < 512)
+        e = set_lds(baseline_adam_f64_kernel<true>, ldsBytes);
+        if (e) return (int)e;
+        hipLaunchKernelGGL(baseline_adam_f64_kernel<true>, dim3((unsigned)B), dim3(nth), ldsBytes, (hipStream_t)stream, pb, ba);
+    } else {
+        e = set_lds(baseline_adam_f64_kernel<false>, ldsBytes);
+        if (e) return (int)e;
+        hipLaunchKernelGGL(baseline_adam_f64_kernel<false>, dim3((unsigned)B), dim3(nth), ldsBytes, (hipStream_t)stream, pb, ba);
+    }
+    return (int)hipGetLastError();
+}
+
+static int baseline_quad_setup_f64(const NocfProb64* prob, int32_t d, int64_t B, int32_t nt, int32_t hist, F64Prob* pb, Quad64Args* qa) {
+    if (!prob) return NOCF_E_NULL;
+    if (prob->kind != NOCF_PROB_QUADCOPTER) return NOCF_E_PROB;         // the point agents' baseline is nocf_baseline_*_f64
+    if (d != 12) return NOCF_E_SHAPE;
+    int rc = prob64_to_dev(prob, d, pb);
+    if (rc) return rc;
+    if (B < 1 || B > 0x7fffffffL || nt < 1 || nt > NOCF_BLQ_MAX_NT || hist < 0 || hist > NOCF_BLQ_MAX_HISTORY) return NOCF_E_SHAPE;
+    if (!prob->xtarget) return NOCF_E_NULL;
+    *qa = Quad64Args{};
+    qa->xt = pb->xtarget;
+    qa->nt = nt; qa->hist = hist;
+    qa->h = 1.0 / nt; qa->mass = pb->mass; qa->grav = pb->grav;
+    return 0;
+}
+
+size_t nocf_baseline_quad_workspace_bytes_f64(int64_t B, int32_t nt, int32_t history_size) {
+    if (B < 1 || B > 0x7fffffffL || nt < 1 || nt > NOCF_BLQ_MAX_NT || history_size < 1 || history_size > NOCF_BLQ_MAX_HISTORY) return 0;
+    return (size_t)B * 2 * (size_t)history_size * 4 * (size_t)nt * sizeof(double);
+}
+
+int nocf_baseline_quad_eval_f64(const NocfProb64* prob, int32_t d, int64_t B, int32_t nt, double alphG, const double* z0, const double* U,
+                                double* loss, double* grad, double* report, double* traj, void* stream) {
+    if (!z0 || !U || !loss) return NOCF_E_NULL;
+    F64Prob pb;
+    Quad64Args qa;
+    int rc = baseline_quad_setup_f64(prob, d, B, nt, 0, &pb, &qa);
+    if (rc) return rc;
+    qa.z0 = z0; qa.U = const_cast<double*>(U); qa.loss = loss; qa.grad = grad; qa.report = report; qa.traj = traj;
+    qa.aG = alphG; qa.aGh = alphG * 0.5;
+    const size_t ldsBytes = (size_t)blq_layout(nt, 0).total * sizeof(double);
+    hipError_t e = set_lds(baseline_quad_eval_f64_kernel, ldsBytes);
+    if (e) return (int)e;
+    hipLaunchKernelGGL(baseline_quad_eval_f64_kernel, dim3((unsigned)B), dim3(NOCF_BLQ_WAVE), ldsBytes, (hipStream_t)stream, qa);
+    return (int)hipGetLastError();
+}
+
+extern "C++" {
+template <int E>
+static int launch_quad_lbfgs_f64(const Quad64Args& qa, int64_t B, size_t ldsBytes, hipStream_t st) {
+    hipError_t e = set_lds(baseline_quad_lbfgs_f64_kernel<E>, ldsBytes);
+    if (e) return (int)e;
+    hipLaunchKernelGGL(baseline_quad_lbfgs_f64_kernel<E>, dim3((unsigned)B), dim3(NOCF_BLQ_WAVE), ldsBytes, st, qa);
+    return (int)hipGetLastError();
+}
+}
+
+int nocf_baseline_quad_lbfgs_f64(const NocfProb64* prob, int32_t d, int64_t B, int32_t nt, double alphG, double lr, int32_t max_iter,
+                                 int32_t max_eval, double tolerance_grad, double tolerance_change, int32_t history_size,
+                                 const double* z0, double* U, double* loss, int32_t* n_iter, int32_t* n_evals, int32_t* reason,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    if (!z0 || !U || !loss || !n_iter || !n_evals || !reason || !workspace) return NOCF_E_NULL;
+    if (history_size < 1 || max_iter < 0 || max_eval < 1) return NOCF_E_SHAPE;
+    F64Prob pb;
+    Quad64Args qa;
+    int rc = baseline_quad_setup_f64(prob, d, B, nt, history_size, &pb, &qa);
+    if (rc) return rc;
+    if (workspace_bytes < nocf_baseline_quad_workspace_bytes_f64(B, nt, history_size)) return NOCF_E_WORKSPACE;
+    if (max_iter == 0) return 0;
+    qa.z0 = z0; qa.U = U; qa.loss = loss; qa.n_iter = n_iter; qa.n_evals = n_evals; qa.reason = reason;
+    qa.ws = (double*)workspace;
+    qa.aG = alphG; qa.aGh = alphG * 0.5;
+    qa.max_iter = max_iter; qa.max_eval = max_eval;
+    qa.lr = lr; qa.tol_grad = tolerance_grad; qa.tol_change = tolerance_change;
+    const size_t ldsBytes = (size_t)blq_layout(nt, history_size).total * sizeof(double);
+    const int per_lane = (4 * nt + NOCF_BLQ_WAVE - 1) / NOCF_BLQ_WAVE;  // L-BFGS vector elements per lane
+    hipStream_t st = (hipStream_t)stream;
+    if (per_lane <= 1) return launch_quad_lbfgs_f64<1>(qa, B, ldsBytes, st);
+    if (per_lane <= 2) return launch_quad_lbfgs_f64<2>(qa, B, ldsBytes, st);
+    if (per_lane <= 4) return launch_quad_lbfgs_f64<4>(qa, B, ldsBytes, st);
+    if (per_lane <= 8) return launch_quad_lbfgs_f64<8>(qa, B, ldsBytes, st);
+    return launch_quad_lbfgs_f64<16>(qa, B, ldsBytes, st);
 }
 
 int nocf_selftest_mfma(const float* a, const float* b, int32_t K, float* out, void* stream) {
