@@ -10,7 +10,9 @@ line, appended to `<save>/deploy_times`) plus a batch, and with --do_shock runs 
 (evalOC.py:113-122) through neuraloc_amd.shock for any problem.
 
 --prec double runs the double-precision rollout (nocf_rollout_f64), like the reference's evalOC.py:28-31.
-Differences, on purpose: --make_vid only states that videos are out of scope; --gpu/--batch are additions."""
+Differences, on purpose: --make_vid only states that videos are out of scope; --gpu/--batch are additions, and so is
+--noise SIGMA [--noise_paths R --noise_seed S]: the distribution of the costs over R rollouts of xInit under per-step Brownian
+disturbances (neuraloc_amd.disturb; single precision), one line per quantity and `<save>/figs/eval_<name>_noise.npz`."""
 import argparse
 import os
 import time
@@ -33,12 +35,18 @@ p.add_argument("--make_vid", default=False, action="store_true", help="including
 p.add_argument("--do_shock", default=False, action="store_true", help="including this flag will incorporate shocks")
 p.add_argument("--batch", type=int, default=1024, help="(addition) batch size of the throughput line")
 p.add_argument("--gpu", type=int, default=0, help="(addition) device index")
+p.add_argument("--noise", type=float, default=None, metavar="SIGMA",
+               help="(addition) roll xInit out under Brownian state disturbances sigma dB at every step (neuraloc_amd.noise_study)")
+p.add_argument("--noise_paths", type=int, default=256, metavar="R", help="(addition) noise realisations per start for --noise")
+p.add_argument("--noise_seed", type=int, default=0, metavar="S", help="(addition) seed of the disturbances for --noise")
 
 
 def main(argv=None):
     args = p.parse_args(argv)
     args.alph = [float(item) for item in args.alph.split(",")]
     prec = torch.float64 if args.prec == "double" else torch.float32          # evalOC.py:28-31
+    if args.noise is not None and prec != torch.float32:                     # refused before anything runs or is written
+        raise SystemExit("--noise runs in single precision only (the double-precision rollout takes no disturbance)")
     os.makedirs(os.path.join(args.save, "figs"), exist_ok=True)
     print(args)
     dev = f"cuda:{args.gpu}"
@@ -100,6 +108,19 @@ def main(argv=None):
                 np.savez(os.path.join(args.save, "figs", f"{strTitle}_{tag}.npz"), traj=res["traj"].cpu().numpy(), ctrl=res["ctrl"].cpu().numpy())
                 print("%s at t=0.1: nShock=%d, final state error %.4e" %
                       (tag, res["nShock"], float((res["traj"][0, :, -1] - prob.xtarget.reshape(-1)).norm())))
+        if args.noise is not None:
+            gen = torch.Generator(device=xInit.device).manual_seed(args.noise_seed)
+            st = na.noise_study(xInit, net, prob, nt, args.noise, args.noise_paths, alph=alph, generator=gen)
+            print("noise sigma=%g, %d paths, seed %d: %-4s %11s %11s %11s %11s %11s" %
+                  (args.noise, args.noise_paths, args.noise_seed, "", "mean", "std", "5%", "50%", "95%"))
+            keys = ("mean", "std", "q05", "q50", "q95")
+            for name in ("L+G", "G", "Q", "W"):
+                print("noise %-4s" % name + "".join(" %11.4e" % float(st[name][k][0]) for k in keys))
+            sPath = os.path.join(args.save, "figs", strTitle + "_noise.npz")
+            np.savez(sPath, sigma=args.noise, paths=args.noise_paths, seed=args.noise_seed, persample=st["persample"].cpu().numpy(),
+                     **{f"{name}/{k}": st[name][k].cpu().numpy() for name in ("L+G", "G", "Q", "W") for k in keys})
+            print("saved the noise study to " + sPath)
+            out["noise"] = {name: {k: float(st[name][k][0]) for k in keys} for name in ("L+G", "G", "Q", "W")}
     return out
 
 

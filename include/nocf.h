@@ -170,6 +170,22 @@ int nocf_rollout_means_f32(const NocfPhi* phi, const NocfProb* prob, const float
                            void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * nocf_rollout_means_f32 under per-step state disturbances: W device [nt, n, d], float32, time-major like zFull, contiguous, not modified.
+ * With h, tk and the steppers of nocf_rollout_f32:
+ *     z = [x, 0, 0, 0, 0]; for k in 0 .. nt-1: z = step(z, tk, tk + h); z[:, :d] += W[k]; (zFull[k+1] = z, ctrlFull[k+1] from grad Phi at
+ *     the displaced state and the step's start time); tk += h
+ * and the terminal terms at the displaced z(T): additive noise in the Euler-Maruyama position.  The four cost columns are not displaced;
+ * W[nt-1] lands on the terminal state and nothing reacts to it.  W == 0 gives the undisturbed call's outputs on the same kernel.
+ * Dispatch: the register-resident small-network kernel, then the one-CU kernel, then the per-tile kernel -- never the split-role kernel
+ * (m = 512 networks run on the per-tile kernel here).  float32 only; an evaluation (nothing is recorded for an adjoint); no segments.
+ * W == NULL: NOCF_E_NULL.  Every refusal returns before anything is enqueued.
+ */
+int nocf_rollout_disturbed_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, const float* W, int64_t n,
+                               double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                               float* z_out, float* persample, float* cost_sums, float* cost_means, float* zFull, float* ctrlFull,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Several rollouts that differ only in their start time and step count, in ONE launch (round 5): the second segments of a shock sweep.
  * The reference's shocked rollout (src/plotter.py:815-824, driven by evalOC.py:113-122) is OCflow on [0, t_s] with int(t_s nt) steps, the
  * shock added to the end state, and OCflow on [t_s, 1] with 1 + nt - int(t_s nt) steps; a sweep over shock times (BASELINE config 5) repeats

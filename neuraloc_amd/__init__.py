@@ -9,8 +9,10 @@ from .distributed import OCflow_sharded, shard_rows, reduce_cost_sums
 from ._lib import check_errors
 from .baseline import baseline_loss, baseline_report, baseline_adam_steps, solve_baseline
 from .baseline_quad import quad_baseline_loss, quad_baseline_report, quad_initial_guess, solve_baseline_quad
+from .disturb import disturbed_rollout, brownian_disturbances, noise_study
 
 __all__ = ["Phi", "ResNN", "antiderivTanh", "derivTanh", "OCflow", "ocG", "Cross2D", "SwarmTraj",
            "Quadcopter", "initProb", "resample", "OCflow_sharded", "shard_rows", "reduce_cost_sums", "check_errors",
            "baseline_loss", "baseline_report", "baseline_adam_steps", "solve_baseline",
-           "quad_baseline_loss", "quad_baseline_report", "quad_initial_guess", "solve_baseline_quad"]
+           "quad_baseline_loss", "quad_baseline_report", "quad_initial_guess", "solve_baseline_quad",
+           "disturbed_rollout", "brownian_disturbances", "noise_study"]

@@ -159,4 +159,7 @@ struct RollArgs {
     // q and w of that state, 0; terminal block: Phi - alph0 G, 0, 0, 0).  Null: no tape.
     float* tapeU1; float* tapeSc;
     SegTab seg;
+    // per-step state disturbances (include/nocf.h, nocf_rollout_disturbed_f32): W [nt][n][d], time-major; after step k the state rows take
+    // z[:, :d] += W[k].  Read only by the DIST instantiations of the lane / one-CU / per-tile kernels; null everywhere else.
+    const float* dist;
 };

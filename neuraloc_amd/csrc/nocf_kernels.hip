@@ -995,7 +995,11 @@ __device__ void ctrl_write(const Ctx& c, const DevPlan& pl, const DevProb& pb, f
 // the rollout kernel: src/OCflow.py:7-95 for T samples per workgroup
 // ------------------------------------------------------------------------------------------
 
-template <int S>
+// DIST: the disturbed rollout (RollArgs::dist, W [nt][n][d]): behind step k the state rows take z[:, :d] += W[k] where the step's z is written
+// back.  The entries are loaded in the write-back sweep itself, not at the top of the step: this kernel runs at its register budget, and two
+// registers held across phi_eval turned 3 spilled registers into 59 on swarm50's instantiation.  The sweep is followed by the physics phase, and
+// one exposed load per step is small beside the step's four evaluations.
+template <int S, bool DIST = false>
 __device__ __forceinline__ void rollout_body(const DevPlan& pl, const DevPlan* __restrict__ plp, const DevProb& pb,
                                              const float* __restrict__ ws, const RollArgs& ra) {
     Ctx c;
@@ -1044,6 +1048,13 @@ __device__ __forceinline__ void rollout_body(const DevPlan& pl, const DevPlan* _
     const int nstage = (ra.stepper == NOCF_RK4) ? 4 : 1;
     const int nsub = nstage + (ra.zFull ? 1 : 0);
     const bool quad = (pb.kind == NOCF_PROB_QUADCOPTER);
+    // disturbance of item j of step k's write-back sweep: point agents sweep the T*d state components (the tile's rows of W[k] are one
+    // contiguous run), quadcopters the T*(d+4) components of z
+    auto dist_at = [&](int k, int j) -> float {
+        if (!quad) return (j < T * d && (row0 * d + j) < ra.n * d) ? ra.dist[((long)k * ra.n + row0) * d + j] : 0.f;
+        const int t = j / (d + 4), i = j - t * (d + 4);
+        return (j < T * (d + 4) && i < d && row0 + t < ra.n) ? ra.dist[((long)k * ra.n + row0 + t) * d + i] : 0.f;
+    };
     // One call site for phi_eval: steps k < nt run the RK stages (plus, with intermediates, the
     // control evaluation); the extra pass k == nt is the terminal evaluation.
     for (int k = 0; k <= ra.nt; ++k) {
@@ -1116,6 +1127,9 @@ __device__ __forceinline__ void rollout_body(const DevPlan& pl, const DevPlan* _
                     else if (st == 1) { ZA[t * ZLD + i] += c26 * K; xs = z0 + 0.5f * K; }
                     else if (st == 2) { ZA[t * ZLD + i] += c26 * K; xs = z0 + K; }
                     else { xs = ZA[t * ZLD + i] + c16 * K; Z0[t * ZLD + i] = xs; }
+                    if constexpr (DIST) {
+                        if (st == nstage - 1) { xs += dist_at(k, j); Z0[t * ZLD + i] = xs; }
+                    }
                     SB[t * pl.LDs + i] = xs;
                 }
                 if (c.tid < T) SB[c.tid * pl.LDs + d] = (float)tnx;
@@ -1138,7 +1152,7 @@ __device__ __forceinline__ void rollout_body(const DevPlan& pl, const DevPlan* _
             // BEFORE the physics (into XN = DZ: the physics still reads the current x from SB) and the tail
             // below overlaps three jobs on different waves
             float* XN = DZ;
-            auto rk = [&](int t, int i, float dzi) {
+            auto rk = [&](int t, int i, float dzi, float w = 0.f) {
                 const float K = hs * dzi;
                 const float z0 = Z0[t * ZLD + i];
                 float xs;
@@ -1147,6 +1161,9 @@ __device__ __forceinline__ void rollout_body(const DevPlan& pl, const DevPlan* _
                 else if (st == 1) { ZA[t * ZLD + i] += c26 * K; xs = z0 + 0.5f * K; }
                 else if (st == 2) { ZA[t * ZLD + i] += c26 * K; xs = z0 + K; }
                 else { xs = ZA[t * ZLD + i] + c16 * K; Z0[t * ZLD + i] = xs; }
+                if constexpr (DIST) {
+                    if (last && i < d) { xs += w; Z0[t * ZLD + i] = xs; }
+                }
                 if (i < d) { if (quad) SB[t * pl.LDs + i] = xs; else XN[t * ZLD + i] = xs; }
                 if (last && ra.zFull && row0 + t < ra.n)
                     ra.zFull[((long)(k + 1) * ra.n + row0 + t) * (d + 4) + i] = xs;
@@ -1155,7 +1172,8 @@ __device__ __forceinline__ void rollout_body(const DevPlan& pl, const DevPlan* _
                 for (int j = c.tid; j < T * d; j += c.nthreads) {
                     int t = 0, i = j;
                     while (i >= d) { i -= d; ++t; }
-                    rk(t, i, -G[t * pl.GLD + i]);
+                    if constexpr (DIST) rk(t, i, -G[t * pl.GLD + i], last ? dist_at(k, j) : 0.f);
+                    else rk(t, i, -G[t * pl.GLD + i]);
                 }
             }
             physics_sums(c, pl, pb, xpre);                  // ends with a barrier
@@ -1224,7 +1242,11 @@ __device__ __forceinline__ void rollout_body(const DevPlan& pl, const DevPlan* _
                         DZ[s * ZLD + d + 3] = cs.W;
                     }
                     __syncthreads();
-                    for (int j = c.tid; j < T * (d + 4); j += c.nthreads) { const int t = j / (d + 4), i = j - t * (d + 4); rk(t, i, DZ[t * ZLD + i]); }
+                    for (int j = c.tid; j < T * (d + 4); j += c.nthreads) {
+                        const int t = j / (d + 4), i = j - t * (d + 4);
+                        if constexpr (DIST) rk(t, i, DZ[t * ZLD + i], last ? dist_at(k, j) : 0.f);
+                        else rk(t, i, DZ[t * ZLD + i]);
+                    }
                     if (c.tid < T) SB[c.tid * pl.LDs + d] = (float)tnext;
                 }
             } else {
@@ -1283,13 +1305,13 @@ __device__ __forceinline__ void rollout_body(const DevPlan& pl, const DevPlan* _
 
 // DynPlan: the plan is the record in the workspace (fields are scalar loads, not 60 pinned SGPRs).
 // FixedPlan<...>: the plan is a compile-time constant of that shape.
-template <int S, class SP>
+template <int S, class SP, bool DIST = false>
 __global__ void __launch_bounds__(NOCF_MAXTHREADS) rollout_kernel(const DevPlan* __restrict__ plp, DevProb pb, const float* __restrict__ ws, RollArgs ra) {
     if constexpr (SP::fixed) {
         constexpr DevPlan plc = SP::make();
-        rollout_body<S>(plc, plp, pb, ws, ra);
+        rollout_body<S, DIST>(plc, plp, pb, ws, ra);
     } else {
-        rollout_body<S>(*plp, plp, pb, ws, ra);
+        rollout_body<S, DIST>(*plp, plp, pb, ws, ra);
     }
 }
 
@@ -1953,7 +1975,7 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
                         float* z_out, float* persample, float* cost_sums, float* zFull, float* ctrlFull,
                         void* workspace, size_t workspace_bytes, void* stream, float* s_all,
                         float* act = nullptr, int32_t* act_recorded = nullptr, float* tapeU1 = nullptr, float* tapeSc = nullptr,
-                        const SegTab* seg = nullptr, float* cost_means = nullptr) {
+                        const SegTab* seg = nullptr, float* cost_means = nullptr, const float* dist = nullptr) {
     if (act_recorded) *act_recorded = 0;
     int rc = check_phi(phi);
     if (rc) return rc;
@@ -1962,6 +1984,10 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
     if (stepper != NOCF_RK4 && stepper != NOCF_RK1) return NOCF_E_STEPPER;
     if ((zFull != nullptr) != (ctrlFull != nullptr)) return NOCF_E_NULL;
     if (cost_sums && !persample) return NOCF_E_NULL;
+    // a disturbed rollout (nocf_rollout_disturbed_f32) is an evaluation: it records nothing for an adjoint and takes no segments.  No
+    // exported entry point passes either combination today: these two lines guard the ones to come
+    if (dist && (s_all || act || tapeSc)) return NOCF_E_NULL;
+    if (dist && seg) return NOCF_E_SHAPE;
     DevProb pb;
     rc = fill_prob(prob, phi->d, &pb);
     if (rc) return rc;
@@ -1984,6 +2010,7 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
     if (seg) ra.seg = *seg;                       // (several time segments in one launch: the one-CU kernel only, NOCF_E_SHAPE otherwise)
     ra.act = nullptr; ra.actRows = 0;             // (only the split-role kernel records activations: set below)
     ra.tapeU1 = nullptr; ra.tapeSc = nullptr;
+    ra.dist = dist;                               // (disturbed rollouts: lane, then one-CU, then per-tile; never the split-role kernel)
     hipError_t e;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     const unsigned* errp = nullptr;
@@ -2003,7 +2030,7 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
         // one launch per call (round 6, NOCF_LANE_ONE=1): with a ticket word the kernel's last workgroup forms the sums (and means) itself.
         // OFF by default -- measured on the MI355X (profiles/r6/07_lane_one_launch.txt): the agent-scope release every workgroup needs in front of
         // its ticket is an L2 write-back (buffer_wbl2 sc1), 256-512 of them cost 7-15 us, more than the 4-us kernel and launch gap they replace
-        unsigned* ticket = (cost_sums && !s_all && env_int("NOCF_LANE_ONE", 0) != 0) ? lane_ticket(st) : nullptr;
+        unsigned* ticket = (cost_sums && !s_all && !dist && env_int("NOCF_LANE_ONE", 0) != 0) ? lane_ticket(st) : nullptr;
         la.sums = ticket ? cost_sums : nullptr; la.ticket = ticket;
         la.means = mean_args.means; la.a0 = mean_args.a0; la.a3 = mean_args.a3; la.a4 = mean_args.a4; la.a5 = mean_args.a5;
         const int grid = (int)((n + 3) / 4);
@@ -2014,7 +2041,8 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
             (void)hipEventRecord(ev0, st);
         }
         const size_t laneLds = ticket ? (size_t)(256 * 7 * 8 + 16) : 0;      // (the last-workgroup reduction's scratch: only with a ticket)
-#define NOCF_LANE_LAUNCH(MPV, DPV) do { if (s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true>), dim3(grid), dim3(256), 0, st, la, pb, ra); \
+#define NOCF_LANE_LAUNCH(MPV, DPV) do { if (dist) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, true>), dim3(grid), dim3(256), 0, st, la, pb, ra); \
+                                         else if (s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true>), dim3(grid), dim3(256), 0, st, la, pb, ra); \
                                          else if (ticket) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, true>), dim3(grid), dim3(256), laneLds, st, la, pb, ra); \
                                          else hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false>), dim3(grid), dim3(256), 0, st, la, pb, ra); } while (0)
         if (MPsel == 16) { if (DPsel == 8) { NOCF_LANE_LAUNCH(16, 8); } else if (DPsel == 16) { NOCF_LANE_LAUNCH(16, 16); } else { NOCF_LANE_LAUNCH(16, 32); } }
@@ -2022,7 +2050,7 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
 #undef NOCF_LANE_LAUNCH
         e = hipGetLastError();
         if (e) return (int)e;
-        g_last_kernel = "rollout_lane_kernel";
+        g_last_kernel = dist ? "rollout_lane_kernel<dist>" : "rollout_lane_kernel";
         if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
         if (cost_sums && !ticket) {
             hipLaunchKernelGGL(cost_sum_kernel, dim3(1), dim3(256), 0, st, persample, (long)n, cost_sums, errp, mean_args);
@@ -2034,7 +2062,7 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
 #ifndef NOCF_JIT_ONLY
     // split-role weight-stationary kernel (nocf_duo.hip): wide two-layer networks (m = 512) on point-agent problems, any batch
     // size (chunks of 2048 rows), evaluation and the recording forward of training
-    if (env_int("NOCF_DUO", 1) != 0 && !seg) {
+    if (env_int("NOCF_DUO", 1) != 0 && !seg && !dist) {
         if (g_prof_on) {
             if (hipEventCreate(&ev0) || hipEventCreate(&ev1)) return (int)hipErrorUnknown;
         }
@@ -2077,7 +2105,7 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
         hipLaunchKernelGGL(mono_pack_kernel, dim3(64), dim3(256), 0, st, mpl, P, ws);
         const size_t ldsBytes = (size_t)mpl.pp.ldsFloats * 4;
         const void* fk = nullptr;
-#define NOCF_MONO_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) fk = s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false>);
+#define NOCF_MONO_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) fk = dist ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, true>) : s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false>);
         MONO_SHAPES(NOCF_MONO_PICK)
 #undef NOCF_MONO_PICK
         e = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes); if (e) return (int)e;
@@ -2094,7 +2122,7 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
         e = hipLaunchKernel(fk, dim3((int)((n + 15) / 16)), dim3(256), args, ldsBytes, st); if (e) return (int)e;
         ra.act = nullptr; ra.actRows = 0;
         if (mono_rec && act_recorded) *act_recorded = 1;
-        g_last_kernel = "rollout_mono_kernel";
+        g_last_kernel = dist ? "rollout_mono_kernel<dist>" : "rollout_mono_kernel";
         e = hipGetLastError();
         if (e) return (int)e;
         if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
@@ -2128,9 +2156,13 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
             // compile-time one bit for bit, so the environment knobs and odd shapes always get the generic kernel
             const void* fk = nullptr;
 #define NOCF_TRY_FIXED(D, M, NTH, R, NAG) \
-            if (!fk && plan_is<FixedPlan<D, M, NTH, R, NAG, 0>>(pl)) fk = reinterpret_cast<const void*>(rollout_kernel<1, FixedPlan<D, M, NTH, R, NAG, 0>>);
+            if (!fk && plan_is<FixedPlan<D, M, NTH, R, NAG, 0>>(pl)) fk = dist ? reinterpret_cast<const void*>(rollout_kernel<1, FixedPlan<D, M, NTH, R, NAG, 0>, true>) \
+                                                                              : reinterpret_cast<const void*>(rollout_kernel<1, FixedPlan<D, M, NTH, R, NAG, 0>>);
             FIXED_SHAPES(NOCF_TRY_FIXED)
             FIXED_SHAPES_EXTRA(NOCF_TRY_FIXED)
+#undef NOCF_TRY_FIXED
+#define NOCF_TRY_FIXED(D, M, NTH, R, NAG) \
+            if (!fk && plan_is<FixedPlan<D, M, NTH, R, NAG, 0>>(pl)) fk = reinterpret_cast<const void*>(rollout_kernel<1, FixedPlan<D, M, NTH, R, NAG, 0>>);
             if (s_all) { FIXED_SHAPES_TRAIN(NOCF_TRY_FIXED) }
 #undef NOCF_TRY_FIXED
             if (fk) {
@@ -2138,12 +2170,20 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
                 void* args[] = {(void*)&plp, (void*)&pb, (void*)&ws, (void*)&ra};
                 e = hipLaunchKernel(fk, dim3(grid), dim3(block), args, ldsBytes, st); if (e) return (int)e;
                 launched = true;
-                g_last_kernel = "rollout_kernel<shape-specialised>";
+                g_last_kernel = dist ? "rollout_kernel<shape-specialised, dist>" : "rollout_kernel<shape-specialised>";
                 if (env_int("NOCF_DEBUG", 0)) fprintf(stderr, "[nocf] shape-specialised rollout kernel\n");
             }
         }
-        if (!launched) g_last_kernel = "rollout_kernel<generic>";
-        if (!launched) switch (pl.T / 4) {
+        if (!launched) g_last_kernel = dist ? "rollout_kernel<generic, dist>" : "rollout_kernel<generic>";
+        if (!launched && dist) switch (pl.T / 4) {
+            case 1: e = set_lds(rollout_kernel<1, DynPlan, true>, ldsBytes); if (e) return (int)e;
+                    hipLaunchKernelGGL((rollout_kernel<1, DynPlan, true>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
+            case 2: e = set_lds(rollout_kernel<2, DynPlan, true>, ldsBytes); if (e) return (int)e;
+                    hipLaunchKernelGGL((rollout_kernel<2, DynPlan, true>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
+            default: e = set_lds(rollout_kernel<4, DynPlan, true>, ldsBytes); if (e) return (int)e;
+                    hipLaunchKernelGGL((rollout_kernel<4, DynPlan, true>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
+        }
+        else if (!launched) switch (pl.T / 4) {
             case 1: e = set_lds(rollout_kernel<1, DynPlan>, ldsBytes); if (e) return (int)e;
                     hipLaunchKernelGGL((rollout_kernel<1, DynPlan>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
             case 2: e = set_lds(rollout_kernel<2, DynPlan>, ldsBytes); if (e) return (int)e;
@@ -2178,6 +2218,16 @@ int nocf_rollout_means_f32(const NocfPhi* phi, const NocfProb* prob, const float
     if (cost_means && !cost_sums) return NOCF_E_NULL;
     return rollout_impl(phi, prob, x, n, t0, t1, nt, stepper, alph, z_out, persample, cost_sums, zFull, ctrlFull,
                         workspace, workspace_bytes, stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, cost_means);
+}
+
+int nocf_rollout_disturbed_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, const float* W, int64_t n,
+                               double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                               float* z_out, float* persample, float* cost_sums, float* cost_means, float* zFull, float* ctrlFull,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+    if (!W) return NOCF_E_NULL;
+    if (cost_means && !cost_sums) return NOCF_E_NULL;
+    return rollout_impl(phi, prob, x, n, t0, t1, nt, stepper, alph, z_out, persample, cost_sums, zFull, ctrlFull,
+                        workspace, workspace_bytes, stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, cost_means, W);
 }
 
 int nocf_rollout_segments_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n,

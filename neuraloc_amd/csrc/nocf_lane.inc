@@ -29,7 +29,9 @@ struct LaneArgs {
 // REC: the training variant also stores every stage input (RollArgs::sAll); the evaluation variant carries no trace of it
 // ONE: the instantiation WITH the last-workgroup reduction (NOCF_LANE_ONE=1, evaluation only).  Its own instantiation because the reduction's code
 // at the kernel's end costs the register-resident rollout in front of it 5-7 % (swap2 0.084 -> 0.090 ms) even when it is never taken
-template <int MP, int DP, bool REC, bool ONE = false>
+// DIST: the disturbed rollout (RollArgs::dist, W [nt][n][d]): lane j < d adds W[k][sample][j] to its component behind step k.  The load is
+// issued at the top of the step -- its address does not depend on the step -- and consumed behind the last stage
+template <int MP, int DP, bool REC, bool ONE = false, bool DIST = false>
 __global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb pb, RollArgs ra) {
     const int lane = threadIdx.x & 63;
     const long sample = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -166,6 +168,8 @@ __global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb 
         const double t1k = tk + ra.h;
         const double hsd = t1k - tk;                      // stepRK4 re-derives h = t1 - t0 (src/OCflow.py:170)
         const float hs = (float)hsd;
+        float wk = 0.f;
+        if constexpr (DIST) wk = lane < d ? ra.dist[((long)k * ra.n + row) * d + lane] : 0.f;
         // training: the stage input s = [x, t] of every evaluation goes to sAll[(k*nstage + st)][sample][0..d] (one row per lane group)
         auto record = [&](int st, int nstage, float s) {
             if (REC && ra.sAll && live && lane <= d) ra.sAll[(((long)k * nstage + st) * ra.n + sample) * (d + 1) + lane] = s;
@@ -196,6 +200,7 @@ __global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb 
             record(0, 1, s);
             z = z + hs * rhs(s, grad_phi(s, false, dummy));
         }
+        if constexpr (DIST) z += wk;                       // (lanes >= d hold 0: the four cost components are not displaced)
         tk += ra.h;
         if (ra.zFull) {
             // src/OCflow.py:51-55: z_{k+1}, and the control from grad Phi at (x_{k+1}, tk - h)

@@ -216,7 +216,10 @@ __device__ __forceinline__ void mono_sincos(float x, float& sn, float& cs) {
 }
 
 // REC: the training variant (stage inputs RollArgs::sAll, activation record RollArgs::act); the evaluation variant carries no trace of it
-template <int KBM, int KBD, bool REC>
+// DIST: the disturbed rollout (RollArgs::dist, W [nt][n][d]): behind step k the state rows take z[:, :d] += W[k] where the step's z is written
+// back (in front of the zFull store and of the control evaluation).  Each thread loads the entries of its own components at the top of the step
+// (KBD + 1 registers at most; one for singlequad) and adds them behind the last stage
+template <int KBM, int KBD, bool REC, bool DIST = false>
 __global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __restrict__ mpp, DevProb pb, float* ws, RollArgs ra) {
     constexpr int MT = (KBM + 3) / 4;              // hidden M-tiles per wave: tiles w, w+4, ...
     constexpr int T = 16;
@@ -337,6 +340,26 @@ __global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __res
             if (tid < T) SB[tid * LDs + d] = (float)ra.t1;     // src/OCflow.py:62
             sf_ready = false;                                  // (the fragments carry the last step's own end time)
             __syncthreads();
+        }
+        constexpr int NDW = KBD + 1;                           // T (d + 4) <= 256 KBD + 48 components over 256 threads
+        float wpre[NDW];
+        if constexpr (DIST) {
+#pragma unroll
+            for (int q = 0; q < NDW; ++q) wpre[q] = 0.f;
+            if (!fin) {
+                const float* wk = ra.dist + ((long)k * ra.n + row0) * d;
+                if (quad1) {
+                    const int s_ = tid >> 4, j = tid & 15;
+                    if (j < d && row0 + s_ < ra.n) wpre[0] = wk[s_ * d + j];
+                } else {
+#pragma unroll
+                    for (int q = 0; q < NDW; ++q) {
+                        const int j = tid + 256 * q;
+                        const int t = j / (d + 4), i = j - t * (d + 4);
+                        if (j < T * (d + 4) && i < d && row0 + t < ra.n) wpre[q] = wk[t * d + i];
+                    }
+                }
+            }
         }
         for (int st = 0; st < (fin ? 1 : nsub); ++st) {
 #ifdef NOCF_STAMPS
@@ -597,7 +620,11 @@ __global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __res
                     const float rk_wa = (nstage == 1) ? 1.f : ((st == 0 || st == 3) ? c16 : c26);
                     const float rk_wx = (st < 2) ? 0.5f : 1.f;
                     float xs_;
-                    if (last) { xs_ = (nstage == 1 ? qz0 : qzA) + rk_wa * K; qz0 = xs_; }
+                    if (last) {
+                        xs_ = (nstage == 1 ? qz0 : qzA) + rk_wa * K;
+                        if constexpr (DIST) xs_ += wpre[0];                    // (j >= 12: 0)
+                        qz0 = xs_;
+                    }
                     else { qzA = (st == 0 ? qz0 : qzA) + rk_wa * K; xs_ = qz0 + rk_wx * K; }
                     const float tn = (float)tnext;
                     __builtin_amdgcn_wave_barrier();                           // every lane of the sample has read x before it is overwritten
@@ -635,6 +662,7 @@ __global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __res
                 }
                 __syncthreads();
                 TL(c, 10);
+                int it = 0;
                 for (int j = tid; j < T * (d + 4); j += 256) {
                     const int t = j / (d + 4), i = j - t * (d + 4);
                     const float dzi = (i < d && !quad) ? -Gl[t * GLD + i] : DZ[t * ZLD + i];      // point agents: dx = -p
@@ -646,6 +674,16 @@ __global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __res
                     else if (st == 1) { ZA[t * ZLD + i] += c26 * K; xs = z0 + 0.5f * K; }
                     else if (st == 2) { ZA[t * ZLD + i] += c26 * K; xs = z0 + K; }
                     else { xs = ZA[t * ZLD + i] + c16 * K; Z0[t * ZLD + i] = xs; }
+                    if constexpr (DIST) {
+                        if (last) {
+                            float w = 0.f;
+#pragma unroll
+                            for (int q = 0; q < NDW; ++q) w = (it == q) ? wpre[q] : w;
+                            xs += w;
+                            Z0[t * ZLD + i] = xs;
+                        }
+                        ++it;
+                    }
                     if (i < d) SB[t * LDs + i] = xs;
                     if (last && ra.zFull && row0 + t < ra.n) ra.zFull[((sg_slot + k + 1) * ra.n + row0 + t) * (d + 4) + i] = xs;
                 }

@@ -1,0 +1,171 @@
+"""Rollouts of the feedback controller under per-step disturbances.
+
+u = -grad_p H(x, grad Phi(x, t)) reacts to wherever the state is.  shock.py displaces the state once; here it is displaced behind EVERY
+step, by a caller-supplied W [nt, n, d] (time-major like the kernels' zFull):
+
+    z = [x, 0, 0, 0, 0];  for k in 0 .. nt-1:  z = step(z, tk, tk + h);  z[:, :d] += W[k];  tk += h;   terminal terms at the displaced z(T)
+
+-- additive noise in the Euler-Maruyama position.  The whole disturbed rollout is ONE launch (nocf_rollout_disturbed_f32): the lane, one-CU
+and per-tile kernels take W as one more input.  The split-role kernel does not: m = 512 point-agent networks run on the per-tile kernel here.
+Single precision, evaluation only (no autograd, no recording forward), no segments.  There is no CPU or eager-torch fallback."""
+import ctypes as C
+import math
+
+import torch
+
+from . import _lib
+from .OCflow import _STEPPERS
+
+_ARGTYPES = [C.POINTER(_lib.NocfPhi), C.POINTER(_lib.NocfProb), C.c_void_p, C.c_void_p, C.c_int64,
+             C.c_double, C.c_double, C.c_int32, C.c_int32, _lib.fp,
+             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+             C.c_void_p, C.c_size_t, C.c_void_p]
+
+
+def _entry(L):
+    """nocf_rollout_disturbed_f32 of library L with its prototype set, or None when L does not export it"""
+    if not hasattr(L, "nocf_rollout_disturbed_f32"):
+        return None
+    f = L.nocf_rollout_disturbed_f32
+    if f.argtypes is None:
+        f.restype = C.c_int
+        f.argtypes = _ARGTYPES
+    return f
+
+
+def disturbed_rollout(x, Phi, prob, nt, W, tspan=(0., 1.), alph=None, stepper="rk4", intermediates=False):
+    """
+    :param x:   nex-by-d initial states on the MI355X, float32
+    :param W:   nt-by-nex-by-d float32 device tensor: W[k] is added to the state (not to the four cost columns) behind step k;
+                W[nt-1] lands on the terminal state.  Not modified.
+    :param alph: 6 multipliers (default: Phi.alph)
+    :return: dict with
+        Jc, cs      the means, as OCflow returns them
+        persample   nex-by-7 table [L, G, HJt, HJfin, HJgrad, Q, W]
+        z_final     nex-by-(d+4)
+        traj, ctrl  with intermediates: nex-by-(d+4)-by-(nt+1) and nex-by-a-by-(nt+1), the reference's layout (ctrl[:, :, k+1] from
+                    grad Phi at the displaced state and the step's start time, like src/OCflow.py:53)
+    """
+    alph = list(Phi.alph if alph is None else alph)
+    for name, t in (("x", x), ("W", W)):
+        if isinstance(t, torch.Tensor) and t.dtype == torch.float64:
+            raise RuntimeError(f"disturbed_rollout: {name} is float64; the disturbed rollout is single precision only "
+                               "(the double-precision kernel takes no disturbance)")
+    x = _lib.require_device_f32(x, "x")
+    W = _lib.require_device_f32(W, "W")
+    if x.dim() != 2:
+        raise ValueError("x must be nex-by-d")
+    n, d = x.shape
+    if d != Phi.d:
+        raise ValueError(f"x has d={d} but Phi was built for d={Phi.d}")
+    if int(nt) < 1:
+        raise ValueError("nt must be >= 1")
+    if n < 1:
+        raise ValueError("x has no rows")
+    if tuple(W.shape) != (int(nt), n, d):
+        raise ValueError(f"W must be nt-by-nex-by-d = {(int(nt), n, d)}, got {tuple(W.shape)}")
+    if W.device != x.device:
+        raise ValueError("x and W must be on the same device")
+    if stepper not in _STEPPERS:
+        raise ValueError(f"stepper must be 'rk4' or 'rk1', got {stepper!r}")
+    if len(alph) < 6:
+        raise ValueError("alph needs 6 entries")
+    Phi._guard_no_autograd(x, "disturbed_rollout")
+    with torch.no_grad():
+        _lib.check_errors()
+        phi_st, keep1, ws = Phi._c_struct(n)
+        prob_st, keep2 = prob._c_struct(x.device)
+        dev = x.device
+        persample = torch.empty(n, 7, dtype=torch.float32, device=dev)
+        sums = torch.empty(8, dtype=torch.float32, device=dev)
+        means = torch.empty(8, dtype=torch.float32, device=dev)
+        z_final = torch.empty(n, d + 4, dtype=torch.float32, device=dev)
+        zFull = ctrlFull = None
+        if intermediates:
+            cdim = _lib.lib().nocf_ctrl_dim(C.byref(prob_st), d)
+            zFull = torch.empty(nt + 1, n, d + 4, dtype=torch.float32, device=dev)
+            ctrlFull = torch.empty(nt + 1, n, cdim, dtype=torch.float32, device=dev)
+        alph_c = (C.c_float * 6)(*[float(a) for a in alph[:6]])
+        with torch.cuda.device(dev):
+            L = _lib.lib_for(Phi.d, Phi.m, Phi.nTh, phi_st.r, prob_st.n_agents, fwd=prob_st.kind != _lib.PROB_QUADCOPTER)
+            f = _entry(L)
+            if f is None:                                  # a per-shape library cached by an older build: the shipped library has the entry
+                L = _lib.lib()
+                f = _entry(L)
+            if f is None:
+                raise RuntimeError("disturbed_rollout: the HIP library does not export nocf_rollout_disturbed_f32; rebuild it")
+            rc = f(C.byref(phi_st), C.byref(prob_st), _lib.ptr(x), _lib.ptr(W), n,
+                   float(tspan[0]), float(tspan[1]), int(nt), _STEPPERS[stepper], alph_c,
+                   _lib.ptr(z_final), _lib.ptr(persample), _lib.ptr(sums), _lib.ptr(means), _lib.ptr(zFull), _lib.ptr(ctrlFull),
+                   _lib.ptr(ws), ws.numel() * ws.element_size(), _lib.stream_ptr(dev))
+        _lib.check(rc, "nocf_rollout_disturbed_f32")
+        _lib.track_rollout_status(L, dev, "disturbed_rollout")
+        out = {"Jc": means[7], "cs": [means[i] for i in range(7)], "persample": persample, "z_final": z_final}
+        if intermediates:
+            _lib.check_errors(sync=True)                   # consumed on the host (plots, files): a failed launch raises here
+            out["traj"], out["ctrl"] = zFull.permute(1, 2, 0), ctrlFull.permute(1, 2, 0)
+    return out
+
+
+def brownian_disturbances(nt, n, d, sigma, tspan=(0., 1.), generator=None, device=None, mask=None):
+    """sigma * sqrt(h) * randn, time-major [nt, n, d], float32: the increments of sigma dB over steps of h = (tspan[1] - tspan[0]) / nt.
+    sigma: a float or a [d] tensor; mask [d]: coordinates with mask == 0 are not disturbed (the quadcopter's velocities only, say);
+    generator: a torch.Generator of `device` (default: that device's global one)."""
+    if int(nt) < 1 or int(n) < 1 or int(d) < 1:
+        raise ValueError("nt, n and d must be >= 1")
+    h = (float(tspan[1]) - float(tspan[0])) / int(nt)
+    if not h > 0:
+        raise ValueError("tspan must have positive length")
+    if device is None:
+        device = generator.device if generator is not None else "cpu"
+    W = torch.randn(int(nt), int(n), int(d), generator=generator, device=device, dtype=torch.float32)
+    scale = torch.as_tensor(sigma, dtype=torch.float32, device=W.device)
+    if scale.dim() > 1 or (scale.dim() == 1 and scale.numel() != int(d)):
+        raise ValueError("sigma must be a float or a [d] tensor")
+    W = W * (scale * math.sqrt(h))
+    if mask is not None:
+        mk = torch.as_tensor(mask, device=W.device)
+        if mk.numel() != int(d):
+            raise ValueError("mask must have d entries")
+        W = W * (mk.reshape(-1) != 0).to(torch.float32)
+    return W.contiguous()
+
+
+QUANTILES = (0.05, 0.5, 0.95)
+
+
+def path_statistics(v):
+    """v [starts, paths] -> dict mean, std (unbiased; 0 for one path), q05, q50, q95, each [starts]"""
+    q = torch.quantile(v, torch.tensor(QUANTILES, dtype=v.dtype, device=v.device), dim=1)
+    std = v.std(dim=1) if v.shape[1] > 1 else torch.zeros_like(v[:, 0])
+    return {"mean": v.mean(dim=1), "std": std, "q05": q[0], "q50": q[1], "q95": q[2]}
+
+
+def noise_study(x, Phi, prob, nt, sigma, paths, tspan=(0., 1.), alph=None, stepper="rk4", generator=None, mask=None, max_rows=1 << 16):
+    """The distribution of the costs over `paths` Brownian disturbances of every start: each start is repeated `paths` times as rows of one
+    batch (start-major: row i * paths + p), in chunks of whole starts of at most max_rows rows (max_rows < paths is a ValueError), one launch
+    per chunk.  The disturbances are drawn chunk by chunk from `generator` (brownian_disturbances(nt, rows, d, sigma, tspan=tspan,
+    generator=generator, device=x.device, mask=mask)).
+    :return: dict with, per quantity "L+G" (L + alph[0] G), "G", "Q", "W": a dict mean / std / q05 / q50 / q95 of [nex] tensors; and
+             "persample" [nex, paths, 7], the table every figure is formed from"""
+    alph = list(Phi.alph if alph is None else alph)
+    paths = int(paths)
+    if paths < 1:
+        raise ValueError("paths must be >= 1")
+    if int(max_rows) < paths:
+        raise ValueError(f"max_rows = {int(max_rows)} holds no whole start of {paths} paths")
+    x = _lib.require_device_f32(x, "x")
+    if x.dim() != 2:
+        raise ValueError("x must be nex-by-d")
+    n, d = x.shape
+    per = int(max_rows) // paths                           # starts per chunk
+    tabs = []
+    for s0 in range(0, n, per):
+        xs = x[s0:s0 + per].repeat_interleave(paths, dim=0).contiguous()
+        Wc = brownian_disturbances(nt, xs.shape[0], d, sigma, tspan=tspan, generator=generator, device=x.device, mask=mask)
+        tabs.append(disturbed_rollout(xs, Phi, prob, nt, Wc, tspan=tspan, alph=alph, stepper=stepper)["persample"])
+    tab = torch.cat(tabs).view(n, paths, 7)
+    _lib.check_errors(sync=True)
+    out = {"L+G": path_statistics(tab[:, :, 0] + alph[0] * tab[:, :, 1]), "G": path_statistics(tab[:, :, 1]),
+           "Q": path_statistics(tab[:, :, 5]), "W": path_statistics(tab[:, :, 6]), "persample": tab}
+    return out
