@@ -186,6 +186,26 @@ int nocf_rollout_disturbed_f32(const NocfPhi* phi, const NocfProb* prob, const f
                                void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The recording forward of training under per-step state disturbances: nocf_rollout_record_act_f32 (below) under the contract of
+ * nocf_rollout_disturbed_f32 -- W device [nt, n, d], float32, time-major, contiguous, not modified; z = step(z, tk, tk + h);
+ * z[:, :d] += W[k]; the terminal terms at the displaced z(T).  s_all [nt*nstage, n, d+1] receives the stage inputs of every RK evaluation:
+ * the first stage of step k+1 is recorded at the DISPLACED state, and W[nt-1] lands on z_out, where the terminal block is evaluated.
+ * W does not depend on the parameters, so the adjoint of the disturbed scheme is the adjoint of the undisturbed one at these recorded
+ * inputs: s_all and z_out go to nocf_rollout_bwd_small_f32 / nocf_rollout_bwd_mid_f32 / nocf_rollout_bwd_act_f32 unchanged (they read
+ * every stage input from s_all and the final state from z_out; none re-derives a state from the previous step).  dJ/dW is not formed.
+ * W == 0 gives nocf_rollout_record_act_f32's outputs on the same kernel.
+ *   act_rec, recorded   as for nocf_rollout_record_act_f32: the one-CU kernel writes the activation record (recorded = 1), the lane and
+ *                       per-tile kernels do not (recorded = 0; pass NULL for shapes the one-CU kernel does not take)
+ * Dispatch: the register-resident small-network kernel, then the one-CU kernel, then the per-tile kernel -- never the split-role kernel
+ * (m = 512 networks record on the per-tile kernel here, and their adjoint is nocf_rollout_bwd_act_f32 with a null record).  No tape.
+ * float32 only; no segments.  W == NULL, s_all == NULL or z_out == NULL: NOCF_E_NULL.  Every refusal returns before anything is enqueued.
+ */
+int nocf_rollout_record_disturbed_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, const float* W, int64_t n,
+                                      double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                      float* z_out, float* persample, float* cost_sums, float* s_all, float* act_rec, int32_t* recorded,
+                                      void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Several rollouts that differ only in their start time and step count, in ONE launch (round 5): the second segments of a shock sweep.
  * The reference's shocked rollout (src/plotter.py:815-824, driven by evalOC.py:113-122) is OCflow on [0, t_s] with int(t_s nt) steps, the
  * shock added to the end state, and OCflow on [t_s, 1] with 1 + nt - int(t_s nt) steps; a sweep over shock times (BASELINE config 5) repeats

@@ -146,7 +146,8 @@ __device__ void physics_xgrad(const Ctx& c, const DevPlan& pl, const DevProb& pb
     // obstacle part (one thread per agent) seeds XD; the barrier orders it before the interaction part adds to it
     for (int a = j0; a < N; a += Gsz) {
         float gq[3] = {0.f, 0.f, 0.f};
-        if (pb.training && pb.obstacle != NOCF_OBS_NONE) NOCF_OBSTACLE_XGRAD(pb, x, a, gq)
+        // (eval mode: the hard corridor and the blocks are masks without a gradient; the soft corridor's Gaussians are the train-mode ones)
+        if ((pb.training && pb.obstacle != NOCF_OBS_NONE) || pb.obstacle == NOCF_OBS_SOFTCORRIDOR) NOCF_OBSTACLE_XGRAD(pb, x, a, gq)
         if (ad == 2) { xd[2 * a] = cf * aQ * gq[0]; xd[2 * a + 1] = cf * aQ * gq[1]; }
         else { xd[3 * a] = cf * aQ * gq[0]; xd[3 * a + 1] = cf * aQ * gq[1]; xd[3 * a + 2] = cf * aQ * gq[2]; }
     }

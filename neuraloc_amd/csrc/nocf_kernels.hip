@@ -998,7 +998,8 @@ __device__ void ctrl_write(const Ctx& c, const DevPlan& pl, const DevProb& pb, f
 // DIST: the disturbed rollout (RollArgs::dist, W [nt][n][d]): behind step k the state rows take z[:, :d] += W[k] where the step's z is written
 // back.  The entries are loaded in the write-back sweep itself, not at the top of the step: this kernel runs at its register budget, and two
 // registers held across phi_eval turned 3 spilled registers into 59 on swarm50's instantiation.  The sweep is followed by the physics phase, and
-// one exposed load per step is small beside the step's four evaluations.
+// one exposed load per step is small beside the step's four evaluations.  With ra.sAll set (disturbed training) the record at the top of an
+// evaluation reads SB, which every write-back path below leaves displaced.
 template <int S, bool DIST = false>
 __device__ __forceinline__ void rollout_body(const DevPlan& pl, const DevPlan* __restrict__ plp, const DevProb& pb,
                                              const float* __restrict__ ws, const RollArgs& ra) {
@@ -1984,9 +1985,11 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
     if (stepper != NOCF_RK4 && stepper != NOCF_RK1) return NOCF_E_STEPPER;
     if ((zFull != nullptr) != (ctrlFull != nullptr)) return NOCF_E_NULL;
     if (cost_sums && !persample) return NOCF_E_NULL;
-    // a disturbed rollout (nocf_rollout_disturbed_f32) is an evaluation: it records nothing for an adjoint and takes no segments.  No
-    // exported entry point passes either combination today: these two lines guard the ones to come
-    if (dist && (s_all || act || tapeSc)) return NOCF_E_NULL;
+    // a disturbed rollout records the stage inputs (and the one-CU kernel's activation record) for the adjoints
+    // (nocf_rollout_record_disturbed_f32), which run unchanged: W does not depend on the parameters.  It writes no tape -- the tape is the
+    // split-role kernel's, which takes no W -- and takes no segments
+    if (dist && tapeSc) return NOCF_E_NULL;
+    if (dist && act && !s_all) return NOCF_E_NULL;
     if (dist && seg) return NOCF_E_SHAPE;
     DevProb pb;
     rc = fill_prob(prob, phi->d, &pb);
@@ -2041,7 +2044,8 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
             (void)hipEventRecord(ev0, st);
         }
         const size_t laneLds = ticket ? (size_t)(256 * 7 * 8 + 16) : 0;      // (the last-workgroup reduction's scratch: only with a ticket)
-#define NOCF_LANE_LAUNCH(MPV, DPV) do { if (dist) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, true>), dim3(grid), dim3(256), 0, st, la, pb, ra); \
+#define NOCF_LANE_LAUNCH(MPV, DPV) do { if (dist && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, true>), dim3(grid), dim3(256), 0, st, la, pb, ra); \
+                                         else if (dist) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, true>), dim3(grid), dim3(256), 0, st, la, pb, ra); \
                                          else if (s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true>), dim3(grid), dim3(256), 0, st, la, pb, ra); \
                                          else if (ticket) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, true>), dim3(grid), dim3(256), laneLds, st, la, pb, ra); \
                                          else hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false>), dim3(grid), dim3(256), 0, st, la, pb, ra); } while (0)
@@ -2105,7 +2109,7 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
         hipLaunchKernelGGL(mono_pack_kernel, dim3(64), dim3(256), 0, st, mpl, P, ws);
         const size_t ldsBytes = (size_t)mpl.pp.ldsFloats * 4;
         const void* fk = nullptr;
-#define NOCF_MONO_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) fk = dist ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, true>) : s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false>);
+#define NOCF_MONO_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) fk = dist ? (s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, true>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, true>)) : s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false>);
         MONO_SHAPES(NOCF_MONO_PICK)
 #undef NOCF_MONO_PICK
         e = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes); if (e) return (int)e;
@@ -2163,7 +2167,9 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
 #undef NOCF_TRY_FIXED
 #define NOCF_TRY_FIXED(D, M, NTH, R, NAG) \
             if (!fk && plan_is<FixedPlan<D, M, NTH, R, NAG, 0>>(pl)) fk = reinterpret_cast<const void*>(rollout_kernel<1, FixedPlan<D, M, NTH, R, NAG, 0>>);
-            if (s_all) { FIXED_SHAPES_TRAIN(NOCF_TRY_FIXED) }
+            // (the training-only shapes are the lane kernel's: they come here under NOCF_LANE=0 alone, and a disturbed call then takes the
+            // generic instantiation, the only one of theirs that reads W)
+            if (s_all && !dist) { FIXED_SHAPES_TRAIN(NOCF_TRY_FIXED) }
 #undef NOCF_TRY_FIXED
             if (fk) {
                 e = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes); if (e) return (int)e;
@@ -2258,6 +2264,16 @@ int nocf_rollout_record_f32(const NocfPhi* phi, const NocfProb* prob, const floa
     if (!s_all || !z_out) return NOCF_E_NULL;
     return rollout_impl(phi, prob, x, n, t0, t1, nt, stepper, alph, z_out, persample, cost_sums, nullptr, nullptr,
                         workspace, workspace_bytes, stream, s_all);
+}
+
+int nocf_rollout_record_disturbed_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, const float* W, int64_t n,
+                                      double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                      float* z_out, float* persample, float* cost_sums, float* s_all, float* act_rec, int32_t* recorded,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+    if (recorded) *recorded = 0;
+    if (!W || !s_all || !z_out) return NOCF_E_NULL;
+    return rollout_impl(phi, prob, x, n, t0, t1, nt, stepper, alph, z_out, persample, cost_sums, nullptr, nullptr,
+                        workspace, workspace_bytes, stream, s_all, act_rec, recorded, nullptr, nullptr, nullptr, nullptr, W);
 }
 
 size_t nocf_activation_record_floats(int32_t d, int32_t m, int32_t nTh, int64_t n, int32_t nt, int32_t stepper) {

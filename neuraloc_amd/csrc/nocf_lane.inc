@@ -30,7 +30,8 @@ struct LaneArgs {
 // ONE: the instantiation WITH the last-workgroup reduction (NOCF_LANE_ONE=1, evaluation only).  Its own instantiation because the reduction's code
 // at the kernel's end costs the register-resident rollout in front of it 5-7 % (swap2 0.084 -> 0.090 ms) even when it is never taken
 // DIST: the disturbed rollout (RollArgs::dist, W [nt][n][d]): lane j < d adds W[k][sample][j] to its component behind step k.  The load is
-// issued at the top of the step -- its address does not depend on the step -- and consumed behind the last stage
+// issued at the top of the step -- its address does not depend on the step -- and consumed behind the last stage.  REC and DIST together (the
+// recording forward of disturbed training): the next step's first stage input is formed from the displaced z, so it is recorded displaced
 template <int MP, int DP, bool REC, bool ONE = false, bool DIST = false>
 __global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb pb, RollArgs ra) {
     const int lane = threadIdx.x & 63;

@@ -143,7 +143,9 @@ __global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, D
             if (pb.obstacle != NOCF_OBS_NONE && lane < d) {
                 const float val = obstacle_cross2d(pb, x0, x1);
                 if (comp == 0) qa = val;
-                if (pb.training) {
+                // (the soft corridor's Gaussians do not depend on the mode: their gradient is due in eval mode too -- a disturbed or an eval-mode
+                // training call differentiates them; the eval-mode hard corridor is a mask, whose gradient is 0)
+                if (pb.training || pb.obstacle == NOCF_OBS_SOFTCORRIDOR) {
                     if (pb.obstacle == NOCF_OBS_SOFTCORRIDOR) {
                         const float cov = 0.2f, denom = (float)TWO_PI_D * sqrtf(cov * cov);
                         const float mus[4] = {-2.5f, 2.5f, -1.5f, 1.5f};

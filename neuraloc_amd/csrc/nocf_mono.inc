@@ -218,7 +218,8 @@ __device__ __forceinline__ void mono_sincos(float x, float& sn, float& cs) {
 // REC: the training variant (stage inputs RollArgs::sAll, activation record RollArgs::act); the evaluation variant carries no trace of it
 // DIST: the disturbed rollout (RollArgs::dist, W [nt][n][d]): behind step k the state rows take z[:, :d] += W[k] where the step's z is written
 // back (in front of the zFull store and of the control evaluation).  Each thread loads the entries of its own components at the top of the step
-// (KBD + 1 registers at most; one for singlequad) and adds them behind the last stage
+// (KBD + 1 registers at most; one for singlequad) and adds them behind the last stage.  REC and DIST together (the recording forward of
+// disturbed training): the state rows SB hold the displaced state when the next step's first stage input and activations are recorded
 template <int KBM, int KBD, bool REC, bool DIST = false>
 __global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __restrict__ mpp, DevProb pb, float* ws, RollArgs ra) {
     constexpr int MT = (KBM + 3) / 4;              // hidden M-tiles per wave: tiles w, w+4, ...

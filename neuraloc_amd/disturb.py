@@ -7,7 +7,8 @@ step, by a caller-supplied W [nt, n, d] (time-major like the kernels' zFull):
 
 -- additive noise in the Euler-Maruyama position.  The whole disturbed rollout is ONE launch (nocf_rollout_disturbed_f32): the lane, one-CU
 and per-tile kernels take W as one more input.  The split-role kernel does not: m = 512 point-agent networks run on the per-tile kernel here.
-Single precision, evaluation only (no autograd, no recording forward), no segments.  There is no CPU or eager-torch fallback."""
+Single precision, no segments.  These calls are evaluations (no autograd); training through disturbed rollouts is
+train.disturbed_ocflow_train (nocf_rollout_record_disturbed_f32).  There is no CPU or eager-torch fallback."""
 import ctypes as C
 import math
 

@@ -225,6 +225,11 @@ class _OCflowTrain(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gJ, _gmeans):
+        return _OCflowTrain._adjoint(ctx, gJ)
+
+    @staticmethod
+    def _adjoint(ctx, gJ):
+        """the backward of _OCflowTrain and of _OCflowTrainDisturbed: everything it reads is what either forward saved"""
         s_all, z_out = ctx.saved_tensors
         net, prob, nt, alph = ctx.net, ctx.prob, ctx.nt, ctx.alph
         if [p._version for p in net.parameters()] != ctx.param_versions:
@@ -398,7 +403,85 @@ class _OCflowTrain(torch.autograd.Function):
             from .distributed import allreduce_flat
             out = allreduce_flat(out, None if ctx.group is True else ctx.group)   # one all-reduce of all gradients
         gx = gJ * lam0 if lam0 is not None else None
-        return (gx,) + (None,) * 8 + tuple(out)
+        return (gx,) + (None,) * getattr(ctx, "n_plain_args", 8) + tuple(out)
+
+
+class _OCflowTrainDisturbed(torch.autograd.Function):
+    """_OCflowTrain under per-step state disturbances W [nt, n, d] (disturb.py): the forward is
+    nocf_rollout_record_disturbed_f32 -- the recording forward with z[:, :d] += W[k] behind step k, on the lane, one-CU or per-tile kernel,
+    never the split-role kernel and never with a tape -- and saves what _OCflowTrain's saves: the stage inputs, recorded at the displaced
+    states, and the displaced z(T).  W does not depend on the parameters, so the adjoint of the disturbed scheme is the adjoint of the
+    undisturbed one at those inputs: the backward is _OCflowTrain's, unchanged, and picks the small, mid or row-stream adjoint as it does
+    there.  dJ/dW is not returned."""
+
+    @staticmethod
+    def forward(ctx, x, net, prob, tspan, nt, stepper, alph, n_total, group, W, *params):
+        ctx.n_plain_args = 9
+        ctx.x_needs_grad = bool(x.requires_grad)
+        x = _lib.require_device_f32(x.detach(), "x")
+        W = _lib.require_device_f32(W.detach(), "W")
+        n, d = x.shape
+        dev = x.device
+        phi_st, keep1, ws = net._c_struct(n)
+        prob_st, keep2 = prob._c_struct(dev)
+        nstage = 4 if stepper == "rk4" else 1
+        persample = torch.empty(n, 7, device=dev)
+        sums = torch.empty(8, device=dev)
+        z_out = torch.empty(n, d + 4, device=dev)
+        s_all = torch.empty(nt * nstage, n, d + 1, device=dev)
+        alph_c = (C.c_float * 6)(*[float(a) for a in alph[:6]])
+        _lib.check_errors()
+        ctx.tape = None
+        with torch.cuda.device(dev):
+            L = _lib.lib_for(net.d, net.m, net.nTh, phi_st.r, prob_st.n_agents, fwd=prob_st.kind != _lib.PROB_QUADCOPTER)
+            f = _disturbed_entry(L)
+            if f is None:                                  # a per-shape library cached by an older build: the shipped library has the entry
+                L = _lib.lib()
+                f = _disturbed_entry(L)
+            if f is None:
+                raise RuntimeError("disturbed_ocflow_train: the HIP library does not export nocf_rollout_record_disturbed_f32; rebuild it")
+            ctx.mid_rows = int(L.nocf_mid_grad_rows(int(d), int(net.m), int(net.nTh), int(phi_st.r), int(prob_st.n_agents), int(n))) \
+                if hasattr(L, "nocf_rollout_bwd_mid_f32") else 0
+            # the activation record is the one-CU kernel's here (m <= 128): the split-role kernel, whose record nocf_activation_record_floats
+            # also sizes (2.9 GB for swarm50), never runs a disturbed call -- m = 512 records on the per-tile kernel and its adjoint recomputes
+            nact = 0 if (os.environ.get("NOCF_ACT_REC", "1") in ("0", "") or net.m > 128) else int(
+                L.nocf_activation_record_floats(int(d), int(net.m), int(net.nTh), int(n), int(nt), _STEPPERS[stepper]))
+            act = None
+            if nact:
+                try:
+                    act = torch.empty(nact, device=dev)
+                except torch.OutOfMemoryError:                     # the record is an optimisation: without it the adjoint recomputes
+                    act = None
+            recorded = C.c_int32(0)
+            rc = f(C.byref(phi_st), C.byref(prob_st), _lib.ptr(x), _lib.ptr(W), n,
+                   float(tspan[0]), float(tspan[1]), int(nt), _STEPPERS[stepper], alph_c,
+                   _lib.ptr(z_out), _lib.ptr(persample), _lib.ptr(sums), _lib.ptr(s_all), _lib.ptr(act), C.byref(recorded),
+                   _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+        _lib.check(rc, "nocf_rollout_record_disturbed_f32")
+        ctx.act = act if recorded.value else None
+        return _OCflowTrain._forward_tail(ctx, L, dev, net, prob, tspan, nt, stepper, alph, n_total, group, n, sums, s_all, z_out)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gJ, _gmeans):
+        return _OCflowTrain._adjoint(ctx, gJ)
+
+
+_DISTURBED_ARGTYPES = [C.POINTER(_lib.NocfPhi), C.POINTER(_lib.NocfProb), C.c_void_p, C.c_void_p, C.c_int64,
+                       C.c_double, C.c_double, C.c_int32, C.c_int32, _lib.fp,
+                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
+                       C.c_void_p, C.c_size_t, C.c_void_p]
+
+
+def _disturbed_entry(L):
+    """nocf_rollout_record_disturbed_f32 of library L with its prototype set, or None when L does not export it"""
+    if not hasattr(L, "nocf_rollout_record_disturbed_f32"):
+        return None
+    f = L.nocf_rollout_record_disturbed_f32
+    if f.argtypes is None:
+        f.restype = C.c_int
+        f.argtypes = _DISTURBED_ARGTYPES
+    return f
 
 
 class _OCflowTrain64(torch.autograd.Function):
@@ -505,4 +588,50 @@ def ocflow_train(x, net, prob, tspan, nt, stepper, alph, n_total=None, group=Non
     params = [p for _, p in net.named_parameters()]
     fn = _OCflowTrain64 if x.dtype == torch.float64 else _OCflowTrain
     Jc, means = fn.apply(x, net, prob, list(tspan), int(nt), stepper, list(alph), n_total, group, *params)
+    return Jc, [means[i] for i in range(7)]
+
+
+def disturbed_ocflow_train(x, net, prob, tspan, nt, W, stepper="rk4", alph=None, n_total=None, group=None):
+    """ocflow_train under per-step state disturbances: (Jc, cs) of the rollout
+        z = [x, 0, 0, 0, 0];  for k in 0 .. nt-1:  z = step(z, tk, tk + h);  z[:, :d] += W[k];  tk += h;   terminal terms at the displaced z(T)
+    (disturb.disturbed_rollout's), with Jc differentiable w.r.t. every parameter of `net` and w.r.t. x when x requires a gradient.
+    :param W:   nt-by-nex-by-d float32 tensor on x's device (brownian_disturbances); not modified, and not differentiated: dJ/dW is not
+                returned, so a W that requires a gradient is refused
+    :param alph: 6 multipliers (default: net.alph);  n_total, group: as for ocflow_train (each rank passes its own shard's W)
+    Single precision only.  Every check below raises before a device is touched."""
+    alph = list(net.alph if alph is None else alph)
+    tensors = [("x", x), ("W", W)] + [(name, p_) for name, p_ in net.named_parameters()]
+    for name, t in tensors:
+        if isinstance(t, torch.Tensor) and t.dtype == torch.float64:
+            raise RuntimeError(f"disturbed_ocflow_train: {name} is float64; the disturbed rollout is single precision only "
+                               "(the double-precision kernels take no disturbance)")
+    for name, t in (("x", x), ("W", W)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+    if stepper not in _STEPPERS:
+        raise ValueError(f"stepper must be 'rk4' or 'rk1', got {stepper!r}")
+    if x.dim() != 2:
+        raise ValueError("x must be nex-by-d")
+    n, d = x.shape
+    if d != net.d:
+        raise ValueError(f"x has d={d} but Phi was built for d={net.d}")
+    pd_ = getattr(prob, "d", None)
+    if pd_ is not None and int(pd_) != d:
+        raise ValueError(f"the problem object has d={pd_} but x has d={d}")
+    if int(nt) < 1:
+        raise ValueError("nt must be >= 1")
+    if n < 1:
+        raise ValueError("x has no rows")
+    if tuple(W.shape) != (int(nt), n, d):
+        raise ValueError(f"W must be nt-by-nex-by-d = {(int(nt), n, d)}, got {tuple(W.shape)}")
+    if len(alph) < 6:
+        raise ValueError("alph needs 6 entries")
+    if W.requires_grad:
+        raise NotImplementedError("disturbed_ocflow_train: W requires a gradient, but dJ/dW is not returned; pass W.detach()")
+    if W.device != x.device:
+        raise ValueError("x and W must be on the same device")
+    _lib.require_device_f32(x, "x")
+    _lib.require_device_f32(W, "W")
+    params = [p for _, p in net.named_parameters()]
+    Jc, means = _OCflowTrainDisturbed.apply(x, net, prob, list(tspan), int(nt), stepper, alph, n_total, group, W, *params)
     return Jc, [means[i] for i in range(7)]

@@ -10,7 +10,11 @@ forward, Jc.backward(), validation -- runs in the HIP kernels.  No plotting (viz
 One GPU:   python trainOC.py --data softcorridor --niters 200
 N GPUs:    python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 trainOC.py ...
            (one rank per GPU; each rank draws n_train/N samples; the 8 cost sums and one flat gradient buffer are
-           all-reduced over RCCL per iteration, so every rank takes the same Adam step)."""
+           all-reduced over RCCL per iteration, so every rank takes the same Adam step).
+
+--noise SIGMA [--noise_seed S] (addition): the training rollouts run under per-step Brownian state disturbances sigma dB
+(neuraloc_amd.disturbed_ocflow_train), a fresh W every iteration; validation and its logged costs stay undisturbed.
+SIGMA = 0 (default) is the run without the flag."""
 import argparse
 import datetime
 import os
@@ -51,6 +55,9 @@ _FLAGS = [
     ("sample_freq", int, 100, "draw a new batch every this many iterations"),
     ("new_alph", str, None, "'iter, a0, ..., a5': switch the weights at that iteration"),
     ("seed", int, None, "torch seed (rank is added); the reference is unseeded"),
+    ("noise", float, 0.0, "(addition) SIGMA > 0: train on rollouts under Brownian state disturbances sigma dB at every step "
+                          "(neuraloc_amd.disturbed_ocflow_train); validation stays undisturbed; single precision only"),
+    ("noise_seed", int, 0, "(addition) seed of the disturbances for --noise (rank is added)"),
 ]
 _CHOICES = {"data": PROBLEM_NAMES, "optim": ["adam"], "prec": ["single", "double"], "approach": ["ocflow"]}
 
@@ -68,6 +75,10 @@ def parse_args(argv=None):
 
 def main(argv=None):
     args = parse_args(argv)
+    if args.noise < 0:
+        raise SystemExit("--noise SIGMA must be >= 0")
+    if args.noise > 0 and args.prec == "double":                       # refused before anything runs or is written
+        raise SystemExit("--noise runs in single precision only (the double-precision rollout takes no disturbance)")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     if world > 1:
@@ -117,13 +128,19 @@ def main(argv=None):
         "valLoss", "valL", "valG", "valHJt", "valHJf", "valHJg", "valQ", "valW"))
 
     rollout = na.OCflow_sharded if dist else na.OCflow
+    # --noise: every iteration draws its own W on the device; each rank its own shard's, from its own generator
+    noise_gen = torch.Generator(device=dev).manual_seed(args.noise_seed + rank) if args.noise > 0 else None
     best_loss, best_params, total = float("inf"), None, 0.0
     net.train()
     prob.train()
     end = time.time()
     for itr in range(1, args.niters + 1):
         optim.zero_grad()
-        Jc, cs = rollout(x0, net, prob, tspan, args.nt, "rk4", net.alph)
+        if noise_gen is not None:
+            W = na.brownian_disturbances(args.nt, x0.shape[0], d, args.noise, tspan=tspan, generator=noise_gen, device=dev)
+            Jc, cs = na.disturbed_ocflow_train(x0, net, prob, tspan, args.nt, W, "rk4", net.alph, group=True if dist else None)
+        else:
+            Jc, cs = rollout(x0, net, prob, tspan, args.nt, "rk4", net.alph)
         Jc.backward()
         torch.cuda.synchronize()
         na.check_errors()                                 # (after the synchronisation and BEFORE the step: a timed-out rollout raises, its NaN gradients are not applied)
