@@ -597,7 +597,8 @@ int nocf_baseline_quad_lbfgs_f32(const NocfProb* prob, int32_t d, int64_t B, int
  *   - direct transcription: U, z and dJ/dU of one point live in LDS as doubles, (3 nt d + d + 3 nt + 8) doubles plus 6 KiB / 24 KiB of
  *     partial sums; the Adam moments do not (registers, or the m / v arrays themselves), so both entry points share one limit:
  *     nocf_baseline_max_nt(prob, d, adam, 8) -- swarm (d = 96) up to nt = 59, swarm50 (d = 150) up to nt = 38.
- *   - quadcopter: every scalar of torch.optim.LBFGS is a double; the workspace holds doubles (twice the bytes).
+ *   - quadcopter: the fp32 kernels' source instantiated for double (csrc/nocf_baseline_quad.inc); every scalar of torch.optim.LBFGS
+ *     is a double; the workspace holds doubles (twice the bytes).
  *
  * nocf_baseline_max_nt: the largest nt nocf_baseline_eval_* (adam = 0) / nocf_baseline_adam_* (adam != 0) accept for this problem,
  * for elem_bytes = 4 (the _f32 entry points) or 8 (_f64); every nt from 1 to it is accepted, every larger one returns NOCF_E_SHAPE

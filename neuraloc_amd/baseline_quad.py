@@ -6,7 +6,7 @@ nocf_baseline_quad_eval_f32, nocf_baseline_quad_lbfgs_f32; neuraloc_amd/csrc/noc
 Single-agent Quadcopter only (d = 12), on the GPU only.  mass, grav and xtarget come from the problem; alph_Q and alph_W are
 ignored, as the reference ignores them.  The precision follows the tensors, as in Phi.forward / OCflow: float32 z0 / U take the fp32
 kernels, float64 ones (the reference's --prec double; every tensor of the call float64) the double-precision kernels
-(nocf_baseline_quad_eval_f64, nocf_baseline_quad_lbfgs_f64; nocf_baseline_quad_f64.inc) and give float64 results.  With the
+(nocf_baseline_quad_eval_f64, nocf_baseline_quad_lbfgs_f64; the same source, instantiated for double) and give float64 results.  With the
 reference's tolerances (tolerance_change = 1e-6 on a loss of about 2182) only the double solve runs to the optimum: the fp32 one
 stops where the loss stalls at fp32 resolution.
 

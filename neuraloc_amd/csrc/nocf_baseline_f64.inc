@@ -51,13 +51,6 @@ struct Base64Args {
     int step0, niters;
 };
 
-// all 64 lanes, one fixed order (a butterfly: every lane ends with the same bits)
-__device__ __forceinline__ double bl64_sum64(double v) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // Z[i+1] = Z[i] + h U[i], one thread per coordinate: the reference's own order and rounding (no contraction)
 __device__ __forceinline__ void bl64_forward(double* L, const Base64Lay& ly, int d, int nt, double h) {
 #pragma clang fp contract(off)
@@ -155,7 +148,7 @@ __device__ void bl64_rows(double* L, const F64Prob& pb, const Base64Lay& ly, int
         const int lane = tid & 63;
         double s = 0.0;
         for (int k = lane; k < d; k += 64) { const double e = L[ly.oZ + nt * d + k] - pb.xtarget[k]; s += e * e; }
-        s = bl64_sum64(s);
+        s = sum64(s);
         if (lane == 0) L[ly.oS + 1] = 0.5 * s;
     }
     __syncthreads();

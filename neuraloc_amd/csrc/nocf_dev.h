@@ -70,6 +70,12 @@ __device__ __forceinline__ float sum64(float v) {
     const float r2 = __int_as_float(__builtin_amdgcn_readlane(b, 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(b, 48));
     return (r0 + r1) + (r2 + r3);
 }
+// the same for a double: a butterfly, one fixed order of its own (every lane ends with the same bits)
+__device__ __forceinline__ double sum64(double v) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
+    return v;
+}
 // aligned groups of seg = 2, 4, ..., 64 lanes
 __device__ __forceinline__ float sum_seg(float v, int seg) {
     if (seg >= 64) return sum64(v);

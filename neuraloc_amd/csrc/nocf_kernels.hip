@@ -1565,7 +1565,6 @@ __global__ void mfma_selftest_kernel(const float* __restrict__ a, const float* _
 #include "nocf_baseline.inc"
 #include "nocf_baseline_quad.inc"
 #include "nocf_baseline_f64.inc"
-#include "nocf_baseline_quad_f64.inc"
 #include "nocf_lane_bwd.inc"
 #include "nocf_mono_bwd.inc"
 
@@ -2762,80 +2761,7 @@ int nocf_baseline_adam_f32(const NocfProb* prob, int32_t d, int64_t B, int32_t n
 }
 
 // ------------------------------------------------------------------------------------------
-// the quadcopter baseline (nocf_baseline_quad.inc)
-// ------------------------------------------------------------------------------------------
-static int baseline_quad_setup(const NocfProb* prob, int32_t d, int64_t B, int32_t nt, int32_t hist, DevProb* pb, QuadArgs* qa) {
-    if (!prob) return NOCF_E_NULL;
-    if (prob->kind != NOCF_PROB_QUADCOPTER) return NOCF_E_PROB;         // the point agents' baseline is nocf_baseline_*_f32
-    if (d != 12) return NOCF_E_SHAPE;                                   // baselineQuad.py's dynamics are single-agent
-    int rc = fill_prob(prob, d, pb);
-    if (rc) return rc;
-    if (B < 1 || B > 0x7fffffffL || nt < 1 || nt > NOCF_BLQ_MAX_NT || hist < 0 || hist > NOCF_BLQ_MAX_HISTORY) return NOCF_E_SHAPE;
-    *qa = QuadArgs{};
-    qa->xt = pb->xtarget;
-    qa->nt = nt; qa->hist = hist;
-    qa->h = (float)(1.0 / nt); qa->mass = (float)pb->mass; qa->grav = (float)pb->grav;
-    return 0;
-}
-
-size_t nocf_baseline_quad_workspace_bytes(int64_t B, int32_t nt, int32_t history_size) {
-    if (B < 1 || B > 0x7fffffffL || nt < 1 || nt > NOCF_BLQ_MAX_NT || history_size < 1 || history_size > NOCF_BLQ_MAX_HISTORY) return 0;
-    return (size_t)B * 2 * (size_t)history_size * 4 * (size_t)nt * sizeof(float);
-}
-
-int nocf_baseline_quad_eval_f32(const NocfProb* prob, int32_t d, int64_t B, int32_t nt, double alphG, const float* z0, const float* U,
-                                float* loss, float* grad, float* report, float* traj, void* stream) {
-    if (!z0 || !U || !loss) return NOCF_E_NULL;
-    DevProb pb;
-    QuadArgs qa;
-    int rc = baseline_quad_setup(prob, d, B, nt, 0, &pb, &qa);
-    if (rc) return rc;
-    qa.z0 = z0; qa.U = const_cast<float*>(U); qa.loss = loss; qa.grad = grad; qa.report = report; qa.traj = traj;
-    qa.aG = (float)alphG; qa.aGh = (float)(alphG * 0.5);
-    const size_t ldsBytes = (size_t)blq_layout(nt, 0).total * sizeof(float);
-    hipLaunchKernelGGL(baseline_quad_eval_kernel, dim3((unsigned)B), dim3(NOCF_BLQ_WAVE), ldsBytes, (hipStream_t)stream, qa);
-    return (int)hipGetLastError();
-}
-
-extern "C++" {
-template <int E>
-static int launch_quad_lbfgs(const QuadArgs& qa, int64_t B, size_t ldsBytes, hipStream_t st) {
-    hipError_t e = set_lds(baseline_quad_lbfgs_kernel<E>, ldsBytes);
-    if (e) return (int)e;
-    hipLaunchKernelGGL(baseline_quad_lbfgs_kernel<E>, dim3((unsigned)B), dim3(NOCF_BLQ_WAVE), ldsBytes, st, qa);
-    return (int)hipGetLastError();
-}
-}
-
-int nocf_baseline_quad_lbfgs_f32(const NocfProb* prob, int32_t d, int64_t B, int32_t nt, double alphG, double lr, int32_t max_iter,
-                                 int32_t max_eval, double tolerance_grad, double tolerance_change, int32_t history_size,
-                                 const float* z0, float* U, float* loss, int32_t* n_iter, int32_t* n_evals, int32_t* reason,
-                                 void* workspace, size_t workspace_bytes, void* stream) {
-    if (!z0 || !U || !loss || !n_iter || !n_evals || !reason || !workspace) return NOCF_E_NULL;
-    if (history_size < 1 || max_iter < 0 || max_eval < 1) return NOCF_E_SHAPE;
-    DevProb pb;
-    QuadArgs qa;
-    int rc = baseline_quad_setup(prob, d, B, nt, history_size, &pb, &qa);
-    if (rc) return rc;
-    if (workspace_bytes < nocf_baseline_quad_workspace_bytes(B, nt, history_size)) return NOCF_E_WORKSPACE;
-    if (max_iter == 0) return 0;
-    qa.z0 = z0; qa.U = U; qa.loss = loss; qa.n_iter = n_iter; qa.n_evals = n_evals; qa.reason = reason;
-    qa.ws = (float*)workspace;
-    qa.aG = (float)alphG; qa.aGh = (float)(alphG * 0.5);
-    qa.max_iter = max_iter; qa.max_eval = max_eval;
-    qa.lr = lr; qa.tol_grad = tolerance_grad; qa.tol_change = tolerance_change;
-    const size_t ldsBytes = (size_t)blq_layout(nt, history_size).total * sizeof(float);
-    const int per_lane = (4 * nt + NOCF_BLQ_WAVE - 1) / NOCF_BLQ_WAVE;  // L-BFGS vector elements per lane
-    hipStream_t st = (hipStream_t)stream;
-    if (per_lane <= 1) return launch_quad_lbfgs<1>(qa, B, ldsBytes, st);
-    if (per_lane <= 2) return launch_quad_lbfgs<2>(qa, B, ldsBytes, st);
-    if (per_lane <= 4) return launch_quad_lbfgs<4>(qa, B, ldsBytes, st);
-    if (per_lane <= 8) return launch_quad_lbfgs<8>(qa, B, ldsBytes, st);
-    return launch_quad_lbfgs<16>(qa, B, ldsBytes, st);
-}
-
-// ------------------------------------------------------------------------------------------
-// the two baselines in double precision (nocf_baseline_f64.inc, nocf_baseline_quad_f64.inc)
+// the point agents' baseline in double precision (nocf_baseline_f64.inc)
 // ------------------------------------------------------------------------------------------
 static int prob64_to_dev(const NocfProb64* prob, int32_t d, F64Prob* pb) {
     if (!prob) return NOCF_E_NULL;
@@ -2904,77 +2830,126 @@ int nocf_baseline_adam_f64(const NocfProb64* prob, int32_t d, int64_t B, int32_t
     return (int)hipGetLastError();
 }
 
-static int baseline_quad_setup_f64(const NocfProb64* prob, int32_t d, int64_t B, int32_t nt, int32_t hist, F64Prob* pb, Quad64Args* qa) {
+// ------------------------------------------------------------------------------------------
+// the quadcopter baseline, both precisions (nocf_baseline_quad.inc)
+// ------------------------------------------------------------------------------------------
+extern "C++" {
+// the problem as the caller passes it, and as the kernels of that precision take it
+template <typename T> struct QuadProb;
+template <> struct QuadProb<float> { typedef NocfProb Host; typedef DevProb Dev; };
+template <> struct QuadProb<double> { typedef NocfProb64 Host; typedef F64Prob Dev; };
+static int quad_prob_to_dev(const NocfProb* prob, int32_t d, DevProb* pb) { return fill_prob(prob, d, pb); }
+static int quad_prob_to_dev(const NocfProb64* prob, int32_t d, F64Prob* pb) { return prob64_to_dev(prob, d, pb); }
+
+template <typename T>
+static int baseline_quad_setup(const typename QuadProb<T>::Host* prob, int32_t d, int64_t B, int32_t nt, int32_t hist, double alphG,
+                               typename QuadProb<T>::Dev* pb, QuadArgs<T>* qa) {
     if (!prob) return NOCF_E_NULL;
-    if (prob->kind != NOCF_PROB_QUADCOPTER) return NOCF_E_PROB;         // the point agents' baseline is nocf_baseline_*_f64
-    if (d != 12) return NOCF_E_SHAPE;
-    int rc = prob64_to_dev(prob, d, pb);
+    if (prob->kind != NOCF_PROB_QUADCOPTER) return NOCF_E_PROB;         // the point agents' baseline is nocf_baseline_*_f32 / _f64
+    if (d != 12) return NOCF_E_SHAPE;                                   // baselineQuad.py's dynamics are single-agent
+    int rc = quad_prob_to_dev(prob, d, pb);
     if (rc) return rc;
     if (B < 1 || B > 0x7fffffffL || nt < 1 || nt > NOCF_BLQ_MAX_NT || hist < 0 || hist > NOCF_BLQ_MAX_HISTORY) return NOCF_E_SHAPE;
-    if (!prob->xtarget) return NOCF_E_NULL;
-    *qa = Quad64Args{};
+    if (sizeof(T) == 8 && !prob->xtarget) return NOCF_E_NULL;           // (only the fp64 entries check the target, and here)
+    *qa = QuadArgs<T>{};
     qa->xt = pb->xtarget;
     qa->nt = nt; qa->hist = hist;
-    qa->h = 1.0 / nt; qa->mass = pb->mass; qa->grav = pb->grav;
+    qa->h = (T)(1.0 / nt); qa->mass = (T)pb->mass; qa->grav = (T)pb->grav;
+    qa->aG = (T)alphG; qa->aGh = (T)(alphG * 0.5);
     return 0;
 }
 
-size_t nocf_baseline_quad_workspace_bytes_f64(int64_t B, int32_t nt, int32_t history_size) {
+static size_t baseline_quad_workspace(int64_t B, int32_t nt, int32_t history_size, size_t elem_bytes) {
     if (B < 1 || B > 0x7fffffffL || nt < 1 || nt > NOCF_BLQ_MAX_NT || history_size < 1 || history_size > NOCF_BLQ_MAX_HISTORY) return 0;
-    return (size_t)B * 2 * (size_t)history_size * 4 * (size_t)nt * sizeof(double);
+    return (size_t)B * 2 * (size_t)history_size * 4 * (size_t)nt * elem_bytes;
+}
+
+template <typename T>
+static int baseline_quad_eval(const typename QuadProb<T>::Host* prob, int32_t d, int64_t B, int32_t nt, double alphG, const T* z0, const T* U,
+                              T* loss, T* grad, T* report, T* traj, void* stream) {
+    if (!z0 || !U || !loss) return NOCF_E_NULL;
+    typename QuadProb<T>::Dev pb;
+    QuadArgs<T> qa;
+    int rc = baseline_quad_setup<T>(prob, d, B, nt, 0, alphG, &pb, &qa);
+    if (rc) return rc;
+    qa.z0 = z0; qa.U = const_cast<T*>(U); qa.loss = loss; qa.grad = grad; qa.report = report; qa.traj = traj;
+    const size_t ldsBytes = (size_t)blq_layout(nt, 0).total * sizeof(T);
+    if (sizeof(T) == 8) {                                               // (fp32: 37 KiB at the largest nt, under the default limit)
+        hipError_t e = set_lds(baseline_quad_eval_kernel<T>, ldsBytes);
+        if (e) return (int)e;
+    }
+    hipLaunchKernelGGL(baseline_quad_eval_kernel<T>, dim3((unsigned)B), dim3(NOCF_BLQ_WAVE), ldsBytes, (hipStream_t)stream, qa);
+    return (int)hipGetLastError();
+}
+
+template <typename T, int E>
+static int launch_quad_lbfgs(const QuadArgs<T>& qa, int64_t B, size_t ldsBytes, hipStream_t st) {
+    hipError_t e = set_lds(baseline_quad_lbfgs_kernel<T, E>, ldsBytes);
+    if (e) return (int)e;
+    hipLaunchKernelGGL((baseline_quad_lbfgs_kernel<T, E>), dim3((unsigned)B), dim3(NOCF_BLQ_WAVE), ldsBytes, st, qa);
+    return (int)hipGetLastError();
+}
+
+template <typename T>
+static int baseline_quad_lbfgs(const typename QuadProb<T>::Host* prob, int32_t d, int64_t B, int32_t nt, double alphG, double lr,
+                               int32_t max_iter, int32_t max_eval, double tolerance_grad, double tolerance_change, int32_t history_size,
+                               const T* z0, T* U, T* loss, int32_t* n_iter, int32_t* n_evals, int32_t* reason, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    if (!z0 || !U || !loss || !n_iter || !n_evals || !reason || !workspace) return NOCF_E_NULL;
+    if (history_size < 1 || max_iter < 0 || max_eval < 1) return NOCF_E_SHAPE;
+    typename QuadProb<T>::Dev pb;
+    QuadArgs<T> qa;
+    int rc = baseline_quad_setup<T>(prob, d, B, nt, history_size, alphG, &pb, &qa);
+    if (rc) return rc;
+    if (workspace_bytes < baseline_quad_workspace(B, nt, history_size, sizeof(T))) return NOCF_E_WORKSPACE;
+    if (max_iter == 0) return 0;
+    qa.z0 = z0; qa.U = U; qa.loss = loss; qa.n_iter = n_iter; qa.n_evals = n_evals; qa.reason = reason;
+    qa.ws = (T*)workspace;
+    qa.max_iter = max_iter; qa.max_eval = max_eval;
+    qa.lr = lr; qa.tol_grad = tolerance_grad; qa.tol_change = tolerance_change;
+    const size_t ldsBytes = (size_t)blq_layout(nt, history_size).total * sizeof(T);
+    const int per_lane = (4 * nt + NOCF_BLQ_WAVE - 1) / NOCF_BLQ_WAVE;  // L-BFGS vector elements per lane
+    hipStream_t st = (hipStream_t)stream;
+    if (per_lane <= 1) return launch_quad_lbfgs<T, 1>(qa, B, ldsBytes, st);
+    if (per_lane <= 2) return launch_quad_lbfgs<T, 2>(qa, B, ldsBytes, st);
+    if (per_lane <= 4) return launch_quad_lbfgs<T, 4>(qa, B, ldsBytes, st);
+    if (per_lane <= 8) return launch_quad_lbfgs<T, 8>(qa, B, ldsBytes, st);
+    return launch_quad_lbfgs<T, 16>(qa, B, ldsBytes, st);
+}
+}
+
+size_t nocf_baseline_quad_workspace_bytes(int64_t B, int32_t nt, int32_t history_size) {
+    return baseline_quad_workspace(B, nt, history_size, sizeof(float));
+}
+
+size_t nocf_baseline_quad_workspace_bytes_f64(int64_t B, int32_t nt, int32_t history_size) {
+    return baseline_quad_workspace(B, nt, history_size, sizeof(double));
+}
+
+int nocf_baseline_quad_eval_f32(const NocfProb* prob, int32_t d, int64_t B, int32_t nt, double alphG, const float* z0, const float* U,
+                                float* loss, float* grad, float* report, float* traj, void* stream) {
+    return baseline_quad_eval<float>(prob, d, B, nt, alphG, z0, U, loss, grad, report, traj, stream);
 }
 
 int nocf_baseline_quad_eval_f64(const NocfProb64* prob, int32_t d, int64_t B, int32_t nt, double alphG, const double* z0, const double* U,
                                 double* loss, double* grad, double* report, double* traj, void* stream) {
-    if (!z0 || !U || !loss) return NOCF_E_NULL;
-    F64Prob pb;
-    Quad64Args qa;
-    int rc = baseline_quad_setup_f64(prob, d, B, nt, 0, &pb, &qa);
-    if (rc) return rc;
-    qa.z0 = z0; qa.U = const_cast<double*>(U); qa.loss = loss; qa.grad = grad; qa.report = report; qa.traj = traj;
-    qa.aG = alphG; qa.aGh = alphG * 0.5;
-    const size_t ldsBytes = (size_t)blq_layout(nt, 0).total * sizeof(double);
-    hipError_t e = set_lds(baseline_quad_eval_f64_kernel, ldsBytes);
-    if (e) return (int)e;
-    hipLaunchKernelGGL(baseline_quad_eval_f64_kernel, dim3((unsigned)B), dim3(NOCF_BLQ_WAVE), ldsBytes, (hipStream_t)stream, qa);
-    return (int)hipGetLastError();
+    return baseline_quad_eval<double>(prob, d, B, nt, alphG, z0, U, loss, grad, report, traj, stream);
 }
 
-extern "C++" {
-template <int E>
-static int launch_quad_lbfgs_f64(const Quad64Args& qa, int64_t B, size_t ldsBytes, hipStream_t st) {
-    hipError_t e = set_lds(baseline_quad_lbfgs_f64_kernel<E>, ldsBytes);
-    if (e) return (int)e;
-    hipLaunchKernelGGL(baseline_quad_lbfgs_f64_kernel<E>, dim3((unsigned)B), dim3(NOCF_BLQ_WAVE), ldsBytes, st, qa);
-    return (int)hipGetLastError();
-}
+int nocf_baseline_quad_lbfgs_f32(const NocfProb* prob, int32_t d, int64_t B, int32_t nt, double alphG, double lr, int32_t max_iter,
+                                 int32_t max_eval, double tolerance_grad, double tolerance_change, int32_t history_size,
+                                 const float* z0, float* U, float* loss, int32_t* n_iter, int32_t* n_evals, int32_t* reason,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    return baseline_quad_lbfgs<float>(prob, d, B, nt, alphG, lr, max_iter, max_eval, tolerance_grad, tolerance_change, history_size, z0, U,
+                                      loss, n_iter, n_evals, reason, workspace, workspace_bytes, stream);
 }
 
 int nocf_baseline_quad_lbfgs_f64(const NocfProb64* prob, int32_t d, int64_t B, int32_t nt, double alphG, double lr, int32_t max_iter,
                                  int32_t max_eval, double tolerance_grad, double tolerance_change, int32_t history_size,
                                  const double* z0, double* U, double* loss, int32_t* n_iter, int32_t* n_evals, int32_t* reason,
                                  void* workspace, size_t workspace_bytes, void* stream) {
-    if (!z0 || !U || !loss || !n_iter || !n_evals || !reason || !workspace) return NOCF_E_NULL;
-    if (history_size < 1 || max_iter < 0 || max_eval < 1) return NOCF_E_SHAPE;
-    F64Prob pb;
-    Quad64Args qa;
-    int rc = baseline_quad_setup_f64(prob, d, B, nt, history_size, &pb, &qa);
-    if (rc) return rc;
-    if (workspace_bytes < nocf_baseline_quad_workspace_bytes_f64(B, nt, history_size)) return NOCF_E_WORKSPACE;
-    if (max_iter == 0) return 0;
-    qa.z0 = z0; qa.U = U; qa.loss = loss; qa.n_iter = n_iter; qa.n_evals = n_evals; qa.reason = reason;
-    qa.ws = (double*)workspace;
-    qa.aG = alphG; qa.aGh = alphG * 0.5;
-    qa.max_iter = max_iter; qa.max_eval = max_eval;
-    qa.lr = lr; qa.tol_grad = tolerance_grad; qa.tol_change = tolerance_change;
-    const size_t ldsBytes = (size_t)blq_layout(nt, history_size).total * sizeof(double);
-    const int per_lane = (4 * nt + NOCF_BLQ_WAVE - 1) / NOCF_BLQ_WAVE;  // L-BFGS vector elements per lane
-    hipStream_t st = (hipStream_t)stream;
-    if (per_lane <= 1) return launch_quad_lbfgs_f64<1>(qa, B, ldsBytes, st);
-    if (per_lane <= 2) return launch_quad_lbfgs_f64<2>(qa, B, ldsBytes, st);
-    if (per_lane <= 4) return launch_quad_lbfgs_f64<4>(qa, B, ldsBytes, st);
-    if (per_lane <= 8) return launch_quad_lbfgs_f64<8>(qa, B, ldsBytes, st);
-    return launch_quad_lbfgs_f64<16>(qa, B, ldsBytes, st);
+    return baseline_quad_lbfgs<double>(prob, d, B, nt, alphG, lr, max_iter, max_eval, tolerance_grad, tolerance_change, history_size, z0, U,
+                                       loss, n_iter, n_evals, reason, workspace, workspace_bytes, stream);
 }
 
 int nocf_selftest_mfma(const float* a, const float* b, int32_t K, float* out, void* stream) {

@@ -1,4 +1,4 @@
-"""GPU: the double-precision baseline kernels (nocf_baseline_f64.inc, nocf_baseline_quad_f64.inc) against the reference's own
+"""GPU: the double-precision baseline kernels (nocf_baseline_f64.inc, nocf_baseline_quad.inc instantiated for double) against the reference's own
 double-precision values (tests/golden/baseline_f64.npz).
 
 Tolerances.  REL = 1e-9 of each quantity's scale is the project's double-precision tolerance.  The capped L-BFGS
