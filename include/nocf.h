@@ -117,6 +117,13 @@ void nocf_debug_reload_env(void);
  * inherited by child processes (compiler children, self-launched ranks) and survives nocf_debug_reload_env: the in-process fallback of a
  * process that shares its GPU (neuraloc_amd/_lib.py: duo_guard) uses it to switch the weight-stationary kernels off. */
 int nocf_set_knob(const char* name, int32_t value, int32_t clear);
+/* The geometry the per-tile kernels (rollout_kernel / rollout_bwd_kernel) would run a shape with, under the NOCF_NWAVES / NOCF_SUBTILES knobs
+ * in force: out = { T (samples per tile), waves per workgroup, MB, DB (64-column blocks of m and of d+1), KQ1, KQm (k-quads of the two
+ * contraction lengths, padded to 8), SK1, SK6, SKm (split-K factors of the opening, closing and residual products), the split-K cap the LDS
+ * carve ended on (8 or 4 unless LDS was short; 0: no cap fits), LDS floats per workgroup, and 1 / 2 when the plan is that of a
+ * shape-specialised instantiation (2: one taken by the recording forward and the adjoint only), else 0 }.  bwd != 0: the adjoint's plan.
+ * Returns 0 or the code the rollout would return (NOCF_E_SHAPE, NOCF_E_LDS: out[9] is still set, the rest 0).  Makes no GPU call. */
+int nocf_debug_tile_plan(int32_t d, int32_t m, int32_t nTh, int32_t r, int32_t n_agents, int32_t bwd, int32_t out[12]);
 
 /* bytes of scratch `workspace` a call with these shapes needs (packed weight images) */
 size_t nocf_workspace_bytes(int32_t d, int32_t m, int32_t nTh);

@@ -117,7 +117,11 @@ class Phi(nn.Module):
         # recently used workspaces (about 50 MB each for a 2048-row swarm50 batch) and is not copied by deepcopy / pickle.
         nbytes = _lib.lib().nocf_rollout_workspace_bytes(self.d, self.m, self.nTh, int(n))
         if nbytes == 0:
-            raise RuntimeError("nocf_workspace_bytes: unsupported (d, m, nTh)")
+            # (no plan: name the code the rollout would return -- NOCF_E_LDS for a network too wide for the LDS plan.  Like the size query
+            # above this asks for one agent and the forward plan, the problem is not known here: a refusal that only the problem's agent
+            # count causes keeps the plain text)
+            rc = _lib.lib().nocf_debug_tile_plan(self.d, self.m, self.nTh, int(st.r), 1, 0, (C.c_int32 * 12)())
+            raise RuntimeError("nocf_workspace_bytes: unsupported (d, m, nTh)" + (f": {_lib._ERRORS.get(rc, rc)}" if rc < 0 else ""))
         if self._ws is None:
             self._ws = {}
         ws = _pool_get(self._ws, (dev.index, torch.cuda.current_stream(dev).cuda_stream), nbytes, dev)

@@ -90,7 +90,9 @@ constexpr int choose_sk(int nblk, int halves, int nwaves, int cap) {
 }
 
 // fills the shape / image part of the plan; returns 0 or an NOCF_E_* code.  nw_req / S_req / diagHalf: 0 = default.
-constexpr int plan_layout(int d, int m, int nTh, int r, int n_agents, int bwd, int nw_req, int S_req, int diagHalf, DevPlan& out) {
+// cap_out (host only): receives the split-K cap the LDS loop ended on (0 when it ends without a fit).
+constexpr int plan_layout(int d, int m, int nTh, int r, int n_agents, int bwd, int nw_req, int S_req, int diagHalf, DevPlan& out,
+                          int* cap_out = nullptr) {
     if (d < 1 || m < 1 || nTh < 2 || nTh > MAX_NTH || r < 1 || r > d + 1 || r > ZQLD) return NOCF_E_SHAPE;
     if (n_agents > 255) return NOCF_E_SHAPE;
     DevPlan pl{};
@@ -127,7 +129,7 @@ constexpr int plan_layout(int d, int m, int nTh, int r, int n_agents, int bwd, i
     // LDS carve; the split-K cap shrinks until the partial-sum slots fit next to the activations
     const int T = pl.T;
     (void)n_agents;
-    int l = 0;
+    int l = 0, capUsed = 0;
     for (int cap = bwd ? 4 : MAX_SK; cap >= 1; cap >>= 1) {
         pl.pMB = diagHalf ? imax(1, pl.MB / 2) : pl.MB;          // diagHalf: timing experiment only (results are wrong)
         pl.pKQc = diagHalf ? imax(HALF, (pl.KQm / 2) / HALF * HALF) : pl.KQm;
@@ -178,8 +180,9 @@ constexpr int plan_layout(int d, int m, int nTh, int r, int n_agents, int bwd, i
             pl.lSCB = l; l += rup(T * 4 + 8, 4);
         }
         l += 64;                                    // slack: the activation ring's last prefetch reads 32 floats past a row
-        if ((long)l * 4 <= 160 * 1024) break;
+        if ((long)l * 4 <= 160 * 1024) { capUsed = cap; break; }
     }
+    if (cap_out) *cap_out = capUsed;
     pl.ldsFloats = l;
     if ((long)l * 4 > 160 * 1024) return NOCF_E_LDS;
     pl.hN = (float)(1.0 / (nTh - 1));
@@ -1593,13 +1596,13 @@ int nocf_env_int(const char* name, int dflt) {
 static int env_int(const char* name, int dflt) { return nocf_env_int(name, dflt); }
 
 // host wrapper: geometry knobs from the environment, then the (constexpr) layout
-static int make_plan(int d, int m, int nTh, int r, int n_agents, DevPlan* out, int bwd = 0) {
+static int make_plan(int d, int m, int nTh, int r, int n_agents, DevPlan* out, int bwd = 0, int* cap_out = nullptr) {
 #ifdef NOCF_STAMPS
     const int diagHalf = env_int("NOCF_DIAG_HALF", 0);    // diagnostic builds only: a timing experiment with wrong results
 #else
     const int diagHalf = 0;
 #endif
-    return plan_layout(d, m, nTh, r, n_agents, bwd, env_int("NOCF_NWAVES", 0), env_int("NOCF_SUBTILES", 0), diagHalf, *out);
+    return plan_layout(d, m, nTh, r, n_agents, bwd, env_int("NOCF_NWAVES", 0), env_int("NOCF_SUBTILES", 0), diagHalf, *out, cap_out);
 }
 
 // Mono (one-CU weight-stationary) plan: returns 0 and fills *out when the shape has an instantiation, else an NOCF_E_* code.
@@ -1753,6 +1756,30 @@ int nocf_set_knob(const char* name, int32_t value, int32_t clear) {
     if (!name || strncmp(name, "NOCF_", 5) != 0) return NOCF_E_NULL;
     std::lock_guard<std::mutex> lk(g_env_mu);
     if (clear) g_env_override.erase(name); else g_env_override[name] = value;
+    return 0;
+}
+
+int nocf_debug_tile_plan(int32_t d, int32_t m, int32_t nTh, int32_t r, int32_t n_agents, int32_t bwd, int32_t out[12]) {
+    if (!out) return NOCF_E_NULL;
+    for (int i = 0; i < 12; ++i) out[i] = 0;
+    DevPlan pl;
+    int cap = 0;
+    const int rc = make_plan(d, m, nTh, r, n_agents, &pl, bwd ? 1 : 0, &cap);
+    out[9] = cap;
+    if (rc) return rc;
+    // 1: the plan of a FIXED_SHAPES instantiation (evaluation, record and adjoint); 2: of a training-only one (record and adjoint)
+    int fixed = 0;
+#define NOCF_IS_FIXED(D, M, NTH, R, NAG) \
+    if (!fixed && (bwd ? plan_is<FixedPlan<D, M, NTH, R, NAG, 1>>(pl) : plan_is<FixedPlan<D, M, NTH, R, NAG, 0>>(pl))) fixed = 1;
+    FIXED_SHAPES(NOCF_IS_FIXED)
+    FIXED_SHAPES_EXTRA(NOCF_IS_FIXED)
+#undef NOCF_IS_FIXED
+#define NOCF_IS_FIXED(D, M, NTH, R, NAG) \
+    if (!fixed && (bwd ? plan_is<FixedPlan<D, M, NTH, R, NAG, 1>>(pl) : plan_is<FixedPlan<D, M, NTH, R, NAG, 0>>(pl))) fixed = 2;
+    FIXED_SHAPES_TRAIN(NOCF_IS_FIXED)
+#undef NOCF_IS_FIXED
+    const int v[12] = {pl.T, pl.nwaves, pl.MB, pl.DB, pl.KQ1, pl.KQm, pl.SK1, pl.SK6, pl.SKm, cap, pl.ldsFloats, fixed};
+    for (int i = 0; i < 12; ++i) out[i] = v[i];
     return 0;
 }
 
@@ -1994,7 +2021,8 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
     rc = fill_prob(prob, phi->d, &pb);
     if (rc) return rc;
     DevPlan pl;
-    rc = make_plan(phi->d, phi->m, phi->nTh, phi->r, pb.nAgents, &pl);
+    int skCap = 0;
+    rc = make_plan(phi->d, phi->m, phi->nTh, phi->r, pb.nAgents, &pl, 0, &skCap);
     if (rc) return rc;
     pl.cb = phi->cb;
     if (workspace_bytes < plan_ws_bytes(pl)) return NOCF_E_WORKSPACE;
@@ -2180,6 +2208,9 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
             }
         }
         if (!launched) g_last_kernel = dist ? "rollout_kernel<generic, dist>" : "rollout_kernel<generic>";
+        if (!launched && env_int("NOCF_DEBUG", 0))
+            fprintf(stderr, "[nocf] generic rollout kernel: T %d, %d waves, SK1/SK6/SKm %d/%d/%d, cap %d, LDS %zu B/workgroup\n",
+                    pl.T, pl.nwaves, pl.SK1, pl.SK6, pl.SKm, skCap, ldsBytes);
         if (!launched && dist) switch (pl.T / 4) {
             case 1: e = set_lds(rollout_kernel<1, DynPlan, true>, ldsBytes); if (e) return (int)e;
                     hipLaunchKernelGGL((rollout_kernel<1, DynPlan, true>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
@@ -2488,7 +2519,8 @@ static int rollout_bwd_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n,
         if (rc) return rc;
     }
     DevPlan pl;
-    rc = make_plan(phi->d, phi->m, phi->nTh, phi->r, pb.nAgents, &pl, 1);
+    int skCap = 0;
+    rc = make_plan(phi->d, phi->m, phi->nTh, phi->r, pb.nAgents, &pl, 1, &skCap);
     if (rc) return rc;
     if (pl.T != 4) return NOCF_E_SHAPE;
     pl.cb = phi->cb;
@@ -2518,7 +2550,12 @@ static int rollout_bwd_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n,
         FIXED_SHAPES_TRAIN(NOCF_TRY_FIXED)
 #undef NOCF_TRY_FIXED
     }
+    const bool specialised = fk != nullptr;
     if (!fk) fk = reinterpret_cast<const void*>(rollout_bwd_kernel<1, DynPlan>);
+    if (env_int("NOCF_DEBUG", 0))
+        fprintf(stderr, "[nocf] %s rollout adjoint kernel: T %d, %d waves, SK1/SK6/SKm %d/%d/%d, cap %d, LDS %zu B/workgroup, activations %s\n",
+                specialised ? "specialised" : "generic", pl.T, pl.nwaves, pl.SK1, pl.SK6, pl.SKm, skCap, ldsBytes,
+                ba.act ? "from the record" : "recomputed");
     hipError_t e = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes);
     if (e) return (int)e;
     {
