@@ -12,7 +12,10 @@ line, appended to `<save>/deploy_times`) plus a batch, and with --do_shock runs 
 --prec double runs the double-precision rollout (nocf_rollout_f64), like the reference's evalOC.py:28-31.
 Differences, on purpose: --make_vid only states that videos are out of scope; --gpu/--batch are additions, and so is
 --noise SIGMA [--noise_paths R --noise_seed S]: the distribution of the costs over R rollouts of xInit under per-step Brownian
-disturbances (neuraloc_amd.disturb; single precision), one line per quantity and `<save>/figs/eval_<name>_noise.npz`."""
+disturbances (neuraloc_amd.disturb; single precision), one line per quantity and `<save>/figs/eval_<name>_noise.npz`;
+--worst EPS [--worst_steps K]: the disturbance path of energy ||W||_2 <= EPS that hurts the control objective L + alph0 G of xInit most
+(neuraloc_amd.worst_case_disturbances, K projected ascent steps; single precision), one line per quantity, nominal against worst case,
+and `<save>/figs/eval_<name>_worst.npz`."""
 import argparse
 import os
 import time
@@ -39,6 +42,9 @@ p.add_argument("--noise", type=float, default=None, metavar="SIGMA",
                help="(addition) roll xInit out under Brownian state disturbances sigma dB at every step (neuraloc_amd.noise_study)")
 p.add_argument("--noise_paths", type=int, default=256, metavar="R", help="(addition) noise realisations per start for --noise")
 p.add_argument("--noise_seed", type=int, default=0, metavar="S", help="(addition) seed of the disturbances for --noise")
+p.add_argument("--worst", type=float, default=None, metavar="EPS",
+               help="(addition) search the per-step state disturbances of path norm <= EPS that hurt xInit's L + G most (neuraloc_amd.worst_case_disturbances)")
+p.add_argument("--worst_steps", type=int, default=20, metavar="K", help="(addition) projected ascent steps for --worst")
 
 
 def main(argv=None):
@@ -47,6 +53,8 @@ def main(argv=None):
     prec = torch.float64 if args.prec == "double" else torch.float32          # evalOC.py:28-31
     if args.noise is not None and prec != torch.float32:                     # refused before anything runs or is written
         raise SystemExit("--noise runs in single precision only (the double-precision rollout takes no disturbance)")
+    if args.worst is not None and prec != torch.float32:
+        raise SystemExit("--worst runs in single precision only (the double-precision rollout takes no disturbance)")
     os.makedirs(os.path.join(args.save, "figs"), exist_ok=True)
     print(args)
     dev = f"cuda:{args.gpu}"
@@ -121,6 +129,22 @@ def main(argv=None):
                      **{f"{name}/{k}": st[name][k].cpu().numpy() for name in ("L+G", "G", "Q", "W") for k in keys})
             print("saved the noise study to " + sPath)
             out["noise"] = {name: {k: float(st[name][k][0]) for k in keys} for name in ("L+G", "G", "Q", "W")}
+        if args.worst is not None:
+            nom = na.disturbed_rollout(xInit, net, prob, nt, torch.zeros(nt, xInit.shape[0], xInit.shape[1], device=xInit.device), alph=alph)
+            res = na.worst_case_disturbances(xInit, net, prob, nt, args.worst, steps=args.worst_steps, alph=alph, objective="control")
+            na.check_errors(sync=True)
+            t0_, t1_ = nom["persample"][0], res["persample"][0]
+            print("worst eps=%g, %d steps: %-4s %11s %11s" % (args.worst, args.worst_steps, "", "nominal", "worst case"))
+            rows = {"L+G": (float(t0_[0] + alph[0] * t0_[1]), float(t1_[0] + alph[0] * t1_[1])), "G": (float(t0_[1]), float(t1_[1])),
+                    "Q": (float(t0_[5]), float(t1_[5])), "W": (float(t0_[6]), float(t1_[6]))}
+            for name in ("L+G", "G", "Q", "W"):
+                print("worst %-4s %11.4e %11.4e" % ((name,) + rows[name]))
+            sPath = os.path.join(args.save, "figs", strTitle + "_worst.npz")
+            np.savez(sPath, eps=args.worst, steps=args.worst_steps, W=res["W"].cpu().numpy(), history=res["history"].cpu().numpy(),
+                     persample=res["persample"].cpu().numpy(), nominal=nom["persample"].cpu().numpy())
+            print("saved the worst-case disturbance to " + sPath)
+            out["worst"] = {name: {"nominal": rows[name][0], "worst": rows[name][1]} for name in rows}
+            out["worst"]["norm"] = float(res["W"].pow(2).sum().sqrt())
     return out
 
 

@@ -199,7 +199,8 @@ int nocf_rollout_disturbed_f32(const NocfPhi* phi, const NocfProb* prob, const f
  * the first stage of step k+1 is recorded at the DISPLACED state, and W[nt-1] lands on z_out, where the terminal block is evaluated.
  * W does not depend on the parameters, so the adjoint of the disturbed scheme is the adjoint of the undisturbed one at these recorded
  * inputs: s_all and z_out go to nocf_rollout_bwd_small_f32 / nocf_rollout_bwd_mid_f32 / nocf_rollout_bwd_act_f32 unchanged (they read
- * every stage input from s_all and the final state from z_out; none re-derives a state from the previous step).  dJ/dW is not formed.
+ * every stage input from s_all and the final state from z_out; none re-derives a state from the previous step).  These three do not form dJ/dW;
+ * nocf_rollout_bwd_states_f32 (below) does, from the same s_all and z_out.
  * W == 0 gives nocf_rollout_record_act_f32's outputs on the same kernel.
  *   act_rec, recorded   as for nocf_rollout_record_act_f32: the one-CU kernel writes the activation record (recorded = 1), the lane and
  *                       per-tile kernels do not (recorded = 0; pass NULL for shapes the one-CU kernel does not take)
@@ -412,6 +413,45 @@ int nocf_rollout_bwd_mid_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n
                              const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
                              const float* act_rec, float* gpart, int64_t gpart_rows, float* lam0, void* workspace, size_t workspace_bytes,
                              void* stream);
+
+/*
+ * The STATE-ONLY adjoint: the lambda recursion of the three adjoints above (nocf_rollout_bwd_small_f32 / _mid_f32 / _act_f32) with every
+ * parameter-gradient operation compiled out -- no gradient rows or accumulators, no outer products, no partial vectors, no row streams --
+ * and the per-step state cotangents written out.  The inner loop of a worst-case disturbance search (nocf_disturbance_ascent_f32) and
+ * the sensitivity of a disturbed rollout: with z_{k+1} = step(z_k) + W[k] (nocf_rollout_record_disturbed_f32), dJ/dW[k] is the cotangent
+ * of z_{k+1}, which every adjoint kernel holds when it begins the last stage of step k.
+ *   inputs   those of the three adjoints; s_all / z_final from ANY recording forward, disturbed or not; hs the forward's fp32 step sizes;
+ *            inv_n = 1 / (global batch size) (1: every row's own objective); alph[3..5] = 0 is supported: the control objective L + alph0 G
+ *   act_rec  nullable; the forward's activation record, used by the one-CU kernel only (when the forward reported recorded = 1)
+ *   lam0     device [n, d] = dJ/dx0 (nullable)
+ *   lamW     device [nt, n, d] (nullable), time-major like W, contiguous: lamW[k] = the state cotangent behind step k = dJ/dW[k];
+ *            lamW[nt-1] is the terminal cotangent dJ/dx(T).  Only rows < n and d floats per row are written
+ *   workspace: nocf_workspace_bytes (same as the forward's)
+ * Dispatch: the register-resident small-network kernel, then the one-CU kernel, then the per-tile kernel -- the order of
+ * nocf_rollout_record_disturbed_f32, so the adjoint runs on the forward's family.  nocf_last_rollout_kernel() reports
+ * "rollout_lane_bwd_kernel<states>", "rollout_mono_bwd_kernel<states>" or "rollout_bwd_kernel<states>".
+ * lam0 == NULL and lamW == NULL: NOCF_E_NULL.  Shape, stepper, workspace and LDS refusals are the three adjoints' own.  Every refusal
+ * returns before anything is enqueued.  float32 only.
+ */
+int nocf_rollout_bwd_states_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t nt, int32_t stepper, double t1,
+                                const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
+                                const float* act_rec, float* lam0, float* lamW,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * One step of projected gradient ascent on per-row disturbance paths, in place: for every row i, over its [nt, d] path of W,
+ *     W_i += step (mask o g_i) / ||mask o g_i||_2          (the row is left untouched when that norm is 0 or not finite)
+ *     W_i *= eps / ||W_i||_2   when ||W_i||_2 > eps         (projection onto the ball over the whole path)
+ *   W     device [nt, n, d] float32, time-major, contiguous: updated
+ *   g     device [nt, n, d]: the ascent direction (lamW of nocf_rollout_bwd_states_f32); not modified
+ *   mask  device [d] floats of 0 / 1 (nullable), the meaning of brownian_disturbances(mask=): masked components take no step and keep
+ *         their bits; the projection scales the whole row
+ * One wavefront per row; both norms are reductions in a fixed order, no atomics: identical inputs give identical bits.  With the
+ * recording forward and the state-only adjoint an iteration of the search is three launches and no host round trip.
+ * n, nt, d < 1 or a negative / non-finite step or eps: NOCF_E_SHAPE.
+ */
+int nocf_disturbance_ascent_f32(float* W, const float* g, const float* mask, int64_t n, int32_t nt, int32_t d,
+                                double step, double eps, void* stream);
 
 /*
  * C[m, n] (+)= sum_k A[k, 0..m) (x) B[k, 0..n) for small outputs (m, n <= 512, at most 64 tiles of 64 x 64) and very many rows: the contraction of the rows that

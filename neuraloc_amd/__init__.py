@@ -11,9 +11,11 @@ from .baseline import baseline_loss, baseline_report, baseline_adam_steps, solve
 from .baseline_quad import quad_baseline_loss, quad_baseline_report, quad_initial_guess, solve_baseline_quad
 from .disturb import disturbed_rollout, brownian_disturbances, noise_study
 from .train import disturbed_ocflow_train
+from .adversary import disturbance_gradient, worst_case_disturbances
 
 __all__ = ["Phi", "ResNN", "antiderivTanh", "derivTanh", "OCflow", "ocG", "Cross2D", "SwarmTraj",
            "Quadcopter", "initProb", "resample", "OCflow_sharded", "shard_rows", "reduce_cost_sums", "check_errors",
            "baseline_loss", "baseline_report", "baseline_adam_steps", "solve_baseline",
            "quad_baseline_loss", "quad_baseline_report", "quad_initial_guess", "solve_baseline_quad",
-           "disturbed_rollout", "brownian_disturbances", "noise_study", "disturbed_ocflow_train"]
+           "disturbed_rollout", "brownian_disturbances", "noise_study", "disturbed_ocflow_train",
+           "disturbance_gradient", "worst_case_disturbances"]

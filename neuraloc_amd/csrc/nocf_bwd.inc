@@ -44,6 +44,9 @@ struct BwdArgs {
     // cotangent of grad Phi(s) (src/Phi.py:99-138 under autograd); sbar_out [n][d+1] = (d grad Phi / d s)' gbar, the rows of the first block
     // carry the parameter gradients
     const float* gbar_in; float* sbar_out;
+    // state-only instantiations (STATES, nocf_rollout_bwd_states_f32): [nt][n][d] (nullable), the state cotangent LAM when the last stage of
+    // step k begins = dJ/dW[k] of a disturbed rollout (z_{k+1} = step(z_k) + W[k]); lamW[nt-1] is the terminal cotangent dJ/dx(T)
+    float* lamW;
 };
 
 // d(raw obstacle cost of agent a)/dx at the sample x, added into gq[3]: the per-agent math of physics_xgrad's obstacle part
@@ -231,7 +234,8 @@ __device__ void quad_adjoint(const Ctx& c, const DevPlan& pl, const DevProb& pb,
 //   obar = (1-tau_0^2).taubar_0 + tau_0.ubar_0 ;  sbar = K0' obar + A'A gbar
 // in: GB[t][0..d] ; out: SBAR[t][0..d], and the row streams of this evaluation at global row `grow0 + t`
 // (per layer i: hN v_i with abar_{i-1}, and qbar_i with u_{i-1}, at layer offset (i-1)*lstride).
-template <int S>
+// STATES: no row stream is stored and no stream pointer is dereferenced (the state-only adjoint: SBAR is all the caller needs).
+template <int S, bool STATES = false>
 __device__ void phi_vjp(const Ctx& c, const DevPlan& pl, Ring& rg, const BwdArgs& ba, long grow0, long nvalid) {
     const int T = pl.T, LD = pl.LD, m = pl.m, D1 = pl.D1, r = pl.r, L = pl.nTh - 1, TLD = pl.T * pl.LD;
     const float hN = pl.hN;
@@ -291,7 +295,7 @@ __device__ void phi_vjp(const Ctx& c, const DevPlan& pl, Ring& rg, const BwdArgs
                     lds[otb + t * LD + col] = lds[oAi + t * LD + col] * vb;     // taubar_i
                 } else {
                     lds[oq + t * LD + col] = (1.f - ti * ti) * wv[col] * vb;    // qbar_L  (a_L = w, ubar_L = 0)
-                    if (t < nvalid) ba.Wb[(grow0 + t) * m + col] = ab;          // dw row
+                    if constexpr (!STATES) { if (t < nvalid) ba.Wb[(grow0 + t) * m + col] = ab; }          // dw row
                 }
             }
         });
@@ -326,6 +330,7 @@ __device__ void phi_vjp(const Ctx& c, const DevPlan& pl, Ring& rg, const BwdArgs
     });
     __syncthreads();
     TL(c, 58);
+    if constexpr (!STATES) {
     // row streams of this evaluation (coalesced rows), after the last phase: nothing here competes with a weight prefetch
     const int oy = oV(0);
     // the m-wide streams go out as 16-B pieces (one float4 per lane and stream: a quarter of the store instructions of a
@@ -374,9 +379,10 @@ __device__ void phi_vjp(const Ctx& c, const DevPlan& pl, Ring& rg, const BwdArgs
             ba.Sx[row * D1 + i] = lds[pl.lSB + t * pl.LDs + i];
         }
     }
+    }
 }
 
-template <int S>
+template <int S, bool STATES = false>
 __device__ __forceinline__ void rollout_bwd_body(const DevPlan& pl, const DevPlan* __restrict__ plp, const DevProb& pb,
                                                  const float* __restrict__ ws, const BwdArgs& ba) {
     Ctx c;
@@ -428,6 +434,13 @@ __device__ __forceinline__ void rollout_bwd_body(const DevPlan& pl, const DevPla
             }
             if (c.tid < T) SB[c.tid * pl.LDs + d] = ba.t1;
         } else {
+            if constexpr (STATES) {
+                if (st == ba.nstage - 1 && ba.lamW)
+                    for (int j = c.tid; j < T * d; j += c.nthreads) {
+                        const int t = j / d, i = j - t * d;
+                        if (t < nvalid) ba.lamW[((long)k * ba.n + row0 + t) * d + i] = LAM[t * ZLD + i];
+                    }
+            }
             if (st == ba.nstage - 1)
                 for (int j = c.tid; j < T * d; j += c.nthreads) { const int t = j / d, i = j - t * d; XS[t * ZLD + i] = 0.f; XP[t * ZLD + i] = 0.f; }
             const float* src = ba.sAll + (ev * ba.n) * D1;
@@ -512,6 +525,7 @@ __device__ __forceinline__ void rollout_bwd_body(const DevPlan& pl, const DevPla
             __syncthreads();
         }
         if (fin) {
+            if constexpr (!STATES) {
             // value rows: the cotangent of Phi1 reuses the forward quantities: ubar_i = phib a_i, so
             // qbar_i = phib hN v_i, obar = phib y, dw row = phib u_L  (no extra GEMM)
             const long vrow0 = (total + 1) * ba.n + row0;
@@ -531,6 +545,7 @@ __device__ __forceinline__ void rollout_bwd_body(const DevPlan& pl, const DevPla
                 }
                 for (int i = c.tid; i < D1; i += c.nthreads) ba.Sx[row * D1 + i] = SB[t * pl.LDs + i];
                 if (c.tid == 0 && !ba.value_only) ba.PHIb[row0 + t] = phib;
+            }
             }
         } else if (gmode) {
             for (int j = c.tid; j < T * D1; j += c.nthreads) {
@@ -569,7 +584,7 @@ __device__ __forceinline__ void rollout_bwd_body(const DevPlan& pl, const DevPla
             if (!quad) physics_xgrad(c, pl, pb, SC, 4);
             TL(c, 47);
         }
-        phi_vjp<S>(c, pl, rg, ba, ev * ba.n + row0, nvalid);
+        phi_vjp<S, STATES>(c, pl, rg, ba, ev * ba.n + row0, nvalid);
         TL(c, 59);
         if (gmode)
             for (int j = c.tid; j < T * D1; j += c.nthreads) {
@@ -597,13 +612,13 @@ __device__ __forceinline__ void rollout_bwd_body(const DevPlan& pl, const DevPla
         }
 }
 
-template <int S, class SP>
+template <int S, class SP, bool STATES = false>
 __global__ void __launch_bounds__(NOCF_MAXTHREADS) rollout_bwd_kernel(const DevPlan* __restrict__ plp, DevProb pb,
                                                                       const float* __restrict__ ws, BwdArgs ba) {
     if constexpr (SP::fixed) {
         constexpr DevPlan plc = SP::make();
-        rollout_bwd_body<S>(plc, plp, pb, ws, ba);
+        rollout_bwd_body<S, STATES>(plc, plp, pb, ws, ba);
     } else {
-        rollout_bwd_body<S>(*plp, plp, pb, ws, ba);
+        rollout_bwd_body<S, STATES>(*plp, plp, pb, ws, ba);
     }
 }

@@ -1811,12 +1811,13 @@ int64_t nocf_small_grad_floats(int32_t d, int32_t m) {
     return (long)m * D1 + m + (long)m * m + m + m + D1 + 1 + D1 * D1;
 }
 
-int nocf_rollout_bwd_small_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t nt, int32_t stepper, double t1,
-                               const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
-                               float* gpart, float* lam0, void* stream) {
+// states: the state-only instantiation (nocf_rollout_bwd_states_f32) -- no gpart, lam0 and / or lamW
+static int bwd_small_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t nt, int32_t stepper, double t1,
+                          const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
+                          float* gpart, float* lam0, float* lamW, bool states, void* stream) {
     int rc = check_phi(phi);
     if (rc) return rc;
-    if (!alph || !s_all || !z_final || !hs || !gpart) return NOCF_E_NULL;
+    if (!alph || !s_all || !z_final || !hs || (!states && !gpart) || (states && !lam0 && !lamW)) return NOCF_E_NULL;
     if (n < 1 || nt < 1) return NOCF_E_SHAPE;
     if (stepper != NOCF_RK4 && stepper != NOCF_RK1) return NOCF_E_STEPPER;
     DevProb pb;
@@ -1832,25 +1833,32 @@ int nocf_rollout_bwd_small_f32(const NocfPhi* phi, const NocfProb* prob, int64_t
     la.d = phi->d; la.m = phi->m; la.r = phi->r; la.nAg = pb.nAgents; la.cb = phi->cb;
     la.sAll = s_all; la.zT = z_final; la.hs = hs; la.n = n; la.nt = nt; la.nstage = (stepper == NOCF_RK4) ? 4 : 1;
     la.t1 = (float)t1; la.a0 = alph[0]; la.a3 = alph[3]; la.a4 = alph[4]; la.a5 = alph[5]; la.inv_n = (float)inv_n;
-    la.gpart = gpart; la.P_total = nocf_small_grad_floats(phi->d, phi->m); la.lam0 = lam0;
+    la.gpart = gpart; la.P_total = nocf_small_grad_floats(phi->d, phi->m); la.lam0 = lam0; la.lamW = states ? lamW : nullptr;
     hipStream_t st = (hipStream_t)stream;
     const int grid = (int)((n + 3) / 4);
     const int MPsel = phi->m <= 16 ? 16 : 32;
     const int DPsel = phi->d + 1 <= 8 ? 8 : (phi->d + 1 <= 16 ? 16 : 32);
     if (env_int("NOCF_DEBUG", 0)) fprintf(stderr, "[nocf] lane adjoint kernel\n");
-#define NOCF_LANEB_LAUNCH(MPV, DPV) hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV>), dim3(grid), dim3(256), 0, st, la, pb)
+#define NOCF_LANEB_LAUNCH(MPV, DPV) do { if (states) hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV, true>), dim3(grid), dim3(256), 0, st, la, pb); \
+                                          else hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV>), dim3(grid), dim3(256), 0, st, la, pb); } while (0)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (g_prof_on) {
         if (hipEventCreate(&ev0) || hipEventCreate(&ev1)) return (int)hipErrorUnknown;
         (void)hipEventRecord(ev0, st);
     }
-    if (MPsel == 16) { if (DPsel == 8) NOCF_LANEB_LAUNCH(16, 8); else if (DPsel == 16) NOCF_LANEB_LAUNCH(16, 16); else NOCF_LANEB_LAUNCH(16, 32); }
-    else             { if (DPsel == 8) NOCF_LANEB_LAUNCH(32, 8); else if (DPsel == 16) NOCF_LANEB_LAUNCH(32, 16); else NOCF_LANEB_LAUNCH(32, 32); }
+    if (MPsel == 16) { if (DPsel == 8) { NOCF_LANEB_LAUNCH(16, 8); } else if (DPsel == 16) { NOCF_LANEB_LAUNCH(16, 16); } else { NOCF_LANEB_LAUNCH(16, 32); } }
+    else             { if (DPsel == 8) { NOCF_LANEB_LAUNCH(32, 8); } else if (DPsel == 16) { NOCF_LANEB_LAUNCH(32, 16); } else { NOCF_LANEB_LAUNCH(32, 32); } }
 #undef NOCF_LANEB_LAUNCH
     if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
-    g_last_kernel = "rollout_lane_bwd_kernel";
+    g_last_kernel = states ? "rollout_lane_bwd_kernel<states>" : "rollout_lane_bwd_kernel";
     g_last_errp = nullptr;
     return (int)hipGetLastError();
+}
+
+int nocf_rollout_bwd_small_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t nt, int32_t stepper, double t1,
+                               const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
+                               float* gpart, float* lam0, void* stream) {
+    return bwd_small_impl(phi, prob, n, nt, stepper, t1, alph, inv_n, s_all, z_final, hs, gpart, lam0, nullptr, false, stream);
 }
 
 int nocf_contract_f32(const float* A, const float* B, int64_t K, int32_t m, int32_t n, float* C, int32_t accumulate,
@@ -2336,7 +2344,7 @@ static int rollout_bwd_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n,
                             const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
                             float* Y, float* Ob, float* V, float* Ab, float* Qb, float* U0, float* Wb, float* Gb, float* Sx,
                             float* PHIb, float* lam0, const float* act_rec, void* workspace, size_t workspace_bytes, void* stream,
-                            int value_only = 0, const float* gbar_in = nullptr, float* sbar_out = nullptr);
+                            int value_only = 0, const float* gbar_in = nullptr, float* sbar_out = nullptr, bool states = false, float* lamW = nullptr);
 
 // ---- training tape + split-role adjoint (nocf_duo_bwd.inc)
 static void tape_offsets(int32_t d, int32_t m, int64_t n, int32_t nt, int32_t stepper, size_t* oU1, size_t* oSc, size_t* total) {
@@ -2501,12 +2509,14 @@ static int rollout_bwd_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n,
                             const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
                             float* Y, float* Ob, float* V, float* Ab, float* Qb, float* U0, float* Wb, float* Gb, float* Sx,
                             float* PHIb, float* lam0, const float* act_rec, void* workspace, size_t workspace_bytes, void* stream,
-                            int value_only, const float* gbar_in, float* sbar_out) {
+                            int value_only, const float* gbar_in, float* sbar_out, bool states, float* lamW) {
+    // states: the state-only instantiation (nocf_rollout_bwd_states_f32) -- no row stream, lam0 and / or lamW
     int rc = check_phi(phi);
     if (rc) return rc;
     if (value_only) { if (!s_all || nt != 0 || (value_only == 2 && (!gbar_in || !sbar_out))) return NOCF_E_NULL; }
     else if (!alph || !z_final || !hs) return NOCF_E_NULL;
-    if (!s_all || !Y || !Ob || !V || !Ab || !Qb || !U0 || !Wb || !Gb || !Sx || (!PHIb && value_only != 2) || !workspace)
+    if (states) { if (value_only || !s_all || (!lam0 && !lamW) || !workspace) return NOCF_E_NULL; }
+    else if (!s_all || !Y || !Ob || !V || !Ab || !Qb || !U0 || !Wb || !Gb || !Sx || (!PHIb && value_only != 2) || !workspace)
         return NOCF_E_NULL;
     if (n < 1 || (nt < 1 && !value_only)) return NOCF_E_SHAPE;
     if (stepper != NOCF_RK4 && stepper != NOCF_RK1) return NOCF_E_STEPPER;
@@ -2536,13 +2546,20 @@ static int rollout_bwd_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n,
     if (alph) { ba.a0 = alph[0]; ba.a3 = alph[3]; ba.a4 = alph[4]; ba.a5 = alph[5]; } else { ba.a0 = ba.a3 = ba.a4 = ba.a5 = 0.f; }
     ba.inv_n = (float)inv_n; ba.value_only = value_only; ba.gbar_in = gbar_in; ba.sbar_out = sbar_out;
     ba.Y = Y; ba.Ob = Ob; ba.V = V; ba.Ab = Ab; ba.Qb = Qb; ba.U0 = U0; ba.Wb = Wb; ba.Gb = Gb; ba.Sx = Sx;
-    ba.PHIb = PHIb; ba.lam0 = lam0;
+    ba.PHIb = PHIb; ba.lam0 = lam0; ba.lamW = states ? lamW : nullptr;
     ba.act = (act_rec && phi->nTh == 2) ? act_rec : nullptr; ba.actRows = (long)nt * ba.nstage * n;
     ba.lstride = ((long)nt * ba.nstage + 2) * n * phi->m;
     ba.gpart = nullptr; ba.gstride = 0;
     const size_t ldsBytes = (size_t)pl.ldsFloats * 4;
     const void* fk = nullptr;
-    if (env_int("NOCF_FIXED", 1)) {
+    if (states && env_int("NOCF_FIXED", 1)) {
+        // (the shapes whose disturbed forward is specialised too; the training-only shapes are the lane kernel's and take the generic one here)
+#define NOCF_TRY_FIXED(D, M, NTH, R, NAG) \
+        if (!fk && plan_is<FixedPlan<D, M, NTH, R, NAG, 1>>(pl)) fk = reinterpret_cast<const void*>(rollout_bwd_kernel<1, FixedPlan<D, M, NTH, R, NAG, 1>, true>);
+        FIXED_SHAPES(NOCF_TRY_FIXED)
+        FIXED_SHAPES_EXTRA(NOCF_TRY_FIXED)
+#undef NOCF_TRY_FIXED
+    } else if (env_int("NOCF_FIXED", 1)) {
 #define NOCF_TRY_FIXED(D, M, NTH, R, NAG) \
         if (!fk && plan_is<FixedPlan<D, M, NTH, R, NAG, 1>>(pl)) fk = reinterpret_cast<const void*>(rollout_bwd_kernel<1, FixedPlan<D, M, NTH, R, NAG, 1>>);
         FIXED_SHAPES(NOCF_TRY_FIXED)
@@ -2551,7 +2568,7 @@ static int rollout_bwd_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n,
 #undef NOCF_TRY_FIXED
     }
     const bool specialised = fk != nullptr;
-    if (!fk) fk = reinterpret_cast<const void*>(rollout_bwd_kernel<1, DynPlan>);
+    if (!fk) fk = states ? reinterpret_cast<const void*>(rollout_bwd_kernel<1, DynPlan, true>) : reinterpret_cast<const void*>(rollout_bwd_kernel<1, DynPlan>);
     if (env_int("NOCF_DEBUG", 0))
         fprintf(stderr, "[nocf] %s rollout adjoint kernel: T %d, %d waves, SK1/SK6/SKm %d/%d/%d, cap %d, LDS %zu B/workgroup, activations %s\n",
                 specialised ? "specialised" : "generic", pl.T, pl.nwaves, pl.SK1, pl.SK6, pl.SKm, skCap, ldsBytes,
@@ -2568,7 +2585,7 @@ static int rollout_bwd_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n,
         e = hipLaunchKernel(fk, dim3((int)((n + 3) / 4)), dim3(pl.nwaves * 64), args, ldsBytes, st);
         if (e) return (int)e;
         if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
-        g_last_kernel = "rollout_bwd_kernel";
+        g_last_kernel = states ? "rollout_bwd_kernel<states>" : "rollout_bwd_kernel";
         g_last_errp = nullptr;
     }
     return (int)hipGetLastError();
@@ -2590,18 +2607,19 @@ int64_t nocf_mid_grad_rows(int32_t d, int32_t m, int32_t nTh, int32_t r, int32_t
 #endif
 }
 
-int nocf_rollout_bwd_mid_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t nt, int32_t stepper, double t1,
-                             const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
-                             const float* act_rec, float* gpart, int64_t gpart_rows, float* lam0, void* workspace, size_t workspace_bytes,
-                             void* stream) {
+// states: the state-only instantiation (nocf_rollout_bwd_states_f32) -- no gpart, lam0 and / or lamW
+static int bwd_mid_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t nt, int32_t stepper, double t1,
+                        const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
+                        const float* act_rec, float* gpart, int64_t gpart_rows, float* lam0, float* lamW, bool states,
+                        void* workspace, size_t workspace_bytes, void* stream) {
 #ifdef NOCF_JIT_ONLY
     (void)phi; (void)prob; (void)n; (void)nt; (void)stepper; (void)t1; (void)alph; (void)inv_n; (void)s_all; (void)z_final; (void)hs;
-    (void)act_rec; (void)gpart; (void)gpart_rows; (void)lam0; (void)workspace; (void)workspace_bytes; (void)stream;
+    (void)act_rec; (void)gpart; (void)gpart_rows; (void)lam0; (void)lamW; (void)states; (void)workspace; (void)workspace_bytes; (void)stream;
     return NOCF_E_SHAPE;
 #else
     int rc = check_phi(phi);
     if (rc) return rc;
-    if (!alph || !s_all || !z_final || !hs || !gpart || !workspace) return NOCF_E_NULL;
+    if (!alph || !s_all || !z_final || !hs || (!states && !gpart) || (states && !lam0 && !lamW) || !workspace) return NOCF_E_NULL;
     if (n < 1 || nt < 1) return NOCF_E_SHAPE;
     if (stepper != NOCF_RK4 && stepper != NOCF_RK1) return NOCF_E_STEPPER;
     DevProb pb;
@@ -2609,7 +2627,7 @@ int nocf_rollout_bwd_mid_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n
     if (rc) return rc;
     const int64_t rows = nocf_mid_grad_rows(phi->d, phi->m, phi->nTh, phi->r, pb.nAgents, n);
     if (rows == 0) return NOCF_E_SHAPE;
-    if (gpart_rows < rows) return NOCF_E_WORKSPACE;
+    if (!states && gpart_rows < rows) return NOCF_E_WORKSPACE;
     DevPlan pl;
     rc = make_plan(phi->d, phi->m, phi->nTh, phi->r, pb.nAgents, &pl, 0);
     if (rc) return rc;
@@ -2629,12 +2647,13 @@ int nocf_rollout_bwd_mid_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n
     ba.sAll = s_all; ba.zT = z_final; ba.hs = hs; ba.n = n; ba.nt = nt; ba.nstage = (stepper == NOCF_RK4) ? 4 : 1;
     ba.t1 = (float)t1;
     ba.a0 = alph[0]; ba.a3 = alph[3]; ba.a4 = alph[4]; ba.a5 = alph[5]; ba.inv_n = (float)inv_n;
-    ba.lam0 = lam0;
+    ba.lam0 = lam0; ba.lamW = states ? lamW : nullptr;
     ba.gpart = gpart; ba.gstride = nocf_small_grad_floats(phi->d, phi->m);
     ba.act = (act_rec && (phi->m % 16) == 0) ? act_rec : nullptr; ba.actRows = (long)nt * ba.nstage * n;
     const size_t ldsBytes = (size_t)mpl.pp.ldsFloats * 4;
     const void* fk = nullptr;
-#define NOCF_MBW_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) fk = reinterpret_cast<const void*>(rollout_mono_bwd_kernel<M_, D_>);
+#define NOCF_MBW_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) fk = states ? reinterpret_cast<const void*>(rollout_mono_bwd_kernel<M_, D_, true>) \
+                                                                                  : reinterpret_cast<const void*>(rollout_mono_bwd_kernel<M_, D_>);
     NOCF_MBW_PICK(8, 1) NOCF_MBW_PICK(6, 1) NOCF_MBW_PICK(4, 1) NOCF_MBW_PICK(8, 2) NOCF_MBW_PICK(6, 2) NOCF_MBW_PICK(4, 2)
 #undef NOCF_MBW_PICK
     if (!fk) return NOCF_E_SHAPE;
@@ -2652,10 +2671,48 @@ int nocf_rollout_bwd_mid_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n
     e = hipLaunchKernel(fk, dim3((unsigned)rows), dim3(256), args, ldsBytes, st);
     if (e) return (int)e;
     if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
-    g_last_kernel = "rollout_mono_bwd_kernel";
+    g_last_kernel = states ? "rollout_mono_bwd_kernel<states>" : "rollout_mono_bwd_kernel";
     g_last_errp = nullptr;
     return (int)hipGetLastError();
 #endif
+}
+
+int nocf_rollout_bwd_mid_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t nt, int32_t stepper, double t1,
+                             const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
+                             const float* act_rec, float* gpart, int64_t gpart_rows, float* lam0, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+    return bwd_mid_impl(phi, prob, n, nt, stepper, t1, alph, inv_n, s_all, z_final, hs, act_rec, gpart, gpart_rows, lam0, nullptr, false,
+                        workspace, workspace_bytes, stream);
+}
+
+// ---- the state-only adjoint (include/nocf.h): lane, then one-CU, then per-tile -- nocf_rollout_record_disturbed_f32's order.  A family says
+// NOCF_E_SHAPE when the shape is not its own; every refusal comes before anything is enqueued
+int nocf_rollout_bwd_states_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t nt, int32_t stepper, double t1,
+                                const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
+                                const float* act_rec, float* lam0, float* lamW,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = check_phi(phi);
+    if (rc) return rc;
+    if (!prob || !alph || !s_all || !z_final || !hs || (!lam0 && !lamW) || !workspace) return NOCF_E_NULL;
+    if (n < 1 || nt < 1) return NOCF_E_SHAPE;
+    if (stepper != NOCF_RK4 && stepper != NOCF_RK1) return NOCF_E_STEPPER;
+    rc = bwd_small_impl(phi, prob, n, nt, stepper, t1, alph, inv_n, s_all, z_final, hs, nullptr, lam0, lamW, true, stream);
+    if (rc != NOCF_E_SHAPE) return rc;
+    rc = bwd_mid_impl(phi, prob, n, nt, stepper, t1, alph, inv_n, s_all, z_final, hs, act_rec, nullptr, 0, lam0, lamW, true,
+                      workspace, workspace_bytes, stream);
+    if (rc != NOCF_E_SHAPE) return rc;
+    return rollout_bwd_impl(phi, prob, n, nt, stepper, t1, alph, inv_n, s_all, z_final, hs, nullptr, nullptr, nullptr, nullptr, nullptr,
+                            nullptr, nullptr, nullptr, nullptr, nullptr, lam0, nullptr, workspace, workspace_bytes, stream, 0, nullptr, nullptr,
+                            true, lamW);
+}
+
+int nocf_disturbance_ascent_f32(float* W, const float* g, const float* mask, int64_t n, int32_t nt, int32_t d,
+                                double step, double eps, void* stream) {
+    if (!W || !g) return NOCF_E_NULL;
+    if (n < 1 || nt < 1 || d < 1 || !(step >= 0.0 && step <= 3.0e38) || !(eps >= 0.0 && eps <= 3.0e38)) return NOCF_E_SHAPE;
+    hipLaunchKernelGGL(disturbance_ascent_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, W, g, mask, (long)n, (int)nt,
+                       (int)d, (float)step, (float)eps);
+    return (int)hipGetLastError();
 }
 
 static int phi_common(const NocfPhi* phi, const float* s, int64_t n, float* grad, float* value,

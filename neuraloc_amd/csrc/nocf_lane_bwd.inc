@@ -7,6 +7,10 @@
 //     gpart[sample] = [dK0 (m x D1) | db0 (m) | dK1 (m x m) | db1 (m) | dw (m) | dc.weight (D1) | dc.bias (1) | dM (D1 x D1)]
 // (dM = d/d(A'A), the host forms dA = A (dM + dM')).  The host sums gpart over the samples (fixed order).
 // 4x the parallelism of the 4-samples-per-wave tile adjoint, no LDS, no barrier, no row streams, no contraction GEMMs.
+//
+// STATES (nocf_rollout_bwd_states_f32): the state-only instantiation.  The lambda recursion (fbar, gbar, XD, XS, XP, LAM) is the same
+// statements; the gradient rows, their FMAs and the gpart store are compiled out, and LAM is written to lamW[k] when the last stage of step
+// k begins -- z_{k+1} = step(z_k) + W[k], so that cotangent is dJ/dW[k] (lamW[nt-1]: the terminal cotangent dJ/dx(T)).
 
 struct LaneBwdArgs {
     DevPhi P;
@@ -17,11 +21,12 @@ struct LaneBwdArgs {
     float t1, a0, a3, a4, a5, inv_n;
     float* gpart; long P_total;
     float* lam0;
+    float* lamW;              // [nt][n][d] (nullable): the state cotangent behind every step, dJ/dW of a disturbed rollout (STATES instantiation)
 };
 
 __device__ __forceinline__ float sgnf(float v) { return (v > 0.f) ? 1.f : (v < 0.f ? -1.f : 0.f); }
 
-template <int MP, int DP>
+template <int MP, int DP, bool STATES = false>
 __global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, DevProb pb) {
     const int lane = threadIdx.x & 63;
     const long sample = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -78,7 +83,10 @@ __global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, D
         const float hs = fin ? 0.f : la.hs[k];
         float wst = 1.f, cpl = 0.f;
         if (la.nstage != 1) { wst = (st == 0 || st == 3) ? c16 : c26; cpl = (st == 3) ? 0.f : (st == 2 ? 1.f : 0.5f); }
-        if (!fin && st == la.nstage - 1) { XS = 0.f; XP = 0.f; }
+        if (!fin && st == la.nstage - 1) {
+            if constexpr (STATES) { if (la.lamW && live && lane < d) la.lamW[((long)k * la.n + sample) * d + lane] = LAM; }
+            XS = 0.f; XP = 0.f;
+        }
         float s;
         if (fin) s = lane < d ? la.zT[row * (d + 4) + lane] : (lane == d ? la.t1 : 0.f);
         else s = lane < D1 ? la.sAll[(ev * la.n + row) * D1 + lane] : 0.f;
@@ -122,6 +130,7 @@ __global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, D
                 gbar = la.inv_n * la.a5 * eg;
             }
             // the value cotangent reuses the forward quantities: ubar = phib a, qbar = phib v, obar = phib y
+            if constexpr (!STATES) {
             const float phib = la.inv_n * la.a4 * ef;
 #pragma unroll
             for (int kk = 0; kk < MP; ++kk) gK1[kk] = fmaf(phib * v, lane_bcast(u0, kk), gK1[kk]);
@@ -134,6 +143,7 @@ __global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, D
             gb1 += phib * v; gb0 += phib * y; gw += phib * u1;
             if (lane < D1) gcw += phib * s;
             gcb += phib;
+            }
         } else {
             // problem physics (Cross2D.py:73-160): sum p^2, obstacle sum, interaction sum and their x-gradients
             const float sp2 = wave_sum(lane < d ? g * g : 0.f);
@@ -203,8 +213,7 @@ __global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, D
             const float gi = lane_bcast(gbar, i), si = lane_bcast(s, i);
             ybar = fmaf(k0row[i], gi, ybar);
             sA = fmaf(symA[i], gi, sA);
-            gK0[i] = fmaf(y, gi, gK0[i]);
-            gM[i] = fmaf(gbar, si, gM[i]);
+            if constexpr (!STATES) { gK0[i] = fmaf(y, gi, gK0[i]); gM[i] = fmaf(gbar, si, gM[i]); } else (void)si;
         }
         const float abar = th0 * ybar, tau0bar = a * ybar;
         float vbar = 0.f;
@@ -212,23 +221,27 @@ __global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, D
         for (int kk = 0; kk < MP; ++kk) {
             const float ak = lane_bcast(abar, kk);
             vbar = fmaf(k1row[kk], ak, vbar);
-            gK1[kk] = fmaf(v, ak, gK1[kk]);
+            if constexpr (!STATES) gK1[kk] = fmaf(v, ak, gK1[kk]);
         }
         const float qbar = (1.f - th1 * th1) * wv * vbar;
-        gw += abar + th1 * vbar;
+        if constexpr (!STATES) gw += abar + th1 * vbar;
         float u0bar = 0.f;
 #pragma unroll
         for (int j = 0; j < MP; ++j) u0bar = fmaf(k1col[j], lane_bcast(qbar, j), u0bar);
+        if constexpr (!STATES) {
 #pragma unroll
-        for (int kk = 0; kk < MP; ++kk) gK1[kk] = fmaf(qbar, lane_bcast(u0, kk), gK1[kk]);
+            for (int kk = 0; kk < MP; ++kk) gK1[kk] = fmaf(qbar, lane_bcast(u0, kk), gK1[kk]);
+        }
         const float obar = th0 * u0bar + (1.f - th0 * th0) * tau0bar;
         float sbar = sA;
 #pragma unroll
         for (int kk = 0; kk < MP; ++kk) sbar = fmaf(k0col[kk], lane_bcast(obar, kk), sbar);
+        if constexpr (!STATES) {
 #pragma unroll
-        for (int i = 0; i < DP; ++i) gK0[i] = fmaf(obar, lane_bcast(s, i), gK0[i]);
-        gb0 += obar; gb1 += qbar;
-        if (lane < D1) gcw += gbar;
+            for (int i = 0; i < DP; ++i) gK0[i] = fmaf(obar, lane_bcast(s, i), gK0[i]);
+            gb0 += obar; gb1 += qbar;
+            if (lane < D1) gcw += gbar;
+        }
 
         const float xb = (lane < d) ? sbar + XD : 0.f;
         if (fin) LAM += xb;
@@ -239,6 +252,7 @@ __global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, D
     }
 
     if (!live) return;
+    if constexpr (!STATES) {
     float* gp = la.gpart + sample * la.P_total;
     long o = 0;
 #pragma unroll
@@ -259,5 +273,46 @@ __global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, D
     o += 1;
 #pragma unroll
     for (int j = 0; j < DP; ++j) if (lane < D1 && j < D1) gp[o + (long)lane * D1 + j] = gM[j];
+    }
     if (la.lam0 && lane < d) la.lam0[sample * d + lane] = LAM;
+}
+
+// One projected-ascent step of the worst-case search (nocf_disturbance_ascent_f32), one wavefront per row i over its [nt, d] path of
+// W / g [nt][n][d]:  W_i += step (mask o g_i) / ||mask o g_i||  (row untouched when that norm is 0 or not finite: no step, no projection),
+// then W_i *= eps / ||W_i|| when ||W_i|| > eps.  Masked components take no step (left bit for bit); the projection scales the whole row.
+// Both norms: every lane sums its elements e = lane, lane + 64, ... in that order, sum64 adds the lanes in a fixed order -- no atomics,
+// identical inputs give identical bits.  A lane re-reads only elements it wrote itself.
+__global__ void __launch_bounds__(256) disturbance_ascent_kernel(float* __restrict__ W, const float* __restrict__ g, const float* __restrict__ mask,
+                                                                 long n, int nt, int d, float step, float eps) {
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;                                            // (wave-uniform: sum64 needs every lane of the wave)
+    const int L = nt * d;
+    float s = 0.f;
+    for (int e = lane; e < L; e += 64) {
+        const int k = e / d, i = e - k * d;
+        float v = g[((long)k * n + row) * d + i];
+        if (mask) v *= mask[i];
+        s = fmaf(v, v, s);
+    }
+    const float gn = sqrtf(sum64(s));
+    if (!(gn > 0.f) || !(gn <= 3.0e38f)) return;
+    const float sc = step / gn;
+    float q = 0.f;
+    for (int e = lane; e < L; e += 64) {
+        const int k = e / d, i = e - k * d;
+        const long o = ((long)k * n + row) * d + i;
+        float w = W[o];
+        const float mk = mask ? mask[i] : 1.f;
+        if (mk != 0.f) { w = fmaf(sc, mk * g[o], w); W[o] = w; }
+        q = fmaf(w, w, q);
+    }
+    const float wn = sqrtf(sum64(q));
+    if (!(wn > eps)) return;
+    const float f = eps / wn;
+    for (int e = lane; e < L; e += 64) {
+        const int k = e / d, i = e - k * d;
+        const long o = ((long)k * n + row) * d + i;
+        W[o] *= f;
+    }
 }

@@ -412,7 +412,7 @@ class _OCflowTrainDisturbed(torch.autograd.Function):
     never the split-role kernel and never with a tape -- and saves what _OCflowTrain's saves: the stage inputs, recorded at the displaced
     states, and the displaced z(T).  W does not depend on the parameters, so the adjoint of the disturbed scheme is the adjoint of the
     undisturbed one at those inputs: the backward is _OCflowTrain's, unchanged, and picks the small, mid or row-stream adjoint as it does
-    there.  dJ/dW is not returned."""
+    there.  dJ/dW is not returned here: adversary.disturbance_gradient forms it (nocf_rollout_bwd_states_f32)."""
 
     @staticmethod
     def forward(ctx, x, net, prob, tspan, nt, stepper, alph, n_total, group, W, *params):
@@ -596,7 +596,7 @@ def disturbed_ocflow_train(x, net, prob, tspan, nt, W, stepper="rk4", alph=None,
         z = [x, 0, 0, 0, 0];  for k in 0 .. nt-1:  z = step(z, tk, tk + h);  z[:, :d] += W[k];  tk += h;   terminal terms at the displaced z(T)
     (disturb.disturbed_rollout's), with Jc differentiable w.r.t. every parameter of `net` and w.r.t. x when x requires a gradient.
     :param W:   nt-by-nex-by-d float32 tensor on x's device (brownian_disturbances); not modified, and not differentiated: dJ/dW is not
-                returned, so a W that requires a gradient is refused
+                returned, so a W that requires a gradient is refused (neuraloc_amd.disturbance_gradient returns dJ/dW)
     :param alph: 6 multipliers (default: net.alph);  n_total, group: as for ocflow_train (each rank passes its own shard's W)
     Single precision only.  Every check below raises before a device is touched."""
     alph = list(net.alph if alph is None else alph)
