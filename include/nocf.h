@@ -124,6 +124,14 @@ int nocf_set_knob(const char* name, int32_t value, int32_t clear);
  * shape-specialised instantiation (2: one taken by the recording forward and the adjoint only), else 0 }.  bwd != 0: the adjoint's plan.
  * Returns 0 or the code the rollout would return (NOCF_E_SHAPE, NOCF_E_LDS: out[9] is still set, the rest 0).  Makes no GPU call. */
 int nocf_debug_tile_plan(int32_t d, int32_t m, int32_t nTh, int32_t r, int32_t n_agents, int32_t bwd, int32_t out[12]);
+/* The instantiation the double-precision kernels would run a shape with.  which: 0 nocf_rollout_f64 / nocf_rollout_record_f64, 1
+ * nocf_rollout_bwd_f64 (under the NOCF_F64_BWD_T knob in force), 2 nocf_phi_f64 (n_agents is not used).  out = { T (samples per workgroup),
+ * wide (m > 256), LDS doubles per workgroup, the form of the m x (d+1), m x m and (d+1) x m products (0 plain loop, 1 register-tiled two
+ * rows per thread, 2 register-tiled one row per thread, 3 matrix pipe), matrix pipe: row groups per wave and passes at M = m, the same at
+ * M = d+1 (0 otherwise), register-tiled two-row form: 512-row trips at M = m and at M = d+1 (0 otherwise) }.  Returns 0 or the code the
+ * entry would return for these shapes (NOCF_E_SHAPE, NOCF_E_LDS: out is all 0).  Makes no GPU call.  Libraries older than this entry
+ * lack the symbol: probe for it. */
+int nocf_debug_f64_plan(int32_t d, int32_t m, int32_t nTh, int32_t r, int32_t n_agents, int64_t n, int32_t which, int32_t out[12]);
 
 /* bytes of scratch `workspace` a call with these shapes needs (packed weight images) */
 size_t nocf_workspace_bytes(int32_t d, int32_t m, int32_t nTh);

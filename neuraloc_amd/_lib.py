@@ -385,6 +385,9 @@ def _bind(L):
     L.nocf_debug_reload_env.restype = None
     L.nocf_debug_tile_plan.restype = C.c_int
     L.nocf_debug_tile_plan.argtypes = [C.c_int32] * 6 + [C.POINTER(C.c_int32)]
+    if hasattr(L, "nocf_debug_f64_plan"):
+        L.nocf_debug_f64_plan.restype = C.c_int
+        L.nocf_debug_f64_plan.argtypes = [C.c_int32] * 5 + [C.c_int64, C.c_int32, C.POINTER(C.c_int32)]
     L.nocf_last_rollout_status_async.restype = C.c_int
     L.nocf_last_rollout_status_async.argtypes = [C.c_void_p, C.c_void_p]
     L.nocf_debug_set_stamp_buffer.restype = C.c_int

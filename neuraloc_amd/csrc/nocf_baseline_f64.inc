@@ -5,9 +5,8 @@
 // x-gradients, a suffix sum per coordinate for the adjoint, torch's _single_tensor_adam step with the bias corrections in double.
 // The physics is the double-precision device code of the rollout kernels, called as it stands: f64_obstacle / f64_gauss2
 // (nocf_f64.inc) for the obstacle values, f64_xgrad (nocf_f64_bwd.inc) for d(alphQ Q + alphW W)/dz; the pair sum and calcLHQW's
-// scalars are f64_physics' statements (they are not a function there).  f64_xgrad leaves out one term the baseline needs -- the
-// soft corridor's gradient in eval mode (its cost is the same in both modes; the rollout's adjoint only runs in train mode) -- which
-// bl64_soft_eval_grad adds from f64_gauss2.
+// scalars are f64_physics' statements (they are not a function there).  f64_xgrad covers both modes: the soft corridor's Gaussians
+// have the same gradient in train and eval mode, the hard corridor and the blocks are masks without a gradient in eval mode.
 //
 // LDS (doubles): U, Z [nt+1][d], XD [nt][d], three partial sums per thread, three cost rows [nt], 8 scalars.  The Adam moments are NOT
 // in LDS: an element is always touched by the same thread, once per iteration, so they live in that thread's registers (256-thread
@@ -60,25 +59,6 @@ __device__ __forceinline__ void bl64_forward(double* L, const Base64Lay& ly, int
     }
 }
 
-// the soft corridor's d(alphQ Q)/dz in eval mode, times cf, ADDED to xd for this lane's agents (f64_xgrad wrote xd just before, the same
-// lane the same entries): the four Gaussians of f64_obstacle differentiated, as f64_xgrad does it in train mode
-__device__ __forceinline__ void bl64_soft_eval_grad(const F64Prob& pb, const double* x, double* xd, double cf, int j0, int Gsz) {
-    const double two_pi = 6.283185307179586;
-    const double cov = 0.2, denom = two_pi * sqrt(cov * cov);
-    const double mus[4] = {-2.5, 2.5, -1.5, 1.5};
-    for (int a = j0; a < pb.nAgents; a += Gsz) {
-        const double x0 = x[2 * a], x1 = x[2 * a + 1];
-        double g0 = 0.0, g1 = 0.0;
-        for (int k = 0; k < 4; ++k) {
-            const double pdf = f64_gauss2(x0, x1, mus[k], 0.0, cov, denom);
-            g0 -= pdf * (x0 - mus[k]) / cov;
-            g1 -= pdf * x1 / cov;
-        }
-        xd[2 * a] += cf * (pb.alphQ * g0);
-        xd[2 * a + 1] += cf * (pb.alphQ * g1);
-    }
-}
-
 // Partial sums of L(z_{i + shift}, U_i) for all steps: lanes [i G, (i+1) G) take step i and leave sum U_i^2, the raw obstacle sum and the
 // raw interaction sum of their share in P[0 / 1 / 2][tid].  grad: also XD[i] = h d(alphQ Q + alphW W)/dz at z_{i+shift}.
 __device__ void bl64_costs(double* L, const F64Prob& pb, const Base64Lay& ly, int d, int nt, int G, int shift, bool grad, double h) {
@@ -116,7 +96,6 @@ __device__ void bl64_costs(double* L, const F64Prob& pb, const Base64Lay& ly, in
         if (grad) {
             double* xd = L + ly.oXD + i * d;
             f64_xgrad(pb, x, xd, h, j0, G);
-            if (!pb.training && pb.kind == NOCF_PROB_CROSS2D && pb.obstacle == NOCF_OBS_SOFTCORRIDOR) bl64_soft_eval_grad(pb, x, xd, h, j0, G);
         }
     }
     L[ly.oP + tid] = sp;

@@ -44,7 +44,8 @@ static int make_f64_bwd_plan(int d, int m, int nTh, int r, int nAgents, int T, F
     return ((size_t)l * 8 <= 160u * 1024u) ? 0 : NOCF_E_LDS;
 }
 
-// d(alphQ Q + alphW W)/dx of the point-agent problems for the thread group's sample, times cf, into XD[0..d); train-mode masks are constants
+// d(alphQ Q + alphW W)/dx of the point-agent problems for the thread group's sample, times cf, into XD[0..d); train-mode masks are constants;
+// eval mode: the hard corridor and the blocks are masks without a gradient, the soft corridor's Gaussians are the train-mode ones
 // (nocf_bwd.inc physics_xgrad restated in double: Cross2D.py:89-160, SwarmTraj.py:89-162)
 __device__ __forceinline__ void f64_xgrad(const F64Prob& pb, const double* x, double* xd, double cf, int j0, int Gsz) {
     const int N = pb.nAgents, ad = pb.agentDim;
@@ -54,7 +55,7 @@ __device__ __forceinline__ void f64_xgrad(const F64Prob& pb, const double* x, do
     const double two_pi = 6.283185307179586;
     for (int a = j0; a < N; a += Gsz) {
         double gq[3] = {0.0, 0.0, 0.0}, gw[3] = {0.0, 0.0, 0.0};
-        if (pb.training && pb.obstacle != NOCF_OBS_NONE) {
+        if ((pb.training && pb.obstacle != NOCF_OBS_NONE) || pb.obstacle == NOCF_OBS_SOFTCORRIDOR) {
             if (pb.kind == NOCF_PROB_CROSS2D) {
                 const double x0 = x[2 * a], x1 = x[2 * a + 1];
                 if (pb.obstacle == NOCF_OBS_SOFTCORRIDOR) {

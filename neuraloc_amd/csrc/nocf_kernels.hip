@@ -3060,6 +3060,56 @@ size_t nocf_workspace_bytes_f64(int32_t d, int32_t m, int32_t nTh) {
     return f64_ws_doubles(d, m, nTh) * sizeof(double);
 }
 
+// samples per workgroup of the three double-precision entries (nocf_debug_f64_plan reports the same choices): the plan, or 0 when no T fits the LDS
+// rollout: 4 when the batch still fills the chip that way, fewer for small batches or tight LDS
+static int f64_rollout_plan(int d, int m, int nTh, int r, int nAgents, int64_t n, F64Plan* pl) {
+    const int pref[3] = {n >= 1024 ? 4 : (n >= 512 ? 2 : 1), 2, 1};
+    for (int q = 0; q < 3; ++q)
+        if ((q == 0 || pref[q] < pref[0]) && make_f64_plan(d, m, nTh, r, nAgents, pref[q], pl) == 0) return pref[q];
+    return 0;
+}
+// adjoint: the largest T the LDS takes (wide networks: the register-tiled products run at 2 or 1); NOCF_F64_BWD_T (diagnostic) caps it
+static int f64_bwd_plan(int d, int m, int nTh, int r, int nAgents, F64BwdPlan* bp) {
+    const bool wide = m > 256;
+    const int tpref = env_int("NOCF_F64_BWD_T", 0);
+    for (int cand : {4, 2, 1}) {
+        if (wide && cand == 4) continue;
+        if (tpref && cand > tpref) continue;
+        if (make_f64_bwd_plan(d, m, nTh, r, nAgents, cand, bp) == 0) return cand;
+    }
+    return 0;
+}
+// Phi / grad Phi of n points: the rollout's rule without a problem's scratch
+static int f64_phi_plan(int d, int m, int nTh, int r, int64_t n, F64Plan* pl) { return f64_rollout_plan(d, m, nTh, r, 1, n, pl); }
+
+// the form f64_rows<T, WIDE> takes for an M x K product: 0 plain loop, 1 f64_gemm<., 2>, 2 f64_gemm<., 1>, 3 matrix pipe
+static int f64_rows_form(int T, bool wide, int M, int K) {
+    if (wide && T == 4) return 3;
+    if (wide && M > 256) return 1;
+    if (wide && K > 256) return 2;
+    return 0;
+}
+
+int nocf_debug_f64_plan(int32_t d, int32_t m, int32_t nTh, int32_t r, int32_t n_agents, int64_t n, int32_t which, int32_t out[12]) {
+    if (!out) return NOCF_E_NULL;
+    for (int i = 0; i < 12; ++i) out[i] = 0;
+    if (which < 0 || which > 2) return NOCF_E_SHAPE;
+    if (n < 1 || d < 1 || m < 1 || nTh < 2 || r < 1 || r > 16) return NOCF_E_SHAPE;
+    int T = 0, lds = 0;
+    if (which == 1) { F64BwdPlan bp{}; T = f64_bwd_plan(d, m, nTh, r, n_agents, &bp); lds = bp.ldsDoubles; }
+    else { F64Plan pl{}; T = which == 0 ? f64_rollout_plan(d, m, nTh, r, n_agents, n, &pl) : f64_phi_plan(d, m, nTh, r, n, &pl); lds = pl.ldsDoubles; }
+    if (!T) return NOCF_E_LDS;
+    const bool wide = m > 256;
+    const int D1 = d + 1;
+    const int f0 = f64_rows_form(T, wide, m, D1), f1 = f64_rows_form(T, wide, m, m), f2 = f64_rows_form(T, wide, D1, m);
+    auto passes = [](int M) { const int ng = (M + 15) / 16; return (ng + 4 * f64_img_rg(M) - 1) / (4 * f64_img_rg(M)); };
+    const bool pipe = f1 == 3;
+    const int v[12] = {T, wide ? 1 : 0, lds, f0, f1, f2, pipe ? f64_img_rg(m) : 0, pipe ? passes(m) : 0, pipe ? f64_img_rg(D1) : 0, pipe ? passes(D1) : 0,
+                       f1 == 1 ? (m + 511) / 512 : 0, f2 == 1 ? (D1 + 511) / 512 : 0};
+    for (int i = 0; i < 12; ++i) out[i] = v[i];
+    return 0;
+}
+
 static int rollout_f64_impl(const NocfPhi64* phi, const NocfProb64* prob, const double* x, int64_t n,
                             double t0, double t1, int32_t nt, int32_t stepper, const double* alph,
                             double* z_out, double* persample, double* cost_sums, double* zFull, double* ctrlFull, double* s_all,
@@ -3096,11 +3146,8 @@ static int rollout_f64_impl(const NocfPhi64* phi, const NocfProb64* prob, const 
     if (rc) return rc;
     F64Prob pb{pb32.kind, pb32.obstacle, pb32.nAgents, pb32.training, pb32.agentDim, prob->r, prob->alph_Q, prob->alph_W, prob->mass, prob->grav, prob->xtarget};
     if (workspace_bytes < nocf_workspace_bytes_f64(phi->d, phi->m, phi->nTh)) return NOCF_E_WORKSPACE;
-    // samples per workgroup: 4 when the batch still fills the chip that way, fewer for small batches or tight LDS
     F64Plan pl;
-    int T = 0;
-    const int pref[3] = {n >= 1024 ? 4 : (n >= 512 ? 2 : 1), 2, 1};
-    for (int q = 0; q < 3 && !T; ++q) if ((q == 0 || pref[q] < pref[0]) && make_f64_plan(phi->d, phi->m, phi->nTh, phi->r, pb.nAgents, pref[q], &pl) == 0) T = pref[q];
+    const int T = f64_rollout_plan(phi->d, phi->m, phi->nTh, phi->r, pb.nAgents, n, &pl);
     if (!T) return NOCF_E_LDS;
     hipStream_t st = (hipStream_t)stream;
     double* ws = (double*)workspace;
@@ -3121,7 +3168,7 @@ static int rollout_f64_impl(const NocfPhi64* phi, const NocfProb64* prob, const 
                              : T == 2 ? reinterpret_cast<const void*>(rollout_f64_kernel<2, false>) : reinterpret_cast<const void*>(rollout_f64_kernel<1, false>));
     hipError_t e = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes);
     if (e) return (int)e;
-    if (env_int("NOCF_DEBUG", 0)) fprintf(stderr, "[nocf] f64 kernel: %d sample(s) per workgroup, LDS %zu B\n", T, ldsBytes);
+    if (env_int("NOCF_DEBUG", 0)) fprintf(stderr, "[nocf] f64 kernel: %d sample(s) per workgroup, wide %d, LDS %zu B\n", T, wide ? 1 : 0, ldsBytes);
     const double* wsc = ws;
     void* args[] = {(void*)&pl, (void*)&P, (void*)&pb, (void*)&wsc, (void*)&ra};
     e = hipLaunchKernel(fk, dim3((unsigned)((n + T - 1) / T)), dim3(256), args, ldsBytes, st);
@@ -3152,13 +3199,7 @@ int nocf_rollout_bwd_f64(const NocfPhi64* phi, const NocfProb64* prob, int64_t n
     if (workspace_bytes < nocf_workspace_bytes_f64(phi->d, phi->m, phi->nTh)) return NOCF_E_WORKSPACE;
     const bool wide = phi->m > 256;                            // (the register-tiled products; they run at 2 or 1 samples per workgroup here)
     F64BwdPlan bp;
-    int T = 0;
-    const int tpref = env_int("NOCF_F64_BWD_T", 0);             // (diagnostic: force the samples per workgroup)
-    for (int cand : {4, 2, 1}) {
-        if (wide && cand == 4) continue;
-        if (tpref && cand > tpref) continue;
-        if (make_f64_bwd_plan(phi->d, phi->m, phi->nTh, phi->r, pb.nAgents, cand, &bp) == 0) { T = cand; break; }
-    }
+    const int T = f64_bwd_plan(phi->d, phi->m, phi->nTh, phi->r, pb.nAgents, &bp);
     if (!T) return NOCF_E_LDS;
     hipStream_t st = (hipStream_t)stream;
     double* ws = (double*)workspace;
@@ -3179,7 +3220,7 @@ int nocf_rollout_bwd_f64(const NocfPhi64* phi, const NocfProb64* prob, int64_t n
                              : T == 2 ? reinterpret_cast<const void*>(rollout_bwd_f64_narrow_kernel<2>) : reinterpret_cast<const void*>(rollout_bwd_f64_narrow_kernel<1>));
     hipError_t e = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes);
     if (e) return (int)e;
-    if (env_int("NOCF_DEBUG", 0)) fprintf(stderr, "[nocf] f64 adjoint kernel: %d sample(s) per workgroup, LDS %zu B\n", T, ldsBytes);
+    if (env_int("NOCF_DEBUG", 0)) fprintf(stderr, "[nocf] f64 adjoint kernel: %d sample(s) per workgroup, wide %d, LDS %zu B\n", T, wide ? 1 : 0, ldsBytes);
     const double* wsc = ws;
     void* args[] = {(void*)&bp, (void*)&P, (void*)&pb, (void*)&wsc, (void*)&ba};
     e = hipLaunchKernel(fk, dim3((unsigned)((n + T - 1) / T)), dim3(256), args, ldsBytes, st);
@@ -3196,9 +3237,7 @@ int nocf_phi_f64(const NocfPhi64* phi, const double* s, int64_t n, double* value
     if (n < 1 || phi->d < 1 || phi->m < 1 || phi->nTh < 2 || phi->r < 1 || phi->r > 16) return NOCF_E_SHAPE;
     if (workspace_bytes < nocf_workspace_bytes_f64(phi->d, phi->m, phi->nTh)) return NOCF_E_WORKSPACE;
     F64Plan pl;
-    int T = 0;
-    const int pref[3] = {n >= 1024 ? 4 : (n >= 512 ? 2 : 1), 2, 1};
-    for (int q = 0; q < 3 && !T; ++q) if ((q == 0 || pref[q] < pref[0]) && make_f64_plan(phi->d, phi->m, phi->nTh, phi->r, 1, pref[q], &pl) == 0) T = pref[q];
+    const int T = f64_phi_plan(phi->d, phi->m, phi->nTh, phi->r, n, &pl);
     if (!T) return NOCF_E_LDS;
     hipStream_t st = (hipStream_t)stream;
     double* ws = (double*)workspace;
@@ -3212,6 +3251,7 @@ int nocf_phi_f64(const NocfPhi64* phi, const double* s, int64_t n, double* value
                              : T == 2 ? reinterpret_cast<const void*>(phi_f64_kernel<2, false>) : reinterpret_cast<const void*>(phi_f64_kernel<1, false>));
     hipError_t e = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes);
     if (e) return (int)e;
+    if (env_int("NOCF_DEBUG", 0)) fprintf(stderr, "[nocf] f64 phi kernel: %d sample(s) per workgroup, wide %d, LDS %zu B\n", T, wide ? 1 : 0, ldsBytes);
     const double* wsc = ws;
     long nn = (long)n;
     void* args[] = {(void*)&pl, (void*)&P, (void*)&wsc, (void*)&s, (void*)&nn, (void*)&value, (void*)&grad};
