@@ -42,6 +42,9 @@ p.add_argument("--noise", type=float, default=None, metavar="SIGMA",
                help="(addition) roll xInit out under Brownian state disturbances sigma dB at every step (neuraloc_amd.noise_study)")
 p.add_argument("--noise_paths", type=int, default=256, metavar="R", help="(addition) noise realisations per start for --noise")
 p.add_argument("--noise_seed", type=int, default=0, metavar="S", help="(addition) seed of the disturbances for --noise")
+p.add_argument("--noise_rng", type=str, default="torch", choices=["torch", "counter"],
+               help="(addition) torch: the disturbances are drawn with torch.randn; counter: inside the kernels from (seed, row, step, "
+                    "component) (neuraloc_amd.noisy_rollout): no tensor, and the figures do not depend on the chunking")
 p.add_argument("--worst", type=float, default=None, metavar="EPS",
                help="(addition) search the per-step state disturbances of path norm <= EPS that hurt xInit's L + G most (neuraloc_amd.worst_case_disturbances)")
 p.add_argument("--worst_steps", type=int, default=20, metavar="K", help="(addition) projected ascent steps for --worst")
@@ -53,6 +56,10 @@ def main(argv=None):
     prec = torch.float64 if args.prec == "double" else torch.float32          # evalOC.py:28-31
     if args.noise is not None and prec != torch.float32:                     # refused before anything runs or is written
         raise SystemExit("--noise runs in single precision only (the double-precision rollout takes no disturbance)")
+    if args.noise_rng == "counter" and prec != torch.float32:
+        raise SystemExit("--noise_rng counter runs in single precision only (the double-precision rollout takes no disturbance)")
+    if args.noise_rng == "counter" and not 0 <= args.noise_seed < 2 ** 64:
+        raise SystemExit("--noise_rng counter needs 0 <= --noise_seed < 2**64")
     if args.worst is not None and prec != torch.float32:
         raise SystemExit("--worst runs in single precision only (the double-precision rollout takes no disturbance)")
     os.makedirs(os.path.join(args.save, "figs"), exist_ok=True)
@@ -117,8 +124,11 @@ def main(argv=None):
                 print("%s at t=0.1: nShock=%d, final state error %.4e" %
                       (tag, res["nShock"], float((res["traj"][0, :, -1] - prob.xtarget.reshape(-1)).norm())))
         if args.noise is not None:
-            gen = torch.Generator(device=xInit.device).manual_seed(args.noise_seed)
-            st = na.noise_study(xInit, net, prob, nt, args.noise, args.noise_paths, alph=alph, generator=gen)
+            if args.noise_rng == "counter":
+                st = na.noise_study(xInit, net, prob, nt, args.noise, args.noise_paths, alph=alph, rng="counter", seed=args.noise_seed)
+            else:
+                gen = torch.Generator(device=xInit.device).manual_seed(args.noise_seed)
+                st = na.noise_study(xInit, net, prob, nt, args.noise, args.noise_paths, alph=alph, generator=gen)
             print("noise sigma=%g, %d paths, seed %d: %-4s %11s %11s %11s %11s %11s" %
                   (args.noise, args.noise_paths, args.noise_seed, "", "mean", "std", "5%", "50%", "95%"))
             keys = ("mean", "std", "q05", "q50", "q95")

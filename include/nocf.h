@@ -222,6 +222,46 @@ int nocf_rollout_record_disturbed_f32(const NocfPhi* phi, const NocfProb* prob, 
                                       void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Brownian disturbances from a counter-based generator: the disturbance of (row, step k, component i) is a pure function
+ *     w(seed, row, k, i) = fl32(scale[i] * g),   g = sqrtf(-2 logf(u1)) cospif(2 u2),   u = ((word >> 9) + 0.5) 2^-23 of words 0 and 1 of
+ *     Philox4x32-10 with counter (row & 0xffffffff, row >> 32, k, i) and key (seed & 0xffffffff, seed >> 32)
+ * (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85; words 2 and 3 are not used; |g| <= 5.77).  `row` is the
+ * GLOBAL row: row0 + the row of this call.  A row meets the same disturbances alone, in any batch, on any device and in any chunk, and a
+ * prefix in nt stays a prefix.  scale device [d], float32: sigma_i sqrt(h) with h = (t1 - t0) / nt, 0 for components that are not
+ * disturbed.  The product is rounded to float32 on its own and then added to the state.
+ *
+ * nocf_noise_fill_f32 writes W[k][row][i] = w(seed, row0 + row, k, i), W device [nt, n, d], time-major, contiguous: the tensor that
+ * nocf_rollout_disturbed_f32 takes.  Only rows < n and d floats per row are written.
+ * W == NULL or scale == NULL: NOCF_E_NULL; n, nt or d < 1, or row0 < 0: NOCF_E_SHAPE.  Every refusal returns before anything is enqueued.
+ */
+int nocf_noise_fill_f32(float* W, int64_t n, int32_t nt, int32_t d, const float* scale, uint64_t seed, int64_t row0, void* stream);
+
+/*
+ * nocf_rollout_disturbed_f32 with the disturbances drawn inside the kernels: no W exists.  Same contract, dispatch, outputs and refusals;
+ * the outputs equal, bit for bit, those of nocf_rollout_disturbed_f32 on the W that nocf_noise_fill_f32 writes for (scale, seed, row0).
+ * nocf_last_rollout_kernel() reports "rollout_lane_kernel<noise>", "rollout_mono_kernel<noise>", "rollout_kernel<generic, noise>" or
+ * "rollout_kernel<shape-specialised, noise>".  scale == NULL: NOCF_E_NULL; row0 < 0: NOCF_E_SHAPE.
+ */
+int nocf_rollout_noisy_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, const float* scale, uint64_t seed, int64_t row0,
+                           int64_t n, double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                           float* z_out, float* persample, float* cost_sums, float* cost_means, float* zFull, float* ctrlFull,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * nocf_rollout_record_disturbed_f32 with the disturbances drawn inside the kernels: the recording forward of training under counter-based
+ * noise.  s_all, z_out, persample and the activation record equal those of nocf_rollout_record_disturbed_f32 on the filled W bit for bit,
+ * and go to the same adjoints.  scale == NULL, s_all == NULL or z_out == NULL: NOCF_E_NULL; row0 < 0: NOCF_E_SHAPE.
+ */
+int nocf_rollout_record_noisy_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, const float* scale, uint64_t seed, int64_t row0,
+                                  int64_t n, double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                  float* z_out, float* persample, float* cost_sums, float* s_all, float* act_rec, int32_t* recorded,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* host only: the four Philox words of (seed, row, k, i) as the kernels form them (no device is touched).  out == NULL: NOCF_E_NULL;
+ * row, k or i < 0: NOCF_E_SHAPE. */
+int nocf_debug_noise_words(uint64_t seed, int64_t row, int32_t k, int32_t i, uint32_t out[4]);
+
+/*
  * Several rollouts that differ only in their start time and step count, in ONE launch (round 5): the second segments of a shock sweep.
  * The reference's shocked rollout (src/plotter.py:815-824, driven by evalOC.py:113-122) is OCflow on [0, t_s] with int(t_s nt) steps, the
  * shock added to the end state, and OCflow on [t_s, 1] with 1 + nt - int(t_s nt) steps; a sweep over shock times (BASELINE config 5) repeats

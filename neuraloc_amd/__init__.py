@@ -12,6 +12,7 @@ from .baseline_quad import quad_baseline_loss, quad_baseline_report, quad_initia
 from .disturb import disturbed_rollout, brownian_disturbances, noise_study
 from .train import disturbed_ocflow_train
 from .adversary import disturbance_gradient, worst_case_disturbances
+from .noise import counter_disturbances, noisy_rollout, noisy_ocflow_train
 
 __all__ = ["Phi", "ResNN", "antiderivTanh", "derivTanh", "OCflow", "ocG", "Cross2D", "SwarmTraj",
            "Quadcopter", "initProb", "resample", "OCflow_sharded", "shard_rows", "reduce_cost_sums", "check_errors",

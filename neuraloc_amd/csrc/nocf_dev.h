@@ -168,4 +168,7 @@ struct RollArgs {
     // per-step state disturbances (include/nocf.h, nocf_rollout_disturbed_f32): W [nt][n][d], time-major; after step k the state rows take
     // z[:, :d] += W[k].  Read only by the DIST instantiations of the lane / one-CU / per-tile kernels; null everywhere else.
     const float* dist;
+    // the same disturbances drawn inside the kernels (include/nocf.h, nocf_rollout_noisy_f32; nocf_noise.inc): entry (k, row, i) is
+    // noise_value(nzScale[i], nzSeed, nzRow0 + row, k, i).  Read only by the DIST == 2 instantiations; dist is null there.
+    const float* nzScale; unsigned long long nzSeed; long nzRow0;
 };

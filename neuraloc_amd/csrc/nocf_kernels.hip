@@ -29,6 +29,7 @@
 #include "nocf.h"
 
 #include "nocf_dev.h"
+#include "nocf_noise.inc"
 #ifndef NOCF_JIT_ONLY
 #include "nocf_duo.h"
 #endif
@@ -1003,7 +1004,7 @@ __device__ void ctrl_write(const Ctx& c, const DevPlan& pl, const DevProb& pb, f
 // registers held across phi_eval turned 3 spilled registers into 59 on swarm50's instantiation.  The sweep is followed by the physics phase, and
 // one exposed load per step is small beside the step's four evaluations.  With ra.sAll set (disturbed training) the record at the top of an
 // evaluation reads SB, which every write-back path below leaves displaced.
-template <int S, bool DIST = false>
+template <int S, int DIST = 0>
 __device__ __forceinline__ void rollout_body(const DevPlan& pl, const DevPlan* __restrict__ plp, const DevProb& pb,
                                              const float* __restrict__ ws, const RollArgs& ra) {
     Ctx c;
@@ -1054,7 +1055,13 @@ __device__ __forceinline__ void rollout_body(const DevPlan& pl, const DevPlan* _
     const bool quad = (pb.kind == NOCF_PROB_QUADCOPTER);
     // disturbance of item j of step k's write-back sweep: point agents sweep the T*d state components (the tile's rows of W[k] are one
     // contiguous run), quadcopters the T*(d+4) components of z
+    // DIST == 2: the entry is drawn here (nocf_noise.inc) instead of loaded -- in the sweep for the same reason, the generator's registers die with it
     auto dist_at = [&](int k, int j) -> float {
+        if constexpr (DIST == 2) {
+            const int dd = quad ? d + 4 : d;
+            const int t = j / dd, i = j - t * dd;
+            return (j < T * dd && i < d && row0 + t < ra.n) ? noise_value(ra.nzScale[i], ra.nzSeed, ra.nzRow0 + row0 + t, k, i) : 0.f;
+        }
         if (!quad) return (j < T * d && (row0 * d + j) < ra.n * d) ? ra.dist[((long)k * ra.n + row0) * d + j] : 0.f;
         const int t = j / (d + 4), i = j - t * (d + 4);
         return (j < T * (d + 4) && i < d && row0 + t < ra.n) ? ra.dist[((long)k * ra.n + row0 + t) * d + i] : 0.f;
@@ -1309,7 +1316,7 @@ __device__ __forceinline__ void rollout_body(const DevPlan& pl, const DevPlan* _
 
 // DynPlan: the plan is the record in the workspace (fields are scalar loads, not 60 pinned SGPRs).
 // FixedPlan<...>: the plan is a compile-time constant of that shape.
-template <int S, class SP, bool DIST = false>
+template <int S, class SP, int DIST = 0>
 __global__ void __launch_bounds__(NOCF_MAXTHREADS) rollout_kernel(const DevPlan* __restrict__ plp, DevProb pb, const float* __restrict__ ws, RollArgs ra) {
     if constexpr (SP::fixed) {
         constexpr DevPlan plc = SP::make();
@@ -2005,13 +2012,19 @@ static unsigned* lane_ticket(hipStream_t st) {
     return b + it->second;
 }
 
+struct NoiseSpec { const float* scale; unsigned long long seed; long long row0; };       // nocf_rollout_noisy_f32: mode 2 of rollout_impl
+
 static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n,
                         double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
                         float* z_out, float* persample, float* cost_sums, float* zFull, float* ctrlFull,
                         void* workspace, size_t workspace_bytes, void* stream, float* s_all,
                         float* act = nullptr, int32_t* act_recorded = nullptr, float* tapeU1 = nullptr, float* tapeSc = nullptr,
-                        const SegTab* seg = nullptr, float* cost_means = nullptr, const float* dist = nullptr) {
+                        const SegTab* seg = nullptr, float* cost_means = nullptr, const float* distW = nullptr, const NoiseSpec* noise = nullptr) {
     if (act_recorded) *act_recorded = 0;
+    // disturbance mode of this call: 0 none, 1 W from memory (distW), 2 drawn inside the kernels (noise).  `dist` below: either of the two,
+    // they share every rule and the dispatch
+    const int dmode = noise ? 2 : (distW ? 1 : 0);
+    const bool dist = dmode != 0;
     int rc = check_phi(phi);
     if (rc) return rc;
     if (!x || !alph || !workspace) return NOCF_E_NULL;
@@ -2048,7 +2061,8 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
     if (seg) ra.seg = *seg;                       // (several time segments in one launch: the one-CU kernel only, NOCF_E_SHAPE otherwise)
     ra.act = nullptr; ra.actRows = 0;             // (only the split-role kernel records activations: set below)
     ra.tapeU1 = nullptr; ra.tapeSc = nullptr;
-    ra.dist = dist;                               // (disturbed rollouts: lane, then one-CU, then per-tile; never the split-role kernel)
+    ra.dist = distW;                              // (disturbed rollouts: lane, then one-CU, then per-tile; never the split-role kernel)
+    ra.nzScale = noise ? noise->scale : nullptr; ra.nzSeed = noise ? noise->seed : 0ull; ra.nzRow0 = noise ? (long)noise->row0 : 0l;
     hipError_t e;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     const unsigned* errp = nullptr;
@@ -2079,8 +2093,10 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
             (void)hipEventRecord(ev0, st);
         }
         const size_t laneLds = ticket ? (size_t)(256 * 7 * 8 + 16) : 0;      // (the last-workgroup reduction's scratch: only with a ticket)
-#define NOCF_LANE_LAUNCH(MPV, DPV) do { if (dist && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, true>), dim3(grid), dim3(256), 0, st, la, pb, ra); \
-                                         else if (dist) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, true>), dim3(grid), dim3(256), 0, st, la, pb, ra); \
+#define NOCF_LANE_LAUNCH(MPV, DPV) do { if (dmode == 2 && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 2>), dim3(grid), dim3(256), 0, st, la, pb, ra); \
+                                         else if (dmode == 2) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 2>), dim3(grid), dim3(256), 0, st, la, pb, ra); \
+                                         else if (dist && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 1>), dim3(grid), dim3(256), 0, st, la, pb, ra); \
+                                         else if (dist) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 1>), dim3(grid), dim3(256), 0, st, la, pb, ra); \
                                          else if (s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true>), dim3(grid), dim3(256), 0, st, la, pb, ra); \
                                          else if (ticket) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, true>), dim3(grid), dim3(256), laneLds, st, la, pb, ra); \
                                          else hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false>), dim3(grid), dim3(256), 0, st, la, pb, ra); } while (0)
@@ -2089,7 +2105,7 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
 #undef NOCF_LANE_LAUNCH
         e = hipGetLastError();
         if (e) return (int)e;
-        g_last_kernel = dist ? "rollout_lane_kernel<dist>" : "rollout_lane_kernel";
+        g_last_kernel = dmode == 2 ? "rollout_lane_kernel<noise>" : dist ? "rollout_lane_kernel<dist>" : "rollout_lane_kernel";
         if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
         if (cost_sums && !ticket) {
             hipLaunchKernelGGL(cost_sum_kernel, dim3(1), dim3(256), 0, st, persample, (long)n, cost_sums, errp, mean_args);
@@ -2144,7 +2160,7 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
         hipLaunchKernelGGL(mono_pack_kernel, dim3(64), dim3(256), 0, st, mpl, P, ws);
         const size_t ldsBytes = (size_t)mpl.pp.ldsFloats * 4;
         const void* fk = nullptr;
-#define NOCF_MONO_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) fk = dist ? (s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, true>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, true>)) : s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false>);
+#define NOCF_MONO_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) fk = dmode == 2 ? (s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, 2>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 2>)) : dist ? (s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, 1>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 1>)) : s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false>);
         MONO_SHAPES(NOCF_MONO_PICK)
 #undef NOCF_MONO_PICK
         e = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes); if (e) return (int)e;
@@ -2161,7 +2177,7 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
         e = hipLaunchKernel(fk, dim3((int)((n + 15) / 16)), dim3(256), args, ldsBytes, st); if (e) return (int)e;
         ra.act = nullptr; ra.actRows = 0;
         if (mono_rec && act_recorded) *act_recorded = 1;
-        g_last_kernel = dist ? "rollout_mono_kernel<dist>" : "rollout_mono_kernel";
+        g_last_kernel = dmode == 2 ? "rollout_mono_kernel<noise>" : dist ? "rollout_mono_kernel<dist>" : "rollout_mono_kernel";
         e = hipGetLastError();
         if (e) return (int)e;
         if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
@@ -2195,7 +2211,8 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
             // compile-time one bit for bit, so the environment knobs and odd shapes always get the generic kernel
             const void* fk = nullptr;
 #define NOCF_TRY_FIXED(D, M, NTH, R, NAG) \
-            if (!fk && plan_is<FixedPlan<D, M, NTH, R, NAG, 0>>(pl)) fk = dist ? reinterpret_cast<const void*>(rollout_kernel<1, FixedPlan<D, M, NTH, R, NAG, 0>, true>) \
+            if (!fk && plan_is<FixedPlan<D, M, NTH, R, NAG, 0>>(pl)) fk = dmode == 2 ? reinterpret_cast<const void*>(rollout_kernel<1, FixedPlan<D, M, NTH, R, NAG, 0>, 2>) \
+                                                                   : dist ? reinterpret_cast<const void*>(rollout_kernel<1, FixedPlan<D, M, NTH, R, NAG, 0>, 1>) \
                                                                               : reinterpret_cast<const void*>(rollout_kernel<1, FixedPlan<D, M, NTH, R, NAG, 0>>);
             FIXED_SHAPES(NOCF_TRY_FIXED)
             FIXED_SHAPES_EXTRA(NOCF_TRY_FIXED)
@@ -2211,21 +2228,29 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
                 void* args[] = {(void*)&plp, (void*)&pb, (void*)&ws, (void*)&ra};
                 e = hipLaunchKernel(fk, dim3(grid), dim3(block), args, ldsBytes, st); if (e) return (int)e;
                 launched = true;
-                g_last_kernel = dist ? "rollout_kernel<shape-specialised, dist>" : "rollout_kernel<shape-specialised>";
+                g_last_kernel = dmode == 2 ? "rollout_kernel<shape-specialised, noise>" : dist ? "rollout_kernel<shape-specialised, dist>" : "rollout_kernel<shape-specialised>";
                 if (env_int("NOCF_DEBUG", 0)) fprintf(stderr, "[nocf] shape-specialised rollout kernel\n");
             }
         }
-        if (!launched) g_last_kernel = dist ? "rollout_kernel<generic, dist>" : "rollout_kernel<generic>";
+        if (!launched) g_last_kernel = dmode == 2 ? "rollout_kernel<generic, noise>" : dist ? "rollout_kernel<generic, dist>" : "rollout_kernel<generic>";
         if (!launched && env_int("NOCF_DEBUG", 0))
             fprintf(stderr, "[nocf] generic rollout kernel: T %d, %d waves, SK1/SK6/SKm %d/%d/%d, cap %d, LDS %zu B/workgroup\n",
                     pl.T, pl.nwaves, pl.SK1, pl.SK6, pl.SKm, skCap, ldsBytes);
-        if (!launched && dist) switch (pl.T / 4) {
-            case 1: e = set_lds(rollout_kernel<1, DynPlan, true>, ldsBytes); if (e) return (int)e;
-                    hipLaunchKernelGGL((rollout_kernel<1, DynPlan, true>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
-            case 2: e = set_lds(rollout_kernel<2, DynPlan, true>, ldsBytes); if (e) return (int)e;
-                    hipLaunchKernelGGL((rollout_kernel<2, DynPlan, true>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
-            default: e = set_lds(rollout_kernel<4, DynPlan, true>, ldsBytes); if (e) return (int)e;
-                    hipLaunchKernelGGL((rollout_kernel<4, DynPlan, true>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
+        if (!launched && dmode == 2) switch (pl.T / 4) {
+            case 1: e = set_lds(rollout_kernel<1, DynPlan, 2>, ldsBytes); if (e) return (int)e;
+                    hipLaunchKernelGGL((rollout_kernel<1, DynPlan, 2>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
+            case 2: e = set_lds(rollout_kernel<2, DynPlan, 2>, ldsBytes); if (e) return (int)e;
+                    hipLaunchKernelGGL((rollout_kernel<2, DynPlan, 2>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
+            default: e = set_lds(rollout_kernel<4, DynPlan, 2>, ldsBytes); if (e) return (int)e;
+                    hipLaunchKernelGGL((rollout_kernel<4, DynPlan, 2>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
+        }
+        else if (!launched && dist) switch (pl.T / 4) {
+            case 1: e = set_lds(rollout_kernel<1, DynPlan, 1>, ldsBytes); if (e) return (int)e;
+                    hipLaunchKernelGGL((rollout_kernel<1, DynPlan, 1>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
+            case 2: e = set_lds(rollout_kernel<2, DynPlan, 1>, ldsBytes); if (e) return (int)e;
+                    hipLaunchKernelGGL((rollout_kernel<2, DynPlan, 1>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
+            default: e = set_lds(rollout_kernel<4, DynPlan, 1>, ldsBytes); if (e) return (int)e;
+                    hipLaunchKernelGGL((rollout_kernel<4, DynPlan, 1>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
         }
         else if (!launched) switch (pl.T / 4) {
             case 1: e = set_lds(rollout_kernel<1, DynPlan>, ldsBytes); if (e) return (int)e;
@@ -2274,6 +2299,18 @@ int nocf_rollout_disturbed_f32(const NocfPhi* phi, const NocfProb* prob, const f
                         workspace, workspace_bytes, stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, cost_means, W);
 }
 
+int nocf_rollout_noisy_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, const float* scale, uint64_t seed, int64_t row0, int64_t n,
+                           double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                           float* z_out, float* persample, float* cost_sums, float* cost_means, float* zFull, float* ctrlFull,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+    if (!scale) return NOCF_E_NULL;
+    if (row0 < 0) return NOCF_E_SHAPE;
+    if (cost_means && !cost_sums) return NOCF_E_NULL;
+    const NoiseSpec nz{scale, (unsigned long long)seed, (long long)row0};
+    return rollout_impl(phi, prob, x, n, t0, t1, nt, stepper, alph, z_out, persample, cost_sums, zFull, ctrlFull,
+                        workspace, workspace_bytes, stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, cost_means, nullptr, &nz);
+}
+
 int nocf_rollout_segments_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n,
                               int32_t nseg, int64_t rows_per_seg, const double* t0s, double t1, const int32_t* nts, const int32_t* slot0s,
                               int32_t stepper, const float* alph, float* z_out, float* persample, float* cost_sums, float* zFull, float* ctrlFull,
@@ -2312,6 +2349,38 @@ int nocf_rollout_record_disturbed_f32(const NocfPhi* phi, const NocfProb* prob, 
     if (!W || !s_all || !z_out) return NOCF_E_NULL;
     return rollout_impl(phi, prob, x, n, t0, t1, nt, stepper, alph, z_out, persample, cost_sums, nullptr, nullptr,
                         workspace, workspace_bytes, stream, s_all, act_rec, recorded, nullptr, nullptr, nullptr, nullptr, W);
+}
+
+int nocf_rollout_record_noisy_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, const float* scale, uint64_t seed, int64_t row0, int64_t n,
+                                  double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                  float* z_out, float* persample, float* cost_sums, float* s_all, float* act_rec, int32_t* recorded,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+    if (recorded) *recorded = 0;
+    if (!scale || !s_all || !z_out) return NOCF_E_NULL;
+    if (row0 < 0) return NOCF_E_SHAPE;
+    const NoiseSpec nz{scale, (unsigned long long)seed, (long long)row0};
+    return rollout_impl(phi, prob, x, n, t0, t1, nt, stepper, alph, z_out, persample, cost_sums, nullptr, nullptr,
+                        workspace, workspace_bytes, stream, s_all, act_rec, recorded, nullptr, nullptr, nullptr, nullptr, nullptr, &nz);
+}
+
+// W[k][row][i] = the disturbance of (seed, row0 + row, k, i): what the <noise> kernels add, as a tensor (nocf_noise.inc)
+int nocf_noise_fill_f32(float* W, int64_t n, int32_t nt, int32_t d, const float* scale, uint64_t seed, int64_t row0, void* stream) {
+    if (!W || !scale) return NOCF_E_NULL;
+    if (n < 1 || nt < 1 || d < 1 || row0 < 0) return NOCF_E_SHAPE;
+    const int64_t total = n * (int64_t)nt * d;
+    const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 65536);
+    hipLaunchKernelGGL(noise_fill_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, W, (long)n, (int)nt, (int)d, scale,
+                       (unsigned long long)seed, (long)row0);
+    return (int)hipGetLastError();
+}
+
+int nocf_debug_noise_words(uint64_t seed, int64_t row, int32_t k, int32_t i, uint32_t out[4]) {
+    if (!out) return NOCF_E_NULL;
+    if (row < 0 || k < 0 || i < 0) return NOCF_E_SHAPE;
+    unsigned int w[4];
+    noise_words((unsigned long long)seed, (long long)row, (int)k, (int)i, w);
+    for (int q = 0; q < 4; ++q) out[q] = w[q];
+    return 0;
 }
 
 size_t nocf_activation_record_floats(int32_t d, int32_t m, int32_t nTh, int64_t n, int32_t nt, int32_t stepper) {

@@ -32,7 +32,9 @@ struct LaneArgs {
 // DIST: the disturbed rollout (RollArgs::dist, W [nt][n][d]): lane j < d adds W[k][sample][j] to its component behind step k.  The load is
 // issued at the top of the step -- its address does not depend on the step -- and consumed behind the last stage.  REC and DIST together (the
 // recording forward of disturbed training): the next step's first stage input is formed from the displaced z, so it is recorded displaced
-template <int MP, int DP, bool REC, bool ONE = false, bool DIST = false>
+// DIST == 2: the same with the entry drawn here (nocf_noise.inc: RollArgs::nzScale / nzSeed / nzRow0) where DIST == 1 loads it -- into the same
+// register, at the top of the step, so every instruction behind it is shared.  Tail waves draw the noise of the row they replicate
+template <int MP, int DP, bool REC, bool ONE = false, int DIST = 0>
 __global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb pb, RollArgs ra) {
     const int lane = threadIdx.x & 63;
     const long sample = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -62,6 +64,8 @@ __global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb 
     const float wv = lane < m ? la.P.w[lane] : 0.f;
     const float cw = lane < D1 ? la.P.cw[lane] : 0.f;
     const float xt = lane < d ? pb.xtarget[lane] : 0.f;
+    float nzs = 0.f;                                    // this lane's component of sigma sqrt(h)
+    if constexpr (DIST == 2) nzs = lane < d ? ra.nzScale[lane] : 0.f;
 
     // ---- agent pairs handled by this lane (two trips cover up to 128 pairs; eligibility keeps N <= 15)
     const int npairs = (N * (N - 1)) / 2;
@@ -170,7 +174,8 @@ __global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb 
         const double hsd = t1k - tk;                      // stepRK4 re-derives h = t1 - t0 (src/OCflow.py:170)
         const float hs = (float)hsd;
         float wk = 0.f;
-        if constexpr (DIST) wk = lane < d ? ra.dist[((long)k * ra.n + row) * d + lane] : 0.f;
+        if constexpr (DIST == 2) wk = lane < d ? noise_value(nzs, ra.nzSeed, ra.nzRow0 + row, k, lane) : 0.f;
+        else if constexpr (DIST == 1) wk = lane < d ? ra.dist[((long)k * ra.n + row) * d + lane] : 0.f;
         // training: the stage input s = [x, t] of every evaluation goes to sAll[(k*nstage + st)][sample][0..d] (one row per lane group)
         auto record = [&](int st, int nstage, float s) {
             if (REC && ra.sAll && live && lane <= d) ra.sAll[(((long)k * nstage + st) * ra.n + sample) * (d + 1) + lane] = s;

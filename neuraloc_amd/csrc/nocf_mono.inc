@@ -220,7 +220,9 @@ __device__ __forceinline__ void mono_sincos(float x, float& sn, float& cs) {
 // back (in front of the zFull store and of the control evaluation).  Each thread loads the entries of its own components at the top of the step
 // (KBD + 1 registers at most; one for singlequad) and adds them behind the last stage.  REC and DIST together (the recording forward of
 // disturbed training): the state rows SB hold the displaced state when the next step's first stage input and activations are recorded
-template <int KBM, int KBD, bool REC, bool DIST = false>
+// DIST == 2: the entries are drawn (nocf_noise.inc: RollArgs::nzScale / nzSeed / nzRow0) where DIST == 1 ADDS them, behind the last stage, into the
+// same variable: nothing is held across the step's evaluations (drawn at the top of the step like the loads, the (4, 2) instantiation lost a wave)
+template <int KBM, int KBD, bool REC, int DIST = 0>
 __global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __restrict__ mpp, DevProb pb, float* ws, RollArgs ra) {
     constexpr int MT = (KBM + 3) / 4;              // hidden M-tiles per wave: tiles w, w+4, ...
     constexpr int T = 16;
@@ -344,7 +346,7 @@ __global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __res
         }
         constexpr int NDW = KBD + 1;                           // T (d + 4) <= 256 KBD + 48 components over 256 threads
         float wpre[NDW];
-        if constexpr (DIST) {
+        if constexpr (DIST == 1) {
 #pragma unroll
             for (int q = 0; q < NDW; ++q) wpre[q] = 0.f;
             if (!fin) {
@@ -623,7 +625,8 @@ __global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __res
                     float xs_;
                     if (last) {
                         xs_ = (nstage == 1 ? qz0 : qzA) + rk_wa * K;
-                        if constexpr (DIST) xs_ += wpre[0];                    // (j >= 12: 0)
+                        if constexpr (DIST == 2) xs_ += (j < d && row0 + s_ < ra.n) ? noise_value(ra.nzScale[j], ra.nzSeed, ra.nzRow0 + row0 + s_, k, j) : 0.f;
+                        else if constexpr (DIST == 1) xs_ += wpre[0];          // (j >= 12: 0)
                         qz0 = xs_;
                     }
                     else { qzA = (st == 0 ? qz0 : qzA) + rk_wa * K; xs_ = qz0 + rk_wx * K; }
@@ -678,8 +681,12 @@ __global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __res
                     if constexpr (DIST) {
                         if (last) {
                             float w = 0.f;
+                            if constexpr (DIST == 2) {
+                                if (i < d && row0 + t < ra.n) w = noise_value(ra.nzScale[i], ra.nzSeed, ra.nzRow0 + row0 + t, k, i);
+                            } else {
 #pragma unroll
-                            for (int q = 0; q < NDW; ++q) w = (it == q) ? wpre[q] : w;
+                                for (int q = 0; q < NDW; ++q) w = (it == q) ? wpre[q] : w;
+                            }
                             xs += w;
                             Z0[t * ZLD + i] = xs;
                         }

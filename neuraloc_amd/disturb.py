@@ -142,14 +142,28 @@ def path_statistics(v):
     return {"mean": v.mean(dim=1), "std": std, "q05": q[0], "q50": q[1], "q95": q[2]}
 
 
-def noise_study(x, Phi, prob, nt, sigma, paths, tspan=(0., 1.), alph=None, stepper="rk4", generator=None, mask=None, max_rows=1 << 16):
+def noise_study(x, Phi, prob, nt, sigma, paths, tspan=(0., 1.), alph=None, stepper="rk4", generator=None, mask=None, max_rows=1 << 16,
+                rng="torch", seed=None):
     """The distribution of the costs over `paths` Brownian disturbances of every start: each start is repeated `paths` times as rows of one
     batch (start-major: row i * paths + p), in chunks of whole starts of at most max_rows rows (max_rows < paths is a ValueError), one launch
     per chunk.  The disturbances are drawn chunk by chunk from `generator` (brownian_disturbances(nt, rows, d, sigma, tspan=tspan,
     generator=generator, device=x.device, mask=mask)).
+    rng="counter" (needs `seed`, a Python int in [0, 2**64); takes no generator): nothing is drawn -- every chunk is one noise.noisy_rollout
+    with row_offset = the chunk's first row, so start i, path p meets the noise of global row i * paths + p whatever max_rows is.
     :return: dict with, per quantity "L+G" (L + alph[0] G), "G", "Q", "W": a dict mean / std / q05 / q50 / q95 of [nex] tensors; and
              "persample" [nex, paths, 7], the table every figure is formed from"""
     alph = list(Phi.alph if alph is None else alph)
+    if rng not in ("torch", "counter"):
+        raise ValueError(f"rng must be 'torch' or 'counter', got {rng!r}")
+    if rng == "counter":
+        from .noise import _check_seed, noisy_rollout
+        if generator is not None:
+            raise ValueError("noise_study: rng='counter' draws nothing and takes no generator; pass seed")
+        if seed is None:
+            raise ValueError("noise_study: rng='counter' needs seed")
+        _check_seed(seed)
+    elif seed is not None:
+        raise ValueError("noise_study: seed belongs to rng='counter'; rng='torch' is seeded through generator")
     paths = int(paths)
     if paths < 1:
         raise ValueError("paths must be >= 1")
@@ -163,6 +177,10 @@ def noise_study(x, Phi, prob, nt, sigma, paths, tspan=(0., 1.), alph=None, stepp
     tabs = []
     for s0 in range(0, n, per):
         xs = x[s0:s0 + per].repeat_interleave(paths, dim=0).contiguous()
+        if rng == "counter":
+            tabs.append(noisy_rollout(xs, Phi, prob, nt, sigma, seed, tspan=tspan, alph=alph, stepper=stepper, mask=mask,
+                                      row_offset=s0 * paths)["persample"])
+            continue
         Wc = brownian_disturbances(nt, xs.shape[0], d, sigma, tspan=tspan, generator=generator, device=x.device, mask=mask)
         tabs.append(disturbed_rollout(xs, Phi, prob, nt, Wc, tspan=tspan, alph=alph, stepper=stepper)["persample"])
     tab = torch.cat(tabs).view(n, paths, 7)

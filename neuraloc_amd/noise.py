@@ -1,0 +1,252 @@
+"""Brownian disturbances from a counter-based generator, drawn inside the rollout kernels.
+
+disturb.brownian_disturbances draws a tensor W [nt, n, d] with torch.randn; here the disturbance of (row, step k, component i) is a pure
+function of (seed, GLOBAL row, k, i) -- Philox4x32-10 and a Box-Muller transform, csrc/nocf_noise.inc -- evaluated by the lane, one-CU and
+per-tile kernels where they otherwise load W[k][row][i].  No tensor exists; a row meets the same noise alone, in any batch, on any rank and
+in any chunk (row_offset = the global index of the call's first row), and a prefix in nt stays a prefix as long as sigma sqrt(h) is the same.
+
+    counter_disturbances   the same values as a tensor (nocf_noise_fill_f32): what disturbance_gradient and the worst-case search start from
+    noisy_rollout          disturbed_rollout on that tensor, bit for bit, without it (nocf_rollout_noisy_f32)
+    noisy_ocflow_train     disturbed_ocflow_train likewise (nocf_rollout_record_noisy_f32); the adjoint is the same code
+
+Single precision only; no CPU or eager-torch fallback; every check raises before a device is touched."""
+import ctypes as C
+import math
+import os
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _lib
+from .OCflow import _STEPPERS
+from .train import _OCflowTrain
+
+_FILL_ARGTYPES = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_int64, C.c_void_p]
+_NOISY_ARGTYPES = [C.POINTER(_lib.NocfPhi), C.POINTER(_lib.NocfProb), C.c_void_p, C.c_void_p, C.c_uint64, C.c_int64, C.c_int64,
+                   C.c_double, C.c_double, C.c_int32, C.c_int32, _lib.fp,
+                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                   C.c_void_p, C.c_size_t, C.c_void_p]
+_RECORD_ARGTYPES = [C.POINTER(_lib.NocfPhi), C.POINTER(_lib.NocfProb), C.c_void_p, C.c_void_p, C.c_uint64, C.c_int64, C.c_int64,
+                    C.c_double, C.c_double, C.c_int32, C.c_int32, _lib.fp,
+                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
+                    C.c_void_p, C.c_size_t, C.c_void_p]
+_PROTOTYPES = {"nocf_noise_fill_f32": _FILL_ARGTYPES, "nocf_rollout_noisy_f32": _NOISY_ARGTYPES,
+               "nocf_rollout_record_noisy_f32": _RECORD_ARGTYPES}
+
+
+def _entry(L, name):
+    """entry `name` of library L with its prototype set, or None when L does not export it"""
+    if not hasattr(L, name):
+        return None
+    f = getattr(L, name)
+    if f.argtypes is None:
+        f.restype = C.c_int
+        f.argtypes = _PROTOTYPES[name]
+    return f
+
+
+def _entry_for(L, name, what):
+    """(library, entry): L's, or the shipped library's when L is a per-shape library cached by an older build"""
+    f = _entry(L, name)
+    if f is None:
+        L = _lib.lib()
+        f = _entry(L, name)
+    if f is None:
+        raise RuntimeError(f"{what}: the HIP library does not export {name}; rebuild it")
+    return L, f
+
+
+def _check_seed(seed):
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"seed must be a Python int with 0 <= seed < 2**64, got {seed!r}")
+    return seed
+
+
+def _check_row_offset(row_offset):
+    if isinstance(row_offset, bool) or not isinstance(row_offset, int) or not 0 <= row_offset < 2 ** 62:
+        raise ValueError(f"row_offset must be a Python int >= 0, got {row_offset!r}")
+    return row_offset
+
+
+def noise_scale(sigma, nt, d, tspan=(0., 1.), mask=None):
+    """scale [d] on the host, float32: fp32(sigma_i sqrt(h)) formed in double with h = (tspan[1] - tspan[0]) / nt; 0 where mask == 0"""
+    if int(nt) < 1 or int(d) < 1:
+        raise ValueError("nt and d must be >= 1")
+    h = (float(tspan[1]) - float(tspan[0])) / int(nt)
+    if not h > 0:
+        raise ValueError("tspan must have positive length")
+    sg = (sigma.detach().to("cpu", torch.float64) if isinstance(sigma, torch.Tensor) else torch.as_tensor(sigma, dtype=torch.float64))
+    if sg.dim() > 1 or (sg.dim() == 1 and sg.numel() != int(d)):
+        raise ValueError("sigma must be a float or a [d] tensor")
+    scale = (sg.expand(int(d)) * math.sqrt(h)).to(torch.float32)
+    if mask is not None:
+        mk = torch.as_tensor(mask).detach().to("cpu")
+        if mk.numel() != int(d):
+            raise ValueError("mask must have d entries")
+        scale = scale * (mk.reshape(-1) != 0).to(torch.float32)
+    return scale.contiguous()
+
+
+def _require_device(device, what):
+    if device is None or torch.device(device).type != "cuda":
+        raise RuntimeError(f"{what}: device is {device}: the generator runs only on an MI355X (ROCm 'cuda' device); there is no CPU fallback")
+    return torch.device(device)
+
+
+def counter_disturbances(nt, n, d, sigma, seed, tspan=(0., 1.), mask=None, row_offset=0, device=None):
+    """The counterpart of brownian_disturbances: W [nt, n, d], float32, W[k, row, i] = the disturbance of (seed, row_offset + row, k, i) with
+    scale sigma_i sqrt(h) -- the values noisy_rollout adds, as a tensor (nocf_noise_fill_f32).
+    sigma: a float or [d]; mask [d]: coordinates with mask == 0 are not disturbed; seed: a Python int, 0 <= seed < 2**64;
+    row_offset: global index of row 0; device: an MI355X."""
+    if int(nt) < 1 or int(n) < 1 or int(d) < 1:
+        raise ValueError("nt, n and d must be >= 1")
+    scale = noise_scale(sigma, nt, d, tspan, mask)
+    seed, row_offset = _check_seed(seed), _check_row_offset(row_offset)
+    dev = _require_device(device, "counter_disturbances")
+    W = torch.empty(int(nt), int(n), int(d), dtype=torch.float32, device=dev)
+    scale = scale.to(dev)
+    with torch.cuda.device(dev):
+        _, f = _entry_for(_lib.lib(), "nocf_noise_fill_f32", "counter_disturbances")
+        rc = f(_lib.ptr(W), int(n), int(nt), int(d), _lib.ptr(scale), seed, row_offset, _lib.stream_ptr(dev))
+    _lib.check(rc, "nocf_noise_fill_f32")
+    return W
+
+
+def _check_call(what, x, net, nt, stepper, alph):
+    if isinstance(x, torch.Tensor) and x.dtype == torch.float64:
+        raise RuntimeError(f"{what}: x is float64; the noisy rollout is single precision only (the double-precision kernel takes no disturbance)")
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("x must be a torch.Tensor")
+    if x.dim() != 2:
+        raise ValueError("x must be nex-by-d")
+    n, d = x.shape
+    if d != net.d:
+        raise ValueError(f"x has d={d} but Phi was built for d={net.d}")
+    if int(nt) < 1:
+        raise ValueError("nt must be >= 1")
+    if n < 1:
+        raise ValueError("x has no rows")
+    if stepper not in _STEPPERS:
+        raise ValueError(f"stepper must be 'rk4' or 'rk1', got {stepper!r}")
+    if len(alph) < 6:
+        raise ValueError("alph needs 6 entries")
+    return n, d
+
+
+def noisy_rollout(x, Phi, prob, nt, sigma, seed, tspan=(0., 1.), alph=None, stepper="rk4", intermediates=False, mask=None, row_offset=0):
+    """disturbed_rollout(x, Phi, prob, nt, counter_disturbances(nt, nex, d, sigma, seed, tspan, mask, row_offset), ...) without the tensor: the
+    kernels draw each disturbance where they would load it, and every output equals that call's bit for bit.
+    :param sigma: a float or [d];  seed: a Python int, 0 <= seed < 2**64;  mask [d]: coordinates with mask == 0 are not disturbed
+    :param row_offset: global index of x's first row: row j of this call meets the noise of global row row_offset + j
+    :return: the dict of disturbed_rollout"""
+    alph = list(Phi.alph if alph is None else alph)
+    n, d = _check_call("noisy_rollout", x, Phi, nt, stepper, alph)
+    scale = noise_scale(sigma, nt, d, tspan, mask)
+    seed, row_offset = _check_seed(seed), _check_row_offset(row_offset)
+    x = _lib.require_device_f32(x, "x")
+    Phi._guard_no_autograd(x, "noisy_rollout")
+    with torch.no_grad():
+        _lib.check_errors()
+        phi_st, keep1, ws = Phi._c_struct(n)
+        prob_st, keep2 = prob._c_struct(x.device)
+        dev = x.device
+        scale = scale.to(dev)
+        persample = torch.empty(n, 7, dtype=torch.float32, device=dev)
+        sums = torch.empty(8, dtype=torch.float32, device=dev)
+        means = torch.empty(8, dtype=torch.float32, device=dev)
+        z_final = torch.empty(n, d + 4, dtype=torch.float32, device=dev)
+        zFull = ctrlFull = None
+        if intermediates:
+            cdim = _lib.lib().nocf_ctrl_dim(C.byref(prob_st), d)
+            zFull = torch.empty(nt + 1, n, d + 4, dtype=torch.float32, device=dev)
+            ctrlFull = torch.empty(nt + 1, n, cdim, dtype=torch.float32, device=dev)
+        alph_c = (C.c_float * 6)(*[float(a) for a in alph[:6]])
+        with torch.cuda.device(dev):
+            L = _lib.lib_for(Phi.d, Phi.m, Phi.nTh, phi_st.r, prob_st.n_agents, fwd=prob_st.kind != _lib.PROB_QUADCOPTER)
+            L, f = _entry_for(L, "nocf_rollout_noisy_f32", "noisy_rollout")
+            rc = f(C.byref(phi_st), C.byref(prob_st), _lib.ptr(x), _lib.ptr(scale), seed, row_offset, n,
+                   float(tspan[0]), float(tspan[1]), int(nt), _STEPPERS[stepper], alph_c,
+                   _lib.ptr(z_final), _lib.ptr(persample), _lib.ptr(sums), _lib.ptr(means), _lib.ptr(zFull), _lib.ptr(ctrlFull),
+                   _lib.ptr(ws), ws.numel() * ws.element_size(), _lib.stream_ptr(dev))
+        _lib.check(rc, "nocf_rollout_noisy_f32")
+        _lib.track_rollout_status(L, dev, "noisy_rollout")
+        out = {"Jc": means[7], "cs": [means[i] for i in range(7)], "persample": persample, "z_final": z_final}
+        if intermediates:
+            _lib.check_errors(sync=True)                   # consumed on the host (plots, files): a failed launch raises here
+            out["traj"], out["ctrl"] = zFull.permute(1, 2, 0), ctrlFull.permute(1, 2, 0)
+    return out
+
+
+class _OCflowTrainNoisy(torch.autograd.Function):
+    """_OCflowTrainDisturbed with the disturbances drawn inside the recording forward (nocf_rollout_record_noisy_f32): it saves the same
+    stage inputs and displaced z(T), so the backward is _OCflowTrain's, unchanged."""
+
+    @staticmethod
+    def forward(ctx, x, net, prob, tspan, nt, stepper, alph, n_total, group, noise, *params):
+        ctx.n_plain_args = 9
+        ctx.x_needs_grad = bool(x.requires_grad)
+        x = _lib.require_device_f32(x.detach(), "x")
+        scale, seed, row_offset = noise
+        n, d = x.shape
+        dev = x.device
+        scale = scale.to(dev)
+        phi_st, keep1, ws = net._c_struct(n)
+        prob_st, keep2 = prob._c_struct(dev)
+        nstage = 4 if stepper == "rk4" else 1
+        persample = torch.empty(n, 7, device=dev)
+        sums = torch.empty(8, device=dev)
+        z_out = torch.empty(n, d + 4, device=dev)
+        s_all = torch.empty(nt * nstage, n, d + 1, device=dev)
+        alph_c = (C.c_float * 6)(*[float(a) for a in alph[:6]])
+        _lib.check_errors()
+        ctx.tape = None
+        with torch.cuda.device(dev):
+            L = _lib.lib_for(net.d, net.m, net.nTh, phi_st.r, prob_st.n_agents, fwd=prob_st.kind != _lib.PROB_QUADCOPTER)
+            L, f = _entry_for(L, "nocf_rollout_record_noisy_f32", "noisy_ocflow_train")
+            ctx.mid_rows = int(L.nocf_mid_grad_rows(int(d), int(net.m), int(net.nTh), int(phi_st.r), int(prob_st.n_agents), int(n))) \
+                if hasattr(L, "nocf_rollout_bwd_mid_f32") else 0
+            # (the activation record is the one-CU kernel's here, as in _OCflowTrainDisturbed: m = 512 records on the per-tile kernel)
+            nact = 0 if (os.environ.get("NOCF_ACT_REC", "1") in ("0", "") or net.m > 128) else int(
+                L.nocf_activation_record_floats(int(d), int(net.m), int(net.nTh), int(n), int(nt), _STEPPERS[stepper]))
+            act = None
+            if nact:
+                try:
+                    act = torch.empty(nact, device=dev)
+                except torch.OutOfMemoryError:                 # the record is an optimisation: without it the adjoint recomputes
+                    act = None
+            recorded = C.c_int32(0)
+            rc = f(C.byref(phi_st), C.byref(prob_st), _lib.ptr(x), _lib.ptr(scale), seed, row_offset, n,
+                   float(tspan[0]), float(tspan[1]), int(nt), _STEPPERS[stepper], alph_c,
+                   _lib.ptr(z_out), _lib.ptr(persample), _lib.ptr(sums), _lib.ptr(s_all), _lib.ptr(act), C.byref(recorded),
+                   _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+        _lib.check(rc, "nocf_rollout_record_noisy_f32")
+        ctx.act = act if recorded.value else None
+        return _OCflowTrain._forward_tail(ctx, L, dev, net, prob, tspan, nt, stepper, alph, n_total, group, n, sums, s_all, z_out)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gJ, _gmeans):
+        return _OCflowTrain._adjoint(ctx, gJ)
+
+
+def noisy_ocflow_train(x, net, prob, tspan, nt, sigma, seed, stepper="rk4", alph=None, mask=None, row_offset=0, n_total=None, group=None):
+    """disturbed_ocflow_train under counter_disturbances(nt, nex, d, sigma, seed, tspan, mask, row_offset), without the tensor: (Jc, cs) with Jc
+    differentiable w.r.t. every parameter of `net` and w.r.t. x when x requires a gradient.
+    :param row_offset: global index of x's first row -- a rank passes the first row of its shard, and the noise a sample meets then does not
+                       depend on how the batch is cut;  n_total, group: as for ocflow_train
+    Single precision only.  Every check below raises before a device is touched."""
+    alph = list(net.alph if alph is None else alph)
+    for name, t in [("x", x)] + [(name, p_) for name, p_ in net.named_parameters()]:
+        if isinstance(t, torch.Tensor) and t.dtype == torch.float64:
+            raise RuntimeError(f"noisy_ocflow_train: {name} is float64; the noisy rollout is single precision only "
+                               "(the double-precision kernels take no disturbance)")
+    n, d = _check_call("noisy_ocflow_train", x, net, nt, stepper, alph)
+    pd_ = getattr(prob, "d", None)
+    if pd_ is not None and int(pd_) != d:
+        raise ValueError(f"the problem object has d={pd_} but x has d={d}")
+    scale = noise_scale(sigma, nt, d, tspan, mask)
+    seed, row_offset = _check_seed(seed), _check_row_offset(row_offset)
+    _lib.require_device_f32(x, "x")
+    params = [p for _, p in net.named_parameters()]
+    Jc, means = _OCflowTrainNoisy.apply(x, net, prob, list(tspan), int(nt), stepper, alph, n_total, group, (scale, seed, row_offset), *params)
+    return Jc, [means[i] for i in range(7)]

@@ -12,6 +12,8 @@ N GPUs:    python -m torch.distributed.run --nnodes=1 --nproc-per-node N --maste
            (one rank per GPU; each rank draws n_train/N samples; the 8 cost sums and one flat gradient buffer are
            all-reduced over RCCL per iteration, so every rank takes the same Adam step).
 
+--noise_rng counter (addition, with --noise): the disturbances come from the counter-based generator inside the kernels
+(seed = noise_seed << 32 | iteration, row = the sample's global row), so the run does not depend on the number of ranks.
 --noise SIGMA [--noise_seed S] (addition): the training rollouts run under per-step Brownian state disturbances sigma dB
 (neuraloc_amd.disturbed_ocflow_train), a fresh W every iteration; validation and its logged costs stay undisturbed.
 SIGMA = 0 (default) is the run without the flag."""
@@ -58,8 +60,10 @@ _FLAGS = [
     ("noise", float, 0.0, "(addition) SIGMA > 0: train on rollouts under Brownian state disturbances sigma dB at every step "
                           "(neuraloc_amd.disturbed_ocflow_train); validation stays undisturbed; single precision only"),
     ("noise_seed", int, 0, "(addition) seed of the disturbances for --noise (rank is added)"),
+    ("noise_rng", str, "torch", "(addition) torch: every rank draws its shard's disturbances with torch.randn; counter: they are drawn inside "
+                                "the kernels from (noise_seed, iteration, global row) (neuraloc_amd.noisy_ocflow_train), the same on any number of ranks"),
 ]
-_CHOICES = {"data": PROBLEM_NAMES, "optim": ["adam"], "prec": ["single", "double"], "approach": ["ocflow"]}
+_CHOICES = {"data": PROBLEM_NAMES, "optim": ["adam"], "prec": ["single", "double"], "approach": ["ocflow"], "noise_rng": ["torch", "counter"]}
 
 
 def parse_args(argv=None):
@@ -79,6 +83,10 @@ def main(argv=None):
         raise SystemExit("--noise SIGMA must be >= 0")
     if args.noise > 0 and args.prec == "double":                       # refused before anything runs or is written
         raise SystemExit("--noise runs in single precision only (the double-precision rollout takes no disturbance)")
+    if args.noise_rng == "counter" and args.prec == "double":
+        raise SystemExit("--noise_rng counter runs in single precision only (the double-precision rollout takes no disturbance)")
+    if args.noise_rng == "counter" and not 0 <= args.noise_seed < 2 ** 32:
+        raise SystemExit("--noise_rng counter needs 0 <= --noise_seed < 2**32 (the iteration takes the seed's low word)")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     if world > 1:
@@ -129,14 +137,19 @@ def main(argv=None):
 
     rollout = na.OCflow_sharded if dist else na.OCflow
     # --noise: every iteration draws its own W on the device; each rank its own shard's, from its own generator
-    noise_gen = torch.Generator(device=dev).manual_seed(args.noise_seed + rank) if args.noise > 0 else None
+    # --noise_rng counter: nothing is drawn -- the kernels form the disturbance of (iteration, global row, step, component) themselves
+    noise_counter = args.noise > 0 and args.noise_rng == "counter"
+    noise_gen = torch.Generator(device=dev).manual_seed(args.noise_seed + rank) if args.noise > 0 and not noise_counter else None
     best_loss, best_params, total = float("inf"), None, 0.0
     net.train()
     prob.train()
     end = time.time()
     for itr in range(1, args.niters + 1):
         optim.zero_grad()
-        if noise_gen is not None:
+        if noise_counter:
+            Jc, cs = na.noisy_ocflow_train(x0, net, prob, tspan, args.nt, args.noise, (args.noise_seed << 32) | itr, "rk4", net.alph,
+                                           row_offset=lo, group=True if dist else None)
+        elif noise_gen is not None:
             W = na.brownian_disturbances(args.nt, x0.shape[0], d, args.noise, tspan=tspan, generator=noise_gen, device=dev)
             Jc, cs = na.disturbed_ocflow_train(x0, net, prob, tspan, args.nt, W, "rk4", net.alph, group=True if dist else None)
         else:
