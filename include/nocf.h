@@ -487,6 +487,33 @@ int nocf_rollout_bwd_states_f32(const NocfPhi* phi, const NocfProb* prob, int64_
                                 void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The JOINT adjoints: nocf_rollout_bwd_small_f32 / _mid_f32 / _act_f32 with one more output, lamW (after lam0), the per-step state
+ * cotangents of nocf_rollout_bwd_states_f32.  One launch gives the parameter gradients (and lam0) exactly as the existing entry forms
+ * them AND dJ/dW of a disturbed rollout: an iteration of min-max ("free" adversarial) training is one recording forward, one joint
+ * adjoint and one nocf_disturbance_ascent_f32, where the existing entries need two forwards and two adjoints.  The kernels are the
+ * existing ones' third instantiation: every statement of the full adjoint plus the lamW[k] store of the state-only one, at the same
+ * place (the state cotangent when the last stage of step k begins; rk1 alike).
+ *   lamW   device [nt, n, d] (nullable), time-major like W, contiguous: lamW[k] = dJ/dW[k]; lamW[nt-1] is the terminal cotangent dJ/dx(T).
+ *          Only rows < n and d floats per row are written.  lamW == NULL: the call IS the existing entry (same kernel, same bits)
+ *   every other argument, the workspace and every refusal: the existing entry's (each goes through that entry's own code path)
+ * nocf_last_rollout_kernel() reports "rollout_lane_bwd_kernel<joint>", "rollout_mono_bwd_kernel<joint>" or "rollout_bwd_kernel<joint>"
+ * (the existing names when lamW == NULL).  The per-tile joint kernel is instantiated for the generic plan and for the shapes whose
+ * disturbed forward is specialised, like the state-only one.  nocf_version() is unchanged: callers probe for the symbols.  float32 only.
+ */
+int nocf_rollout_bwd_small_w_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t nt, int32_t stepper, double t1,
+                                 const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
+                                 float* gpart, float* lam0, float* lamW, void* stream);
+int nocf_rollout_bwd_mid_w_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t nt, int32_t stepper, double t1,
+                               const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
+                               const float* act_rec, float* gpart, int64_t gpart_rows, float* lam0, float* lamW,
+                               void* workspace, size_t workspace_bytes, void* stream);
+int nocf_rollout_bwd_act_w_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t nt, int32_t stepper, double t1,
+                               const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
+                               float* Y, float* Ob, float* V, float* Ab, float* Qb, float* U0, float* Wb, float* Gb, float* Sx,
+                               float* PHIb, float* lam0, float* lamW, const float* act_rec,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * One step of projected gradient ascent on per-row disturbance paths, in place: for every row i, over its [nt, d] path of W,
  *     W_i += step (mask o g_i) / ||mask o g_i||_2          (the row is left untouched when that norm is 0 or not finite)
  *     W_i *= eps / ||W_i||_2   when ||W_i||_2 > eps         (projection onto the ball over the whole path)

@@ -45,7 +45,8 @@ struct BwdArgs {
     // carry the parameter gradients
     const float* gbar_in; float* sbar_out;
     // state-only instantiations (STATES, nocf_rollout_bwd_states_f32): [nt][n][d] (nullable), the state cotangent LAM when the last stage of
-    // step k begins = dJ/dW[k] of a disturbed rollout (z_{k+1} = step(z_k) + W[k]); lamW[nt-1] is the terminal cotangent dJ/dx(T)
+    // step k begins = dJ/dW[k] of a disturbed rollout (z_{k+1} = step(z_k) + W[k]); lamW[nt-1] is the terminal cotangent dJ/dx(T).
+    // STATES is a mode: 0 full, 1 state-only, 2 joint (nocf_rollout_bwd_*_w_f32: mode 0's statements plus this store)
     float* lamW;
 };
 
@@ -234,8 +235,9 @@ __device__ void quad_adjoint(const Ctx& c, const DevPlan& pl, const DevProb& pb,
 //   obar = (1-tau_0^2).taubar_0 + tau_0.ubar_0 ;  sbar = K0' obar + A'A gbar
 // in: GB[t][0..d] ; out: SBAR[t][0..d], and the row streams of this evaluation at global row `grow0 + t`
 // (per layer i: hN v_i with abar_{i-1}, and qbar_i with u_{i-1}, at layer offset (i-1)*lstride).
-// STATES: no row stream is stored and no stream pointer is dereferenced (the state-only adjoint: SBAR is all the caller needs).
-template <int S, bool STATES = false>
+// STATES == 1: no row stream is stored and no stream pointer is dereferenced (the state-only adjoint: SBAR is all the caller needs);
+// 0 and 2 (full and joint) store them alike -- the joint mode's lamW store sits in rollout_bwd_body, not here.
+template <int S, int STATES = 0>
 __device__ void phi_vjp(const Ctx& c, const DevPlan& pl, Ring& rg, const BwdArgs& ba, long grow0, long nvalid) {
     const int T = pl.T, LD = pl.LD, m = pl.m, D1 = pl.D1, r = pl.r, L = pl.nTh - 1, TLD = pl.T * pl.LD;
     const float hN = pl.hN;
@@ -295,7 +297,7 @@ __device__ void phi_vjp(const Ctx& c, const DevPlan& pl, Ring& rg, const BwdArgs
                     lds[otb + t * LD + col] = lds[oAi + t * LD + col] * vb;     // taubar_i
                 } else {
                     lds[oq + t * LD + col] = (1.f - ti * ti) * wv[col] * vb;    // qbar_L  (a_L = w, ubar_L = 0)
-                    if constexpr (!STATES) { if (t < nvalid) ba.Wb[(grow0 + t) * m + col] = ab; }          // dw row
+                    if constexpr (STATES != 1) { if (t < nvalid) ba.Wb[(grow0 + t) * m + col] = ab; }          // dw row
                 }
             }
         });
@@ -330,7 +332,7 @@ __device__ void phi_vjp(const Ctx& c, const DevPlan& pl, Ring& rg, const BwdArgs
     });
     __syncthreads();
     TL(c, 58);
-    if constexpr (!STATES) {
+    if constexpr (STATES != 1) {
     // row streams of this evaluation (coalesced rows), after the last phase: nothing here competes with a weight prefetch
     const int oy = oV(0);
     // the m-wide streams go out as 16-B pieces (one float4 per lane and stream: a quarter of the store instructions of a
@@ -382,7 +384,7 @@ __device__ void phi_vjp(const Ctx& c, const DevPlan& pl, Ring& rg, const BwdArgs
     }
 }
 
-template <int S, bool STATES = false>
+template <int S, int STATES = 0>
 __device__ __forceinline__ void rollout_bwd_body(const DevPlan& pl, const DevPlan* __restrict__ plp, const DevProb& pb,
                                                  const float* __restrict__ ws, const BwdArgs& ba) {
     Ctx c;
@@ -434,7 +436,7 @@ __device__ __forceinline__ void rollout_bwd_body(const DevPlan& pl, const DevPla
             }
             if (c.tid < T) SB[c.tid * pl.LDs + d] = ba.t1;
         } else {
-            if constexpr (STATES) {
+            if constexpr (STATES != 0) {
                 if (st == ba.nstage - 1 && ba.lamW)
                     for (int j = c.tid; j < T * d; j += c.nthreads) {
                         const int t = j / d, i = j - t * d;
@@ -525,7 +527,7 @@ __device__ __forceinline__ void rollout_bwd_body(const DevPlan& pl, const DevPla
             __syncthreads();
         }
         if (fin) {
-            if constexpr (!STATES) {
+            if constexpr (STATES != 1) {
             // value rows: the cotangent of Phi1 reuses the forward quantities: ubar_i = phib a_i, so
             // qbar_i = phib hN v_i, obar = phib y, dw row = phib u_L  (no extra GEMM)
             const long vrow0 = (total + 1) * ba.n + row0;
@@ -612,7 +614,7 @@ __device__ __forceinline__ void rollout_bwd_body(const DevPlan& pl, const DevPla
         }
 }
 
-template <int S, class SP, bool STATES = false>
+template <int S, class SP, int STATES = 0>
 __global__ void __launch_bounds__(NOCF_MAXTHREADS) rollout_bwd_kernel(const DevPlan* __restrict__ plp, DevProb pb,
                                                                       const float* __restrict__ ws, BwdArgs ba) {
     if constexpr (SP::fixed) {

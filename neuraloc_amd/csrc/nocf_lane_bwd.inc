@@ -11,6 +11,9 @@
 // STATES (nocf_rollout_bwd_states_f32): the state-only instantiation.  The lambda recursion (fbar, gbar, XD, XS, XP, LAM) is the same
 // statements; the gradient rows, their FMAs and the gpart store are compiled out, and LAM is written to lamW[k] when the last stage of step
 // k begins -- z_{k+1} = step(z_k) + W[k], so that cotangent is dJ/dW[k] (lamW[nt-1]: the terminal cotangent dJ/dx(T)).
+// STATES is a mode: 0 the full adjoint, 1 the state-only one (`false` / `true` select these two as before), 2 the JOINT one
+// (nocf_rollout_bwd_small_w_f32): every statement of mode 0 plus the lamW[k] store of mode 1 at the same place -- one launch gives the
+// parameter gradients and dJ/dW of a disturbed rollout (min-max training).  Both tests are `if constexpr`: mode 0 carries no trace of the store.
 
 struct LaneBwdArgs {
     DevPhi P;
@@ -21,12 +24,12 @@ struct LaneBwdArgs {
     float t1, a0, a3, a4, a5, inv_n;
     float* gpart; long P_total;
     float* lam0;
-    float* lamW;              // [nt][n][d] (nullable): the state cotangent behind every step, dJ/dW of a disturbed rollout (STATES instantiation)
+    float* lamW;              // [nt][n][d] (nullable): the state cotangent behind every step, dJ/dW of a disturbed rollout (STATES modes 1 and 2)
 };
 
 __device__ __forceinline__ float sgnf(float v) { return (v > 0.f) ? 1.f : (v < 0.f ? -1.f : 0.f); }
 
-template <int MP, int DP, bool STATES = false>
+template <int MP, int DP, int STATES = 0>
 __global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, DevProb pb) {
     const int lane = threadIdx.x & 63;
     const long sample = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -84,7 +87,7 @@ __global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, D
         float wst = 1.f, cpl = 0.f;
         if (la.nstage != 1) { wst = (st == 0 || st == 3) ? c16 : c26; cpl = (st == 3) ? 0.f : (st == 2 ? 1.f : 0.5f); }
         if (!fin && st == la.nstage - 1) {
-            if constexpr (STATES) { if (la.lamW && live && lane < d) la.lamW[((long)k * la.n + sample) * d + lane] = LAM; }
+            if constexpr (STATES != 0) { if (la.lamW && live && lane < d) la.lamW[((long)k * la.n + sample) * d + lane] = LAM; }
             XS = 0.f; XP = 0.f;
         }
         float s;
@@ -130,7 +133,7 @@ __global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, D
                 gbar = la.inv_n * la.a5 * eg;
             }
             // the value cotangent reuses the forward quantities: ubar = phib a, qbar = phib v, obar = phib y
-            if constexpr (!STATES) {
+            if constexpr (STATES != 1) {
             const float phib = la.inv_n * la.a4 * ef;
 #pragma unroll
             for (int kk = 0; kk < MP; ++kk) gK1[kk] = fmaf(phib * v, lane_bcast(u0, kk), gK1[kk]);
@@ -213,7 +216,7 @@ __global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, D
             const float gi = lane_bcast(gbar, i), si = lane_bcast(s, i);
             ybar = fmaf(k0row[i], gi, ybar);
             sA = fmaf(symA[i], gi, sA);
-            if constexpr (!STATES) { gK0[i] = fmaf(y, gi, gK0[i]); gM[i] = fmaf(gbar, si, gM[i]); } else (void)si;
+            if constexpr (STATES != 1) { gK0[i] = fmaf(y, gi, gK0[i]); gM[i] = fmaf(gbar, si, gM[i]); } else (void)si;
         }
         const float abar = th0 * ybar, tau0bar = a * ybar;
         float vbar = 0.f;
@@ -221,14 +224,14 @@ __global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, D
         for (int kk = 0; kk < MP; ++kk) {
             const float ak = lane_bcast(abar, kk);
             vbar = fmaf(k1row[kk], ak, vbar);
-            if constexpr (!STATES) gK1[kk] = fmaf(v, ak, gK1[kk]);
+            if constexpr (STATES != 1) gK1[kk] = fmaf(v, ak, gK1[kk]);
         }
         const float qbar = (1.f - th1 * th1) * wv * vbar;
-        if constexpr (!STATES) gw += abar + th1 * vbar;
+        if constexpr (STATES != 1) gw += abar + th1 * vbar;
         float u0bar = 0.f;
 #pragma unroll
         for (int j = 0; j < MP; ++j) u0bar = fmaf(k1col[j], lane_bcast(qbar, j), u0bar);
-        if constexpr (!STATES) {
+        if constexpr (STATES != 1) {
 #pragma unroll
             for (int kk = 0; kk < MP; ++kk) gK1[kk] = fmaf(qbar, lane_bcast(u0, kk), gK1[kk]);
         }
@@ -236,7 +239,7 @@ __global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, D
         float sbar = sA;
 #pragma unroll
         for (int kk = 0; kk < MP; ++kk) sbar = fmaf(k0col[kk], lane_bcast(obar, kk), sbar);
-        if constexpr (!STATES) {
+        if constexpr (STATES != 1) {
 #pragma unroll
             for (int i = 0; i < DP; ++i) gK0[i] = fmaf(obar, lane_bcast(s, i), gK0[i]);
             gb0 += obar; gb1 += qbar;
@@ -252,7 +255,7 @@ __global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, D
     }
 
     if (!live) return;
-    if constexpr (!STATES) {
+    if constexpr (STATES != 1) {
     float* gp = la.gpart + sample * la.P_total;
     long o = 0;
 #pragma unroll

@@ -22,6 +22,8 @@
 // STATES (nocf_rollout_bwd_states_f32): the state-only instantiation.  The lambda recursion is the same statements; the row-layout copies of
 // the outer products' operands, the outer-product MFMAs, every gradient accumulator and the partial-vector write are compiled out, and LAM
 // goes to BwdArgs::lamW[k] when the last stage of step k begins (dJ/dW[k] of a disturbed rollout; lamW[nt-1] is the terminal cotangent).
+// STATES is a mode: 0 the full adjoint, 1 the state-only one (`false` / `true` select these two as before), 2 the JOINT one
+// (nocf_rollout_bwd_mid_w_f32): every statement of mode 0 plus the lamW[k] store of mode 1 at the same place, both under `if constexpr`.
 
 // accumulator in AccVGPRs (the 64 registers of a wave's dK1 tiles sit beside the resident K1 images in the upper half of the register file)
 __device__ __forceinline__ void mfma16_aa(f32x4& acc, float a, float b) {
@@ -140,7 +142,7 @@ __device__ __forceinline__ void mono_lowrank(const MonoPlan& mp, const f32x4& AZ
     L4[(mp.lZP >> 2) + wave * 64 + lane] = make_float4(zacc[0], zacc[1], zacc[2], zacc[3]);
 }
 
-template <int KBM, int KBD, bool STATES = false>
+template <int KBM, int KBD, int STATES = 0>
 __global__ void __launch_bounds__(256) rollout_mono_bwd_kernel(const MonoPlan* __restrict__ mpp, DevProb pb, const float* __restrict__ ws, BwdArgs ba) {
     static_assert(KBD == 1 || KBD == 2, "d + 1 <= 32: the (sample, entry) threads take KBD entries each; dM is KBD x KBD tiles on the four waves");
     constexpr int MT = (KBM + 3) / 4;
@@ -304,7 +306,7 @@ __global__ void __launch_bounds__(256) rollout_mono_bwd_kernel(const MonoPlan* _
                     const int i = (tid & 15) + 16 * q;
                     if (i < D1) SB[t * LDs + i] = s_next[q];
                     lds[mp.lSF + q * 256 + (((tid & 15) >> 2) * 16 + t) * 4 + (tid & 3)] = (i < D1) ? s_next[q] : 0.f;
-                    if constexpr (STATES) {
+                    if constexpr (STATES != 0) {
                         if (!fin && st == ba.nstage - 1 && i < d && ba.lamW && t < nvalid) ba.lamW[((long)k * ba.n + row0 + t) * d + i] = LAM[t * ZLD + i];
                     }
                     if (!fin && st == ba.nstage - 1 && i < d) { XS[t * ZLD + i] = 0.f; XP[t * ZLD + i] = 0.f; }
@@ -318,7 +320,7 @@ __global__ void __launch_bounds__(256) rollout_mono_bwd_kernel(const MonoPlan* _
                         th1[mi] = (f32x4){r_t1[mi].x, r_t1[mi].y, r_t1[mi].z, r_t1[mi].w};
                         av[mi] = (f32x4){r_a[mi].x, r_a[mi].y, r_a[mi].z, r_a[mi].w};
                         u1k[mi] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                        if (!STATES && mt < KBM) {
+                        if (STATES != 1 && mt < KBM) {
                             const int ro = l16 * LDR + 16 * mt + 4 * slot;
                             *reinterpret_cast<float4*>(lds + mp.lRU0 + ro) = r_u0[mi];
                             *reinterpret_cast<float4*>(lds + mp.lRV + ro) = make_float4(hN * th1[mi][0] * wv[mi][0], hN * th1[mi][1] * wv[mi][1],
@@ -373,7 +375,7 @@ __global__ void __launch_bounds__(256) rollout_mono_bwd_kernel(const MonoPlan* _
                     if (mt < KBM) {
                         const float4 u4 = make_float4(sg[0], sg[1], sg[2], sg[3]);
                         L4[(mp.lUF >> 2) + mt * 64 + lane] = u4;
-                        if constexpr (!STATES) *reinterpret_cast<float4*>(lds + mp.lRU0 + l16 * LDR + 16 * mt + 4 * slot) = u4;
+                        if constexpr (STATES != 1) *reinterpret_cast<float4*>(lds + mp.lRU0 + l16 * LDR + 16 * mt + 4 * slot) = u4;
                     }
                 }
                 TL(cc, 2);
@@ -397,7 +399,7 @@ __global__ void __launch_bounds__(256) rollout_mono_bwd_kernel(const MonoPlan* _
                     }
                     if (mt < KBM) {
                         L4[(mp.lVF >> 2) + mt * 64 + lane] = make_float4(vv[0], vv[1], vv[2], vv[3]);
-                        if constexpr (!STATES) *reinterpret_cast<float4*>(lds + mp.lRV + l16 * LDR + 16 * mt + 4 * slot) = make_float4(hN * vv[0], hN * vv[1], hN * vv[2], hN * vv[3]);
+                        if constexpr (STATES != 1) *reinterpret_cast<float4*>(lds + mp.lRV + l16 * LDR + 16 * mt + 4 * slot) = make_float4(hN * vv[0], hN * vv[1], hN * vv[2], hN * vv[3]);
                     }
                 }
                 if (fin) {
@@ -422,7 +424,7 @@ __global__ void __launch_bounds__(256) rollout_mono_bwd_kernel(const MonoPlan* _
                     y.x = th0[mi][0] * av[mi][0]; y.y = th0[mi][1] * av[mi][1]; y.z = th0[mi][2] * av[mi][2]; y.w = th0[mi][3] * av[mi][3];
                     if (mt < KBM) {
                         L4[(mp.lUF >> 2) + mt * 64 + lane] = y;
-                        if constexpr (!STATES) *reinterpret_cast<float4*>(lds + mp.lRY + l16 * LDR + 16 * mt + 4 * slot) = y;
+                        if constexpr (STATES != 1) *reinterpret_cast<float4*>(lds + mp.lRY + l16 * LDR + 16 * mt + 4 * slot) = y;
                     }
                 }
                 TL(cc, 7);
@@ -591,7 +593,7 @@ __global__ void __launch_bounds__(256) rollout_mono_bwd_kernel(const MonoPlan* _
                 if (mt < KBM) {
                     const float4 a4 = make_float4(ab0[mi][0], ab0[mi][1], ab0[mi][2], ab0[mi][3]);
                     L4[(mp.lVF >> 2) + mt * 64 + lane] = a4;                           // (v fragments are consumed: behind P3's barrier)
-                    if constexpr (!STATES) *reinterpret_cast<float4*>(lds + mp.lRAB + l16 * LDR + 16 * mt + 4 * slot) = a4;
+                    if constexpr (STATES != 1) *reinterpret_cast<float4*>(lds + mp.lRAB + l16 * LDR + 16 * mt + 4 * slot) = a4;
                 }
             }
             TL(cc, 14);
@@ -612,14 +614,14 @@ __global__ void __launch_bounds__(256) rollout_mono_bwd_kernel(const MonoPlan* _
                     dwv[e] = dwr;
                 }
                 if (mt < KBM) {
-                    if constexpr (!STATES) {
+                    if constexpr (STATES != 1) {
                         float4 s1_ = L4[(LL.lACC >> 2) + (KBM + mt) * 64 + lane], s2_ = L4[(LL.lACC >> 2) + (2 * KBM + mt) * 64 + lane];
                         s1_.x += qt[0]; s1_.y += qt[1]; s1_.z += qt[2]; s1_.w += qt[3];
                         s2_.x += dwv[0]; s2_.y += dwv[1]; s2_.z += dwv[2]; s2_.w += dwv[3];
                         L4[(LL.lACC >> 2) + (KBM + mt) * 64 + lane] = s1_; L4[(LL.lACC >> 2) + (2 * KBM + mt) * 64 + lane] = s2_;
                     }
                     L4[(mp.lUF >> 2) + mt * 64 + lane] = make_float4(qb[0], qb[1], qb[2], qb[3]);      // (y fragments are consumed: behind P4's barrier)
-                    if constexpr (!STATES) *reinterpret_cast<float4*>(lds + mp.lRQB + l16 * LDR + 16 * mt + 4 * slot) = make_float4(qt[0], qt[1], qt[2], qt[3]);
+                    if constexpr (STATES != 1) *reinterpret_cast<float4*>(lds + mp.lRQB + l16 * LDR + 16 * mt + 4 * slot) = make_float4(qt[0], qt[1], qt[2], qt[3]);
                 }
             }
             TL(cc, 17);
@@ -638,13 +640,13 @@ __global__ void __launch_bounds__(256) rollout_mono_bwd_kernel(const MonoPlan* _
                     ot[e] = ob[e] + phib * (t0 * av[mi][e]);                           // + the value's: phib y
                 }
                 if (mt < KBM) {
-                    if constexpr (!STATES) {
+                    if constexpr (STATES != 1) {
                         float4 s0_ = L4[(LL.lACC >> 2) + mt * 64 + lane];
                         s0_.x += ot[0]; s0_.y += ot[1]; s0_.z += ot[2]; s0_.w += ot[3];
                         L4[(LL.lACC >> 2) + mt * 64 + lane] = s0_;
                     }
                     L4[(mp.lVF >> 2) + mt * 64 + lane] = make_float4(ob[0], ob[1], ob[2], ob[3]);      // (abar0 fragments are consumed: behind the barrier above)
-                    if constexpr (!STATES) *reinterpret_cast<float4*>(lds + mp.lROB + l16 * LDR + 16 * mt + 4 * slot) = make_float4(ot[0], ot[1], ot[2], ot[3]);
+                    if constexpr (STATES != 1) *reinterpret_cast<float4*>(lds + mp.lROB + l16 * LDR + 16 * mt + 4 * slot) = make_float4(ot[0], ot[1], ot[2], ot[3]);
                 }
             }
             TL(cc, 20);
@@ -657,7 +659,7 @@ __global__ void __launch_bounds__(256) rollout_mono_bwd_kernel(const MonoPlan* _
             TL(cc, 23);
 
             // ================= weight gradients: outer products with the 16 samples on the k axis =================
-            if constexpr (!STATES) {
+            if constexpr (STATES != 1) {
                 float aV[MT][4], aQ[MT][4], aY[MT][4], aO[MT][4];
 #pragma unroll
                 for (int mi = 0; mi < MT; ++mi) {
@@ -729,7 +731,7 @@ __global__ void __launch_bounds__(256) rollout_mono_bwd_kernel(const MonoPlan* _
 #pragma unroll
                 for (int q = 0; q < KBD; ++q) {
                     const int i = (tid & 15) + 16 * q;
-                    if constexpr (!STATES) dca[q] += GB[t * LDs + i] + lds[LL.lPHIB + t] * SB[t * LDs + i];  // dc = sum gbar (+ phib s); entries >= d + 1 of the rows are 0
+                    if constexpr (STATES != 1) dca[q] += GB[t * LDs + i] + lds[LL.lPHIB + t] * SB[t * LDs + i];  // dc = sum gbar (+ phib s); entries >= d + 1 of the rows are 0
                     if (i < d) {
                         const float xb = SBAR[t * GLD + i] + XD[t * ZLD + i];
                         if (fin) {
@@ -755,7 +757,7 @@ __global__ void __launch_bounds__(256) rollout_mono_bwd_kernel(const MonoPlan* _
             }
     }
 
-    if constexpr (!STATES) {
+    if constexpr (STATES != 1) {
     // ---- this workgroup's partial gradient vector: K0 [m][D1], b0, K1 [m][m], b1, w, c.weight [D1], c.bias, dM [D1][D1]
     float* gp = ba.gpart + (long)blockIdx.x * ba.gstride;
     const long oK0 = 0, ob0 = (long)m * D1, oK1 = ob0 + m, ob1 = oK1 + (long)m * m, ow = ob1 + m, ocw = ow + m, ocb = ocw + D1, oM = ocb + 1;

@@ -228,8 +228,10 @@ class _OCflowTrain(torch.autograd.Function):
         return _OCflowTrain._adjoint(ctx, gJ)
 
     @staticmethod
-    def _adjoint(ctx, gJ):
-        """the backward of _OCflowTrain and of _OCflowTrainDisturbed: everything it reads is what either forward saved"""
+    def _adjoint(ctx, gJ, want_w=False):
+        """the backward of _OCflowTrain and of _OCflowTrainDisturbed: everything it reads is what either forward saved.
+        want_w (minmax._OCflowTrainMinmax): the JOINT entry of the same family (nocf_rollout_bwd_small_w_f32 / _mid_w_f32 / _act_w_f32) runs in
+        place of the existing one and also writes lamW [nt, n, d] = dJc/dW; _finish returns it as W's gradient"""
         s_all, z_out = ctx.saved_tensors
         net, prob, nt, alph = ctx.net, ctx.prob, ctx.nt, ctx.alph
         if [p._version for p in net.parameters()] != ctx.param_versions:
@@ -252,15 +254,28 @@ class _OCflowTrain(torch.autograd.Function):
         alph_c = (C.c_float * 6)(*[float(a) for a in alph[:6]])
         lam0 = torch.empty(n, d, device=dev) if ctx.x_needs_grad else None          # dJc/dx0, like autograd's x.grad
         lib = _lib.lib_for(net.d, net.m, net.nTh, phi_st.r, prob_st.n_agents)
+        lamW = ()                                                   # the joint entries take lamW right behind lam0; the existing ones nothing
+        if want_w:
+            joint = _joint_entries(lib)
+            if joint is None:                              # a per-shape library cached by an older build: the shipped library has the entries
+                lib = _lib.lib()
+                joint = _joint_entries(lib)
+            if joint is None:
+                raise RuntimeError("minmax_ocflow_train: the HIP library does not export nocf_rollout_bwd_small_w_f32 / _mid_w_f32 / _act_w_f32; "
+                                   "rebuild it")
+            ctx.lamW = torch.empty(int(nt), n, d, device=dev)
+            lamW = (_lib.ptr(ctx.lamW),)
+        f_small, f_mid, f_act = joint if want_w else (lib.nocf_rollout_bwd_small_f32, getattr(lib, "nocf_rollout_bwd_mid_f32", None),
+                                                      lib.nocf_rollout_bwd_act_f32)
         # small networks: the lane-style adjoint accumulates every gradient row in registers (one vector per sample)
         P = int(lib.nocf_small_grad_floats(d, m))
         gpart = torch.empty(n, P, device=dev) if (net.nTh == 2 and m <= 32 and D1 <= 32) else None
         if gpart is not None:
             with torch.cuda.device(dev):
-                rc = lib.nocf_rollout_bwd_small_f32(C.byref(phi_st), C.byref(prob_st), n, int(nt), _STEPPERS[ctx.stepper],
-                                                    float(ctx.tspan[1]), alph_c, 1.0 / float(ctx.n_total), _lib.ptr(s_all),
-                                                    _lib.ptr(z_out), _lib.ptr(hs), _lib.ptr(gpart), _lib.ptr(lam0),
-                                                    _lib.stream_ptr(dev))
+                rc = f_small(C.byref(phi_st), C.byref(prob_st), n, int(nt), _STEPPERS[ctx.stepper],
+                             float(ctx.tspan[1]), alph_c, 1.0 / float(ctx.n_total), _lib.ptr(s_all),
+                             _lib.ptr(z_out), _lib.ptr(hs), _lib.ptr(gpart), _lib.ptr(lam0), *lamW,
+                             _lib.stream_ptr(dev))
             if rc == 0:
                 return _OCflowTrain._finish(ctx, gJ, _unpack_partials(gpart, m, D1, net), lam0, net)
             if rc != -2:                                               # NOCF_E_SHAPE: not a lane-kernel shape -> row streams below
@@ -271,11 +286,11 @@ class _OCflowTrain(torch.autograd.Function):
         if mid_rows:
             gmid = torch.empty(mid_rows, P, device=dev)
             with torch.cuda.device(dev):
-                rc = lib.nocf_rollout_bwd_mid_f32(C.byref(phi_st), C.byref(prob_st), n, int(nt), _STEPPERS[ctx.stepper],
-                                                  float(ctx.tspan[1]), alph_c, 1.0 / float(ctx.n_total), _lib.ptr(s_all),
-                                                  _lib.ptr(z_out), _lib.ptr(hs), _lib.ptr(getattr(ctx, "act", None)), _lib.ptr(gmid), mid_rows,
-                                                  _lib.ptr(lam0),
-                                                  _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+                rc = f_mid(C.byref(phi_st), C.byref(prob_st), n, int(nt), _STEPPERS[ctx.stepper],
+                           float(ctx.tspan[1]), alph_c, 1.0 / float(ctx.n_total), _lib.ptr(s_all),
+                           _lib.ptr(z_out), _lib.ptr(hs), _lib.ptr(getattr(ctx, "act", None)), _lib.ptr(gmid), mid_rows,
+                           _lib.ptr(lam0), *lamW,
+                           _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
             if rc == 0:
                 ctx.act = None
                 return _OCflowTrain._finish(ctx, gJ, _unpack_partials(gmid, m, D1, net), lam0, net)
@@ -292,14 +307,13 @@ class _OCflowTrain(torch.autograd.Function):
             t[:, rows - n:].zero_()
         PHIb = torch.zeros(n, device=dev)
         with torch.cuda.device(dev):
-            rc = _lib.lib_for(net.d, net.m, net.nTh, phi_st.r, prob_st.n_agents).nocf_rollout_bwd_act_f32(
-                                                 C.byref(phi_st), C.byref(prob_st), n, int(nt), _STEPPERS[ctx.stepper],
-                                                 float(ctx.tspan[1]), alph_c, 1.0 / float(ctx.n_total),
-                                                 _lib.ptr(s_all), _lib.ptr(z_out), _lib.ptr(hs),
-                                                 _lib.ptr(Y), _lib.ptr(Ob), _lib.ptr(V), _lib.ptr(Ab), _lib.ptr(Qb),
-                                                 _lib.ptr(U0), _lib.ptr(Wb), _lib.ptr(Gb), _lib.ptr(Sx),
-                                                 _lib.ptr(PHIb), _lib.ptr(lam0), _lib.ptr(getattr(ctx, "act", None)),
-                                                 _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+            rc = f_act(C.byref(phi_st), C.byref(prob_st), n, int(nt), _STEPPERS[ctx.stepper],
+                       float(ctx.tspan[1]), alph_c, 1.0 / float(ctx.n_total),
+                       _lib.ptr(s_all), _lib.ptr(z_out), _lib.ptr(hs),
+                       _lib.ptr(Y), _lib.ptr(Ob), _lib.ptr(V), _lib.ptr(Ab), _lib.ptr(Qb),
+                       _lib.ptr(U0), _lib.ptr(Wb), _lib.ptr(Gb), _lib.ptr(Sx),
+                       _lib.ptr(PHIb), _lib.ptr(lam0), *lamW, _lib.ptr(getattr(ctx, "act", None)),
+                       _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
         _lib.check(rc, "nocf_rollout_bwd_act_f32")
         ctx.act = None
         sT = Sx[(nt * nstage + 1) * n:]                                     # s at the final time (value rows)
@@ -403,7 +417,12 @@ class _OCflowTrain(torch.autograd.Function):
             from .distributed import allreduce_flat
             out = allreduce_flat(out, None if ctx.group is True else ctx.group)   # one all-reduce of all gradients
         gx = gJ * lam0 if lam0 is not None else None
-        return (gx,) + (None,) * getattr(ctx, "n_plain_args", 8) + tuple(out)
+        plain = (None,) * getattr(ctx, "n_plain_args", 8)
+        lamW = getattr(ctx, "lamW", None)
+        if lamW is not None:                                       # (the joint adjoint: W is the last plain argument; the shard's own rows, not reduced)
+            ctx.lamW = None
+            plain = plain[:-1] + (gJ * lamW,)
+        return (gx,) + plain + tuple(out)
 
 
 class _OCflowTrainDisturbed(torch.autograd.Function):
@@ -471,6 +490,29 @@ _DISTURBED_ARGTYPES = [C.POINTER(_lib.NocfPhi), C.POINTER(_lib.NocfProb), C.c_vo
                        C.c_double, C.c_double, C.c_int32, C.c_int32, _lib.fp,
                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
                        C.c_void_p, C.c_size_t, C.c_void_p]
+
+
+_JOINT_HEAD = [C.POINTER(_lib.NocfPhi), C.POINTER(_lib.NocfProb), C.c_int64, C.c_int32, C.c_int32, C.c_double,
+               _lib.fp, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+_JOINT_ARGTYPES = {"nocf_rollout_bwd_small_w_f32": _JOINT_HEAD + [C.c_void_p] * 4,
+                   "nocf_rollout_bwd_mid_w_f32": _JOINT_HEAD + [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                                C.c_void_p, C.c_size_t, C.c_void_p],
+                   "nocf_rollout_bwd_act_w_f32": _JOINT_HEAD + [C.c_void_p] * 13 + [C.c_void_p, C.c_size_t, C.c_void_p]}
+
+
+def _joint_entries(L):
+    """(nocf_rollout_bwd_small_w_f32, nocf_rollout_bwd_mid_w_f32, nocf_rollout_bwd_act_w_f32) of library L with their prototypes set --
+    the existing adjoint entries with `float* lamW` behind lam0 --, or None when L lacks one of them"""
+    out = []
+    for name, argtypes in _JOINT_ARGTYPES.items():
+        if not hasattr(L, name):
+            return None
+        f = getattr(L, name)
+        if f.argtypes is None:
+            f.restype = C.c_int
+            f.argtypes = argtypes
+        out.append(f)
+    return tuple(out)
 
 
 def _disturbed_entry(L):

@@ -16,7 +16,13 @@ N GPUs:    python -m torch.distributed.run --nnodes=1 --nproc-per-node N --maste
 (seed = noise_seed << 32 | iteration, row = the sample's global row), so the run does not depend on the number of ranks.
 --noise SIGMA [--noise_seed S] (addition): the training rollouts run under per-step Brownian state disturbances sigma dB
 (neuraloc_amd.disturbed_ocflow_train), a fresh W every iteration; validation and its logged costs stay undisturbed.
-SIGMA = 0 (default) is the run without the flag."""
+SIGMA = 0 (default) is the run without the flag.
+--adv EPS [--adv_mode free|pgd] [--adv_steps K] [--adv_objective Jc|control] (addition): min-max training against the worst per-step state
+disturbance in the ball ||W_i||_2 <= EPS over every start's [nt, d] path.  free (default): one W per rank persists
+across the iterations on a batch -- zero at the start and whenever the batch is resampled -- and takes one projected ascent step of length
+2.5 EPS / K per Adam step, from the same backward that gives the parameter gradients (neuraloc_amd.adversarial_step).  pgd: every iteration
+runs a K-step search from zero first (neuraloc_amd.pgd_ocflow_train), on the training loss (Jc) or on L + alph0 G (control).  Validation stays
+undisturbed.  EPS = 0 (default) is the run without the flag."""
 import argparse
 import datetime
 import os
@@ -62,8 +68,15 @@ _FLAGS = [
     ("noise_seed", int, 0, "(addition) seed of the disturbances for --noise (rank is added)"),
     ("noise_rng", str, "torch", "(addition) torch: every rank draws its shard's disturbances with torch.randn; counter: they are drawn inside "
                                 "the kernels from (noise_seed, iteration, global row) (neuraloc_amd.noisy_ocflow_train), the same on any number of ranks"),
+    ("adv", float, 0.0, "(addition) EPS > 0: min-max training against the worst disturbance path of norm <= EPS per start "
+                        "(neuraloc_amd.adversarial_step / pgd_ocflow_train); validation stays undisturbed; single precision only; not with --noise"),
+    ("adv_mode", str, "free", "(addition) free: one persistent W per rank, one ascent step per Adam step from the joint adjoint; "
+                              "pgd: a K-step search from zero in front of every iteration"),
+    ("adv_steps", int, 4, "(addition) K: free mode takes ascent steps of length 2.5 EPS / K; pgd mode runs K inner steps"),
+    ("adv_objective", str, "Jc", "(addition, pgd only) what the adversary climbs: Jc (the training loss) or control (L + alph0 G)"),
 ]
-_CHOICES = {"data": PROBLEM_NAMES, "optim": ["adam"], "prec": ["single", "double"], "approach": ["ocflow"], "noise_rng": ["torch", "counter"]}
+_CHOICES = {"data": PROBLEM_NAMES, "optim": ["adam"], "prec": ["single", "double"], "approach": ["ocflow"], "noise_rng": ["torch", "counter"],
+            "adv_mode": ["free", "pgd"], "adv_objective": ["Jc", "control"]}
 
 
 def parse_args(argv=None):
@@ -87,6 +100,16 @@ def main(argv=None):
         raise SystemExit("--noise_rng counter runs in single precision only (the double-precision rollout takes no disturbance)")
     if args.noise_rng == "counter" and not 0 <= args.noise_seed < 2 ** 32:
         raise SystemExit("--noise_rng counter needs 0 <= --noise_seed < 2**32 (the iteration takes the seed's low word)")
+    if not args.adv >= 0 or args.adv == float("inf"):
+        raise SystemExit("--adv EPS must be a finite number >= 0")
+    if args.adv > 0 and args.prec == "double":
+        raise SystemExit("--adv runs in single precision only (the double-precision rollout takes no disturbance)")
+    if args.adv > 0 and args.noise > 0:
+        raise SystemExit("--adv and --noise exclude each other: one disturbance per rollout")
+    if args.adv > 0 and args.adv_steps < 1:
+        raise SystemExit("--adv_steps K must be >= 1")
+    if args.adv > 0 and args.adv_mode == "free" and args.adv_objective == "control":
+        raise SystemExit("--adv_objective control needs --adv_mode pgd: the free adversary climbs the training loss itself")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     if world > 1:
@@ -140,6 +163,8 @@ def main(argv=None):
     # --noise_rng counter: nothing is drawn -- the kernels form the disturbance of (iteration, global row, step, component) themselves
     noise_counter = args.noise > 0 and args.noise_rng == "counter"
     noise_gen = torch.Generator(device=dev).manual_seed(args.noise_seed + rank) if args.noise > 0 and not noise_counter else None
+    # --adv, free mode: one W per rank, kept across the iterations on a batch (zeroed with every new batch)
+    adv_W = torch.zeros(args.nt, x0.shape[0], d, device=dev, requires_grad=True) if args.adv > 0 and args.adv_mode == "free" else None
     best_loss, best_params, total = float("inf"), None, 0.0
     net.train()
     prob.train()
@@ -152,9 +177,16 @@ def main(argv=None):
         elif noise_gen is not None:
             W = na.brownian_disturbances(args.nt, x0.shape[0], d, args.noise, tspan=tspan, generator=noise_gen, device=dev)
             Jc, cs = na.disturbed_ocflow_train(x0, net, prob, tspan, args.nt, W, "rk4", net.alph, group=True if dist else None)
+        elif adv_W is not None:
+            Jc, cs = na.adversarial_step(x0, net, prob, tspan, args.nt, adv_W, args.adv, 2.5 * args.adv / args.adv_steps, stepper="rk4",
+                                         alph=net.alph, group=True if dist else None)
+        elif args.adv > 0:
+            Jc, cs, _ = na.pgd_ocflow_train(x0, net, prob, tspan, args.nt, args.adv, args.adv_steps, objective=args.adv_objective,
+                                            stepper="rk4", alph=net.alph, group=True if dist else None)
         else:
             Jc, cs = rollout(x0, net, prob, tspan, args.nt, "rk4", net.alph)
-        Jc.backward()
+        if adv_W is None:                                 # (adversarial_step has run the backward: both gradients come from one adjoint)
+            Jc.backward()
         torch.cuda.synchronize()
         na.check_errors()                                 # (after the synchronisation and BEFORE the step: a timed-out rollout raises, its NaN gradients are not applied)
         optim.step()
@@ -190,6 +222,9 @@ def main(argv=None):
                 g["lr"] *= args.lr_decay
         if itr % args.sample_freq == 0:
             x0 = resample(x0, xInit, args.var0, cvt)
+            if adv_W is not None:
+                with torch.no_grad():
+                    adv_W.zero_()
         if itr == n_change:
             # like trainOC.py:258-263: the problem is rebuilt with the new Q/W weights; net.alph (what OCflow gets) stays
             alph = args.new_alph[1:]
