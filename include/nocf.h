@@ -444,6 +444,39 @@ int nocf_rollout_bwd_small_f32(const NocfPhi* phi, const NocfProb* prob, int64_t
                                float* gpart, float* lam0, void* stream);
 
 /*
+ * Ensembles: E = `members` small networks of ONE shape rolled out (and differentiated) in one launch each, on the lane kernels of
+ * nocf_rollout_f32 / nocf_rollout_bwd_small_f32 (nTh = 2, m <= 32, d+1 <= 32, point agents, at most 16 of them; the adjoint: Cross2D
+ * agents).  One wavefront integrates one sample, so the launch is one batch of E * n rows: row g is sample g % n of member g / n, a
+ * workgroup may hold rows of two members, and member e's rows carry the bits of the single-network call on that member alone.
+ *   phi        the STACKED network: K0 [E, m, d+1], b0 [E, m], K [E, m, m], b [E, m], w [E, m], A [E, r, d+1], cw [E, d+1], cb_dev [E]
+ *              (contiguous: member e's tensor begins e tensor sizes behind the base; cb_dev is required, cb is not read)
+ *   n          rows of ONE member;  members >= 1;  members * n < 2^31
+ *   x          device [n, d] with x_member_stride = 0 (every member integrates the same starts) or [E, n, d] with x_member_stride = n * d
+ *   alph       DEVICE [E, 6], float32: row e stands for the `alph` of the single-network calls ([0], [3], [4], [5]) AND for the problem's
+ *              alph_Q ([1]) and alph_W ([2]) of member e; prob->alph_Q / alph_W are not read.  Everything else of `prob` (target, obstacle,
+ *              r, mode) and t0, t1, nt, stepper are common to the members
+ *   z_out [E*n, d+4], persample [E*n, 7], s_all [nt*nstage, E*n, d+1], zFull [nt+1, E*n, d+4], ctrlFull [nt+1, E*n, a]: the single-network
+ *              layouts over E*n rows (time-major where they are);  gpart [E*n, nocf_small_grad_floats], lam0 [E*n, d]: member e's
+ *              per-sample partials are rows [e n, (e + 1) n), the caller sums each member's rows;  inv_n: 1 / n of a member
+ *   cost_sums  device [E, 8], cost_means device [E, 8] (nullable; needs cost_sums): per member what nocf_rollout_means_f32 returns, reduced
+ *              in its order by one launch with the member on the grid
+ *   workspace  not used (the lane kernels need none): may be NULL / 0
+ * Any other shape, a quadcopter, members < 1 or NOCF_LANE=0 return NOCF_E_SHAPE / NOCF_E_PROB before anything is enqueued: no other
+ * kernel family takes an ensemble.  nocf_last_rollout_kernel(): "rollout_lane_kernel<ens>" / "rollout_lane_bwd_kernel<ens>".
+ */
+int nocf_rollout_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members, int64_t x_member_stride,
+                              double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                              float* z_out, float* persample, float* cost_sums, float* cost_means, float* zFull, float* ctrlFull,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int nocf_rollout_record_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members, int64_t x_member_stride,
+                                     double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                     float* z_out, float* persample, float* cost_sums, float* s_all,
+                                     void* workspace, size_t workspace_bytes, void* stream);
+int nocf_rollout_bwd_small_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper, double t1,
+                                        const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
+                                        float* gpart, float* lam0, void* stream);
+
+/*
  * The same adjoint for MEDIUM two-layer networks (nTh = 2, 32 < m <= 128, d+1 <= 32, every problem class: the shapes the one-CU
  * weight-stationary kernel of nocf_rollout_f32 takes, e.g. singlequad; reference: trainOC.py:172-174 on src/OCflow.py:7-140).  One
  * workgroup per 16 samples keeps the network in its registers, takes grad Phi's activations from the forward's activation record

@@ -14,6 +14,7 @@ from .train import disturbed_ocflow_train
 from .adversary import disturbance_gradient, worst_case_disturbances
 from .noise import counter_disturbances, noisy_rollout, noisy_ocflow_train
 from .minmax import minmax_ocflow_train, ascend_disturbances, adversarial_step, pgd_ocflow_train
+from .ensemble import PhiEnsemble, ensemble_rollout, ensemble_ocflow_train
 
 __all__ = ["Phi", "ResNN", "antiderivTanh", "derivTanh", "OCflow", "ocG", "Cross2D", "SwarmTraj",
            "Quadcopter", "initProb", "resample", "OCflow_sharded", "shard_rows", "reduce_cost_sums", "check_errors",
@@ -21,4 +22,5 @@ __all__ = ["Phi", "ResNN", "antiderivTanh", "derivTanh", "OCflow", "ocG", "Cross
            "quad_baseline_loss", "quad_baseline_report", "quad_initial_guess", "solve_baseline_quad",
            "disturbed_rollout", "brownian_disturbances", "noise_study", "disturbed_ocflow_train",
            "disturbance_gradient", "worst_case_disturbances",
-           "minmax_ocflow_train", "ascend_disturbances", "adversarial_step", "pgd_ocflow_train"]
+           "minmax_ocflow_train", "ascend_disturbances", "adversarial_step", "pgd_ocflow_train",
+           "PhiEnsemble", "ensemble_rollout", "ensemble_ocflow_train"]

@@ -1431,6 +1431,16 @@ __global__ void __launch_bounds__(256) cost_sum_kernel(float* __restrict__ tab, 
     cost_sum_body(sh, tab, n, out, err, ma);
 }
 
+// an ensemble's sums (nocf_rollout_ensemble_f32): workgroup e runs cost_sum_body on member e's slice of the table with member e's row of the
+// multiplier table -- the arithmetic and the order of cost_sum_kernel on that member alone, so the same bits; one launch for all members
+__global__ void __launch_bounds__(256) cost_sum_ens_kernel(float* __restrict__ tab, long n, float* __restrict__ out, float* __restrict__ means,
+                                                           const float* __restrict__ alph) {
+    __shared__ double sh[256 * 7];
+    const long e = blockIdx.x;
+    const float* at = alph + e * 6;
+    cost_sum_body(sh, tab + e * n * 7, n, out + e * 8, nullptr, MeanArgs{means ? means + e * 8 : nullptr, at[0], at[3], at[4], at[5]});
+}
+
 // means of the 7 cost terms and Jc from the 8 sums, one launch instead of a dozen tiny elementwise ones
 __global__ void cost_means_kernel(const float* __restrict__ sums, float a0, float a3, float a4, float a5, float* __restrict__ out) {
     const int i = threadIdx.x;
@@ -1848,9 +1858,9 @@ static int bwd_small_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n, i
     const int MPsel = phi->m <= 16 ? 16 : 32;
     const int DPsel = phi->d + 1 <= 8 ? 8 : (phi->d + 1 <= 16 ? 16 : 32);
     if (env_int("NOCF_DEBUG", 0)) fprintf(stderr, "[nocf] lane adjoint kernel\n");
-#define NOCF_LANEB_LAUNCH(MPV, DPV) do { if (mode == 1) hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV, 1>), dim3(grid), dim3(256), 0, st, la, pb); \
-                                          else if (mode == 2) hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV, 2>), dim3(grid), dim3(256), 0, st, la, pb); \
-                                          else hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV>), dim3(grid), dim3(256), 0, st, la, pb); } while (0)
+#define NOCF_LANEB_LAUNCH(MPV, DPV) do { if (mode == 1) hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV, 1>), dim3(grid), dim3(256), 0, st, la, pb, EnsArgs{}); \
+                                          else if (mode == 2) hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV, 2>), dim3(grid), dim3(256), 0, st, la, pb, EnsArgs{}); \
+                                          else hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV>), dim3(grid), dim3(256), 0, st, la, pb, EnsArgs{}); } while (0)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (g_prof_on) {
         if (hipEventCreate(&ev0) || hipEventCreate(&ev1)) return (int)hipErrorUnknown;
@@ -1875,6 +1885,129 @@ int nocf_rollout_bwd_small_w_f32(const NocfPhi* phi, const NocfProb* prob, int64
                                  const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
                                  float* gpart, float* lam0, float* lamW, void* stream) {
     return bwd_small_impl(phi, prob, n, nt, stepper, t1, alph, inv_n, s_all, z_final, hs, gpart, lam0, lamW, lamW ? 2 : 0, stream);
+}
+
+// ---- ensembles on the lane kernels (include/nocf.h): E networks of one shape, one launch.  The lane family or nothing: every other shape is
+// refused before anything is enqueued
+static int ensemble_check(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper, bool adjoint,
+                          DevProb* pb) {
+    int rc = check_phi(phi);
+    if (rc) return rc;
+    if (!phi->cb_dev) return NOCF_E_NULL;                  // (c.bias [E] is read on the device: there is no host value per member)
+    if (n < 1 || nt < 1 || members < 1 || (int64_t)members * n > 0x7fffffffl) return NOCF_E_SHAPE;
+    if (stepper != NOCF_RK4 && stepper != NOCF_RK1) return NOCF_E_STEPPER;
+    rc = fill_prob(prob, phi->d, pb);
+    if (rc) return rc;
+    if (phi->r < 1 || phi->r > phi->d + 1 || phi->r > ZQLD) return NOCF_E_SHAPE;
+    if (!(phi->nTh == 2 && phi->m >= 1 && phi->m <= 32 && phi->d + 1 <= 32 && pb->kind != NOCF_PROB_QUADCOPTER && pb->nAgents <= 16 &&
+          env_int("NOCF_LANE", 1) != 0))
+        return NOCF_E_SHAPE;
+    if (adjoint && !(pb->kind == NOCF_PROB_CROSS2D && pb->agentDim == 2 && pb->nAgents * 2 == phi->d)) return NOCF_E_SHAPE;
+    return 0;
+}
+
+static int rollout_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members, int64_t x_member_stride,
+                                 double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                 float* z_out, float* persample, float* cost_sums, float* cost_means, float* zFull, float* ctrlFull,
+                                 float* s_all, void* stream) {
+    DevProb pb;
+    const int rc = ensemble_check(phi, prob, n, members, nt, stepper, false, &pb);
+    if (rc) return rc;
+    if (!x || !alph) return NOCF_E_NULL;
+    if ((zFull != nullptr) != (ctrlFull != nullptr)) return NOCF_E_NULL;
+    if ((cost_sums && !persample) || (cost_means && !cost_sums)) return NOCF_E_NULL;
+    if (x_member_stride != 0 && x_member_stride != n * phi->d) return NOCF_E_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    const long rows = (long)members * n;
+    RollArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    ra.x = x; ra.n = rows; ra.t0 = t0; ra.t1 = t1; ra.h = (t1 - t0) / nt; ra.nt = nt; ra.stepper = stepper;
+    ra.z_out = z_out; ra.persample = persample; ra.zFull = zFull; ra.ctrlFull = ctrlFull;
+    ra.cdim = nocf_ctrl_dim(prob, phi->d);
+    ra.sAll = s_all;
+    LaneArgs la;
+    memset(&la, 0, sizeof(la));
+    la.P = DevPhi{phi->K0, phi->b0, phi->K, phi->b, phi->w, phi->A, phi->cw, phi->cb_dev};
+    la.d = phi->d; la.m = phi->m; la.r = phi->r; la.nAg = pb.nAgents;
+    const EnsArgs ea{(unsigned)n, (long)x_member_stride, alph};
+    const int grid = (int)((rows + 3) / 4);
+    const int MPsel = phi->m <= 16 ? 16 : 32;
+    const int DPsel = phi->d + 1 <= 8 ? 8 : (phi->d + 1 <= 16 ? 16 : 32);
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    if (g_prof_on) {
+        if (hipEventCreate(&ev0) || hipEventCreate(&ev1)) return (int)hipErrorUnknown;
+        (void)hipEventRecord(ev0, st);
+    }
+#define NOCF_LANE_ENS_LAUNCH(MPV, DPV) do { if (s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 0, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea); \
+                                             else hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 0, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea); } while (0)
+    if (MPsel == 16) { if (DPsel == 8) { NOCF_LANE_ENS_LAUNCH(16, 8); } else if (DPsel == 16) { NOCF_LANE_ENS_LAUNCH(16, 16); } else { NOCF_LANE_ENS_LAUNCH(16, 32); } }
+    else             { if (DPsel == 8) { NOCF_LANE_ENS_LAUNCH(32, 8); } else if (DPsel == 16) { NOCF_LANE_ENS_LAUNCH(32, 16); } else { NOCF_LANE_ENS_LAUNCH(32, 32); } }
+#undef NOCF_LANE_ENS_LAUNCH
+    hipError_t e = hipGetLastError();
+    if (e) return (int)e;
+    g_last_kernel = "rollout_lane_kernel<ens>";
+    g_last_errp = nullptr;
+    if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
+    if (cost_sums) {
+        hipLaunchKernelGGL(cost_sum_ens_kernel, dim3(members), dim3(256), 0, st, persample, (long)n, cost_sums, cost_means, alph);
+        e = hipGetLastError();
+        if (e) return (int)e;
+    }
+    return 0;
+}
+
+int nocf_rollout_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members, int64_t x_member_stride,
+                              double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                              float* z_out, float* persample, float* cost_sums, float* cost_means, float* zFull, float* ctrlFull,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+    (void)workspace; (void)workspace_bytes;               // (the lane kernels use no workspace)
+    return rollout_ensemble_impl(phi, prob, x, n, members, x_member_stride, t0, t1, nt, stepper, alph, z_out, persample, cost_sums, cost_means,
+                                 zFull, ctrlFull, nullptr, stream);
+}
+
+int nocf_rollout_record_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members, int64_t x_member_stride,
+                                     double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                     float* z_out, float* persample, float* cost_sums, float* s_all,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+    (void)workspace; (void)workspace_bytes;
+    if (!s_all || !z_out) return NOCF_E_NULL;
+    return rollout_ensemble_impl(phi, prob, x, n, members, x_member_stride, t0, t1, nt, stepper, alph, z_out, persample, cost_sums, nullptr,
+                                 nullptr, nullptr, s_all, stream);
+}
+
+int nocf_rollout_bwd_small_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper, double t1,
+                                        const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
+                                        float* gpart, float* lam0, void* stream) {
+    DevProb pb;
+    const int rc = ensemble_check(phi, prob, n, members, nt, stepper, true, &pb);
+    if (rc) return rc;
+    if (!alph || !s_all || !z_final || !hs || !gpart) return NOCF_E_NULL;
+    const long rows = (long)members * n;
+    LaneBwdArgs la;
+    memset(&la, 0, sizeof(la));
+    la.P = DevPhi{phi->K0, phi->b0, phi->K, phi->b, phi->w, phi->A, phi->cw, phi->cb_dev};
+    la.d = phi->d; la.m = phi->m; la.r = phi->r; la.nAg = pb.nAgents;
+    la.sAll = s_all; la.zT = z_final; la.hs = hs; la.n = rows; la.nt = nt; la.nstage = (stepper == NOCF_RK4) ? 4 : 1;
+    la.t1 = (float)t1; la.inv_n = (float)inv_n;
+    la.gpart = gpart; la.P_total = nocf_small_grad_floats(phi->d, phi->m); la.lam0 = lam0; la.lamW = nullptr;
+    const EnsArgs ea{(unsigned)n, 0l, alph};
+    hipStream_t st = (hipStream_t)stream;
+    const int grid = (int)((rows + 3) / 4);
+    const int MPsel = phi->m <= 16 ? 16 : 32;
+    const int DPsel = phi->d + 1 <= 8 ? 8 : (phi->d + 1 <= 16 ? 16 : 32);
+#define NOCF_LANEB_ENS_LAUNCH(MPV, DPV) hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV, 0, true>), dim3(grid), dim3(256), 0, st, la, pb, ea)
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    if (g_prof_on) {
+        if (hipEventCreate(&ev0) || hipEventCreate(&ev1)) return (int)hipErrorUnknown;
+        (void)hipEventRecord(ev0, st);
+    }
+    if (MPsel == 16) { if (DPsel == 8) { NOCF_LANEB_ENS_LAUNCH(16, 8); } else if (DPsel == 16) { NOCF_LANEB_ENS_LAUNCH(16, 16); } else { NOCF_LANEB_ENS_LAUNCH(16, 32); } }
+    else             { if (DPsel == 8) { NOCF_LANEB_ENS_LAUNCH(32, 8); } else if (DPsel == 16) { NOCF_LANEB_ENS_LAUNCH(32, 16); } else { NOCF_LANEB_ENS_LAUNCH(32, 32); } }
+#undef NOCF_LANEB_ENS_LAUNCH
+    if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
+    g_last_kernel = "rollout_lane_bwd_kernel<ens>";
+    g_last_errp = nullptr;
+    return (int)hipGetLastError();
 }
 
 int nocf_contract_f32(const float* A, const float* B, int64_t K, int32_t m, int32_t n, float* C, int32_t accumulate,
@@ -2102,13 +2235,13 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
             (void)hipEventRecord(ev0, st);
         }
         const size_t laneLds = ticket ? (size_t)(256 * 7 * 8 + 16) : 0;      // (the last-workgroup reduction's scratch: only with a ticket)
-#define NOCF_LANE_LAUNCH(MPV, DPV) do { if (dmode == 2 && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 2>), dim3(grid), dim3(256), 0, st, la, pb, ra); \
-                                         else if (dmode == 2) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 2>), dim3(grid), dim3(256), 0, st, la, pb, ra); \
-                                         else if (dist && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 1>), dim3(grid), dim3(256), 0, st, la, pb, ra); \
-                                         else if (dist) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 1>), dim3(grid), dim3(256), 0, st, la, pb, ra); \
-                                         else if (s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true>), dim3(grid), dim3(256), 0, st, la, pb, ra); \
-                                         else if (ticket) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, true>), dim3(grid), dim3(256), laneLds, st, la, pb, ra); \
-                                         else hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false>), dim3(grid), dim3(256), 0, st, la, pb, ra); } while (0)
+#define NOCF_LANE_LAUNCH(MPV, DPV) do { if (dmode == 2 && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 2>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}); \
+                                         else if (dmode == 2) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 2>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}); \
+                                         else if (dist && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 1>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}); \
+                                         else if (dist) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 1>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}); \
+                                         else if (s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}); \
+                                         else if (ticket) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, true>), dim3(grid), dim3(256), laneLds, st, la, pb, ra, EnsArgs{}); \
+                                         else hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}); } while (0)
         if (MPsel == 16) { if (DPsel == 8) { NOCF_LANE_LAUNCH(16, 8); } else if (DPsel == 16) { NOCF_LANE_LAUNCH(16, 16); } else { NOCF_LANE_LAUNCH(16, 32); } }
         else             { if (DPsel == 8) { NOCF_LANE_LAUNCH(32, 8); } else if (DPsel == 16) { NOCF_LANE_LAUNCH(32, 16); } else { NOCF_LANE_LAUNCH(32, 32); } }
 #undef NOCF_LANE_LAUNCH

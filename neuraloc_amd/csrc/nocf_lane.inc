@@ -26,6 +26,12 @@ struct LaneArgs {
     float a0, a3, a4, a5;
 };
 
+// ENS instantiations only (include/nocf.h, nocf_rollout_ensemble_f32; the adjoint: nocf_lane_bwd.inc): the batch is E * n rows, row g is sample
+// g % n of member g / n; DevPhi then holds the STACKED tensors ([E, ...], contiguous: member e's tensor begins e tensor sizes behind the base),
+// xs is the member stride of x in floats (0: every member integrates the same starts) and alph the device table [E, 6] of the multipliers.
+// The LAST kernel argument, behind the existing ones: their offsets, and with them every existing instantiation's instructions, stay as they are
+struct EnsArgs { unsigned n; long xs; const float* alph; };
+
 // REC: the training variant also stores every stage input (RollArgs::sAll); the evaluation variant carries no trace of it
 // ONE: the instantiation WITH the last-workgroup reduction (NOCF_LANE_ONE=1, evaluation only).  Its own instantiation because the reduction's code
 // at the kernel's end costs the register-resident rollout in front of it 5-7 % (swap2 0.084 -> 0.090 ms) even when it is never taken
@@ -34,35 +40,56 @@ struct LaneArgs {
 // recording forward of disturbed training): the next step's first stage input is formed from the displaced z, so it is recorded displaced
 // DIST == 2: the same with the entry drawn here (nocf_noise.inc: RollArgs::nzScale / nzSeed / nzRow0) where DIST == 1 loads it -- into the same
 // register, at the top of the step, so every instruction behind it is shared.  Tail waves draw the noise of the row they replicate
-template <int MP, int DP, bool REC, bool ONE = false, int DIST = 0>
-__global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb pb, RollArgs ra) {
+// ENS: an ensemble of E networks of one shape in one launch (DIST = 0, ONE = false).  A wave is a whole sample and nothing in a workgroup is
+// shared, so the only change is WHICH network, multipliers and start a wave reads: the member e = row / ensN is wave-uniform and is kept, with
+// the member's eight tensor pointers and its row of the multiplier table, in scalar registers; every statement of the rollout behind these
+// reads is the single-network one, so member e's rows carry the bits of the single-network call on that member.  Every ENS test is
+// `if constexpr`: the other instantiations carry no trace of it
+template <int MP, int DP, bool REC, bool ONE = false, int DIST = 0, bool ENS = false>
+__global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb pb, RollArgs ra, EnsArgs ea) {
     const int lane = threadIdx.x & 63;
     const long sample = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const bool live = sample < ra.n;
     const long row = live ? sample : ra.n - 1;
     const int d = la.d, D1 = d + 1, m = la.m, N = la.nAg, ad = pb.agentDim;
+    DevPhi P = la.P;
+    const float* xrow = ra.x;                           // (ENS: the member's block of starts, indexed by the row inside the member)
+    long xr = row;
+    float eA0 = 0.f, eAQ = 0.f, eAW = 0.f;              // ENS: the member's alph[0], alph_Q, alph_W
+    if constexpr (ENS) {
+        const unsigned e = (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)row / ea.n));
+        P.K0 += (long)e * m * D1; P.b0 += (long)e * m; P.K += (long)e * m * m; P.b += (long)e * m; P.w += (long)e * m;
+        P.A += (long)e * la.r * D1; P.cw += (long)e * D1; P.cbp += e;
+        xrow += (long)e * ea.xs; xr = row - (long)e * ea.n;
+        const float* at = ea.alph + (long)e * 6;
+        eA0 = at[0]; eAQ = at[1]; eAW = at[2];
+    }
+    // the multipliers and the decisions they take: the problem's (one network), the member's (ENS) -- wave-uniform either way
+    auto wantWp = [&]() -> bool { if constexpr (ENS) return eAW != 0.f; else return want_W(pb); };
+    auto posQ = [&]() -> bool { if constexpr (ENS) return eAQ > 0.f; else return pb.alphQ > 0.0; };
+    auto alph0 = [&]() -> float { if constexpr (ENS) return eA0; else return ra.a0; };
 
     // ---- weights: my row and my column of every matrix, for the whole rollout
     float k0row[DP], symA[DP], k1row[MP], k1col[MP], k0col[MP];
 #pragma unroll
-    for (int i = 0; i < DP; ++i) k0row[i] = (lane < m && i < D1) ? la.P.K0[lane * D1 + i] : 0.f;
+    for (int i = 0; i < DP; ++i) k0row[i] = (lane < m && i < D1) ? P.K0[lane * D1 + i] : 0.f;
 #pragma unroll
     for (int k = 0; k < MP; ++k) {
-        k1row[k] = (lane < m && k < m) ? la.P.K[lane * m + k] : 0.f;
-        k1col[k] = (lane < m && k < m) ? la.P.K[k * m + lane] : 0.f;
-        k0col[k] = (lane < D1 && k < m) ? la.P.K0[k * D1 + lane] : 0.f;
+        k1row[k] = (lane < m && k < m) ? P.K[lane * m + k] : 0.f;
+        k1col[k] = (lane < m && k < m) ? P.K[k * m + lane] : 0.f;
+        k0col[k] = (lane < D1 && k < m) ? P.K0[k * D1 + lane] : 0.f;
     }
 #pragma unroll
     for (int j = 0; j < DP; ++j) {                      // symA = A'A like the reference forms it (src/Phi.py:110)
         float a = 0.f;
         if (lane < D1 && j < D1)
-            for (int q = 0; q < la.r; ++q) a += la.P.A[q * D1 + lane] * la.P.A[q * D1 + j];
+            for (int q = 0; q < la.r; ++q) a += P.A[q * D1 + lane] * P.A[q * D1 + j];
         symA[j] = a;
     }
-    const float b0 = lane < m ? la.P.b0[lane] : 0.f;
-    const float b1 = lane < m ? la.P.b[lane] : 0.f;
-    const float wv = lane < m ? la.P.w[lane] : 0.f;
-    const float cw = lane < D1 ? la.P.cw[lane] : 0.f;
+    const float b0 = lane < m ? P.b0[lane] : 0.f;
+    const float b1 = lane < m ? P.b[lane] : 0.f;
+    const float wv = lane < m ? P.w[lane] : 0.f;
+    const float cw = lane < D1 ? P.cw[lane] : 0.f;
     const float xt = lane < d ? pb.xtarget[lane] : 0.f;
     float nzs = 0.f;                                    // this lane's component of sigma sqrt(h)
     if constexpr (DIST == 2) nzs = lane < d ? ra.nzScale[lane] : 0.f;
@@ -78,12 +105,12 @@ __global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb 
         pi_[tr] = (q < npairs) ? i * ad : 0;
         pj_[tr] = (q < npairs) ? (i + 1 + rem) * ad : 0;
     }
-    const bool wantW = want_W(pb) && N >= 2;
+    const bool wantW = wantWp() && N >= 2;
     const float den = (float)(2.0 * pb.r * pb.r);
     const double facN = pb.training ? (N == 2 ? 2.2 : (pb.kind == NOCF_PROB_SWARMTRAJ ? 3.2 : 2.2)) : 2.0;
     const float thr = (float)(facN * pb.r);
     const float thr2 = thr * thr * 1.000002f;
-    const float aQ = (float)pb.alphQ, aW = (float)pb.alphW;
+    const float aQ = ENS ? eAQ : (float)pb.alphQ, aW = ENS ? eAW : (float)pb.alphW;
 
     // grad Phi at s (one component per lane); optionally Phi itself
     auto grad_phi = [&](float s, bool need_value, float& phival) -> float {
@@ -109,7 +136,7 @@ __global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb 
         if (need_value) {
             const float u1 = u0 + sigma_act(q);
             phival = wave_sum(lane < m ? wv * u1 : 0.f) + 0.5f * wave_sum(lane < D1 ? s * sy : 0.f)
-                     + wave_sum(lane < D1 ? cw * s : 0.f) + (la.P.cbp ? *la.P.cbp : la.cb);
+                     + wave_sum(lane < D1 ? cw * s : 0.f) + (P.cbp ? *P.cbp : la.cb);
         }
         return g;
     };
@@ -118,7 +145,7 @@ __global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb 
     auto rhs = [&](float s, float g) -> float {
         const float sp2 = wave_sum(lane < d ? g * g : 0.f);
         float qa = 0.f;
-        if (pb.obstacle != NOCF_OBS_NONE && (pb.kind == NOCF_PROB_CROSS2D || pb.alphQ > 0.0)) {
+        if (pb.obstacle != NOCF_OBS_NONE && (pb.kind == NOCF_PROB_CROSS2D || posQ())) {
             const int a0 = (lane < N ? lane : 0) * ad;
             const float x0 = __shfl(s, a0), x1 = __shfl(s, a0 + 1);
             const float x2 = (ad == 3) ? __shfl(s, a0 + 2) : 0.f;
@@ -149,7 +176,7 @@ __global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb 
         float Lg, Qret;
         if (pb.kind == NOCF_PROB_CROSS2D) { Qret = aQ * Qraw; Lg = 0.5f * sp2 + Qret; }
         else { Qret = Qraw; Lg = 0.5f * sp2 + aQ * Qraw; }
-        if (want_W(pb)) Lg = Lg + aW * Wv;
+        if (wantWp()) Lg = Lg + aW * Wv;
         const float H = -Lg + sp2;
         const float gt = lane_bcast_u(g, d);
         float dz = -g;
@@ -161,7 +188,7 @@ __global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb 
     };
 
     // ---- state: z one component per lane (x | L | HJt | Q | W), s = stage input [x, t]
-    float z = lane < d ? ra.x[row * d + lane] : 0.f;
+    float z = lane < d ? xrow[xr * d + lane] : 0.f;
     if (ra.zFull && live) {
         if (lane < d + 4) ra.zFull[sample * (d + 4) + lane] = z;
         if (lane < d) ra.ctrlFull[sample * ra.cdim + lane] = 0.f;
@@ -225,12 +252,12 @@ __global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb 
         const float g = grad_phi(s, true, phi1);
         const float res = lane < d ? z - xt : 0.f;
         const float cG = 0.5f * wave_sum(res * res);
-        const float hjg = wave_sum(lane < d ? fabsf(g - ra.a0 * res) : 0.f);
+        const float hjg = wave_sum(lane < d ? fabsf(g - alph0() * res) : 0.f);
         const float cL = lane_bcast_u(z, d), cHJt = lane_bcast_u(z, d + 1), cQ = lane_bcast_u(z, d + 2), cW = lane_bcast_u(z, d + 3);
         if (live) {
             if (ra.persample && lane == 0) {
                 float* o = ra.persample + sample * 7;
-                o[0] = cL; o[1] = cG; o[2] = cHJt; o[3] = fabsf(phi1 - ra.a0 * cG); o[4] = hjg; o[5] = cQ; o[6] = cW;
+                o[0] = cL; o[1] = cG; o[2] = cHJt; o[3] = fabsf(phi1 - alph0() * cG); o[4] = hjg; o[5] = cQ; o[6] = cW;
             }
             if (ra.z_out && lane < d + 4) ra.z_out[sample * (d + 4) + lane] = z;
         }

@@ -29,36 +29,51 @@ struct LaneBwdArgs {
 
 __device__ __forceinline__ float sgnf(float v) { return (v > 0.f) ? 1.f : (v < 0.f ? -1.f : 0.f); }
 
-template <int MP, int DP, int STATES = 0>
-__global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, DevProb pb) {
+// ENS (STATES = 0; nocf_rollout_bwd_small_ensemble_f32): the adjoint of an ensemble rollout (nocf_lane.inc), one launch for E networks: la.n =
+// E * ea.n rows, row g belongs to member g / ea.n; la.P holds the stacked tensors; row e of the table ea.alph stands for a0, a3, a4, a5
+// (entries 0, 3, 4, 5) and for the problem's alph_Q / alph_W (1, 2); la.inv_n is 1 / ea.n, the mean over ONE member's samples.  As there: the member of a wave is uniform,
+// its pointers and multipliers sit in scalar registers, every statement behind those reads is the single-network one, and every ENS test is
+// `if constexpr`.  Row g's gradient vector goes to gpart[g]: member e's partials are the contiguous rows [e ea.n, (e + 1) ea.n)
+template <int MP, int DP, int STATES = 0, bool ENS = false>
+__global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, DevProb pb, EnsArgs ea) {
     const int lane = threadIdx.x & 63;
     const long sample = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const bool live = sample < la.n;
     const long row = live ? sample : la.n - 1;
     const int d = la.d, D1 = d + 1, m = la.m, N = la.nAg;
+    DevPhi P = la.P;
+    float eA0 = 0.f, eAQ = 0.f, eAW = 0.f, eA3 = 0.f, eA4 = 0.f, eA5 = 0.f;      // ENS: the member's row of the multiplier table
+    if constexpr (ENS) {
+        const unsigned e = (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)row / ea.n));
+        P.K0 += (long)e * m * D1; P.b0 += (long)e * m; P.K += (long)e * m * m; P.b += (long)e * m; P.w += (long)e * m;
+        P.A += (long)e * la.r * D1; P.cw += (long)e * D1; P.cbp += e;
+        const float* at = ea.alph + (long)e * 6;
+        eA0 = at[0]; eAQ = at[1]; eAW = at[2]; eA3 = at[3]; eA4 = at[4]; eA5 = at[5];
+    }
+    // (below, `ENS ? member's : the call's` is a compile-time choice at the place of use: the other instantiations keep their statements)
 
     // ---- weights: my row and my column of every matrix (as in the forward lane kernel)
     float k0row[DP], symA[DP], k1row[MP], k1col[MP], k0col[MP];
 #pragma unroll
-    for (int i = 0; i < DP; ++i) k0row[i] = (lane < m && i < D1) ? la.P.K0[lane * D1 + i] : 0.f;
+    for (int i = 0; i < DP; ++i) k0row[i] = (lane < m && i < D1) ? P.K0[lane * D1 + i] : 0.f;
 #pragma unroll
     for (int k = 0; k < MP; ++k) {
-        k1row[k] = (lane < m && k < m) ? la.P.K[lane * m + k] : 0.f;
-        k1col[k] = (lane < m && k < m) ? la.P.K[k * m + lane] : 0.f;
-        k0col[k] = (lane < D1 && k < m) ? la.P.K0[k * D1 + lane] : 0.f;
+        k1row[k] = (lane < m && k < m) ? P.K[lane * m + k] : 0.f;
+        k1col[k] = (lane < m && k < m) ? P.K[k * m + lane] : 0.f;
+        k0col[k] = (lane < D1 && k < m) ? P.K0[k * D1 + lane] : 0.f;
     }
 #pragma unroll
     for (int j = 0; j < DP; ++j) {
         float a = 0.f;
         if (lane < D1 && j < D1)
-            for (int q = 0; q < la.r; ++q) a += la.P.A[q * D1 + lane] * la.P.A[q * D1 + j];
+            for (int q = 0; q < la.r; ++q) a += P.A[q * D1 + lane] * P.A[q * D1 + j];
         symA[j] = a;
     }
-    const float b0 = lane < m ? la.P.b0[lane] : 0.f;
-    const float b1 = lane < m ? la.P.b[lane] : 0.f;
-    const float wv = lane < m ? la.P.w[lane] : 0.f;
-    const float cw = lane < D1 ? la.P.cw[lane] : 0.f;
-    const float cbv = la.P.cbp ? *la.P.cbp : la.cb;
+    const float b0 = lane < m ? P.b0[lane] : 0.f;
+    const float b1 = lane < m ? P.b[lane] : 0.f;
+    const float wv = lane < m ? P.w[lane] : 0.f;
+    const float cw = lane < D1 ? P.cw[lane] : 0.f;
+    const float cbv = P.cbp ? *P.cbp : la.cb;
     const float xt = lane < d ? pb.xtarget[lane] : 0.f;
 
     // ---- gradient rows of this lane
@@ -69,12 +84,12 @@ __global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, D
     for (int k = 0; k < MP; ++k) gK1[k] = 0.f;
     float gb0 = 0.f, gb1 = 0.f, gw = 0.f, gcw = 0.f, gcb = 0.f;
 
-    const bool wantW = want_W(pb) && N >= 2;
+    const bool wantW = (ENS ? eAW != 0.f : want_W(pb)) && N >= 2;
     const float den = (float)(2.0 * pb.r * pb.r);
     const float inv_r2 = 1.f / ((float)pb.r * (float)pb.r);
     const double facN = pb.training ? 2.2 : 2.0;                     // Cross2D.py:130-160 (N == 2 and N > 2 alike)
     const float thr = (float)(facN * pb.r);
-    const float aQ = (float)pb.alphQ, aW = (float)pb.alphW;
+    const float aQ = ENS ? eAQ : (float)pb.alphQ, aW = ENS ? eAW : (float)pb.alphW;
     const int comp = lane & 1;                                      // Cross2D: lane = 2*agent + comp
 
     float LAM = 0.f, XS = 0.f, XP = 0.f;
@@ -125,16 +140,16 @@ __global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, D
                               + wave_sum(lane < D1 ? cw * s : 0.f) + cbv;
             const float res = lane < d ? s - xt : 0.f;
             const float cG = 0.5f * wave_sum(res * res);
-            const float ef = sgnf(phi - la.a0 * cG);
-            const float dg = g - la.a0 * res;
+            const float ef = sgnf(phi - (ENS ? eA0 : la.a0) * cG);
+            const float dg = g - (ENS ? eA0 : la.a0) * res;
             const float eg = sgnf(dg);
             if (lane < d) {
-                LAM = la.inv_n * (la.a0 * res + la.a4 * ef * dg - la.a5 * la.a0 * eg);
-                gbar = la.inv_n * la.a5 * eg;
+                LAM = la.inv_n * ((ENS ? eA0 : la.a0) * res + (ENS ? eA4 : la.a4) * ef * dg - (ENS ? eA5 : la.a5) * (ENS ? eA0 : la.a0) * eg);
+                gbar = la.inv_n * (ENS ? eA5 : la.a5) * eg;
             }
             // the value cotangent reuses the forward quantities: ubar = phib a, qbar = phib v, obar = phib y
             if constexpr (STATES != 1) {
-            const float phib = la.inv_n * la.a4 * ef;
+            const float phib = la.inv_n * (ENS ? eA4 : la.a4) * ef;
 #pragma unroll
             for (int kk = 0; kk < MP; ++kk) gK1[kk] = fmaf(phib * v, lane_bcast(u0, kk), gK1[kk]);
 #pragma unroll
@@ -197,11 +212,11 @@ __global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, D
             const float Wv = wantW ? 0.5f * wave_sum((lane < d && comp == 0) ? wsum : 0.f) : 0.f;   // every unordered pair twice
             const float Qs = aQ * Qraw;
             float Lg = 0.5f * sp2 + Qs;
-            if (want_W(pb)) Lg = Lg + aW * Wv;
+            if ((ENS ? eAW != 0.f : want_W(pb))) Lg = Lg + aW * Wv;
             const float H = -Lg + sp2;
             const float gt = lane_bcast_u(g, d);
             const float eh = sgnf(gt - H);
-            const float kL = hs * wst * la.inv_n, kh = kL * la.a3;
+            const float kL = hs * wst * la.inv_n, kh = kL * (ENS ? eA3 : la.a3);
             if (lane < d) {
                 const float fbar = hs * (wst * LAM + cpl * XP);
                 gbar = -fbar + (kL - eh * kh) * g;

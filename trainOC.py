@@ -22,7 +22,12 @@ disturbance in the ball ||W_i||_2 <= EPS over every start's [nt, d] path (DESIGN
 across the iterations on a batch -- zero at the start and whenever the batch is resampled -- and takes one projected ascent step of length
 2.5 EPS / K per Adam step, from the same backward that gives the parameter gradients (neuraloc_amd.adversarial_step).  pgd: every iteration
 runs a K-step search from zero first (neuraloc_amd.pgd_ocflow_train), on the training loss (Jc) or on L + alph0 G (control).  Validation stays
-undisturbed.  EPS = 0 (default) is the run without the flag."""
+undisturbed.  EPS = 0 (default) is the run without the flag.
+--members E [--members_alph FILE] (addition): E networks of the run's shape trained in ONE process, one launch per rollout and per adjoint
+for all of them (neuraloc_amd.ensemble).  Member e is the network the run with --seed SEED+e builds; all members see
+member 0's batches.  FILE: E lines of six comma-separated multipliers, one member each (default: every member uses --alph).  One log line per
+member and iteration, the usual line prefixed by "m<e>"; one checkpoint per member in the reference's layout, ..._m<e>_checkpt.pth, each
+keeping that member's own best.  The small-network shapes only; not with --prec double, --noise, --adv, --resume or more than one rank."""
 import argparse
 import datetime
 import os
@@ -74,6 +79,9 @@ _FLAGS = [
                               "pgd: a K-step search from zero in front of every iteration"),
     ("adv_steps", int, 4, "(addition) K: free mode takes ascent steps of length 2.5 EPS / K; pgd mode runs K inner steps"),
     ("adv_objective", str, "Jc", "(addition, pgd only) what the adversary climbs: Jc (the training loss) or control (L + alph0 G)"),
+    ("members", int, None, "(addition) E >= 1: train E networks of this shape in one process, one launch per rollout for all of them "
+                        "(neuraloc_amd.ensemble); member e is seeded --seed + e; single precision, one rank, the small-network shapes only"),
+    ("members_alph", str, None, "(addition, with --members) file of E lines of six comma-separated multipliers, one member each (default: --alph)"),
 ]
 _CHOICES = {"data": PROBLEM_NAMES, "optim": ["adam"], "prec": ["single", "double"], "approach": ["ocflow"], "noise_rng": ["torch", "counter"],
             "adv_mode": ["free", "pgd"], "adv_objective": ["Jc", "control"]}
@@ -88,6 +96,121 @@ def parse_args(argv=None):
     if a.new_alph is not None:
         a.new_alph = [float(v) for v in a.new_alph.split(",")]
     return a
+
+
+def members_refusals(args, world):
+    """--members: everything the ensemble run does not take, refused before anything runs or is written.  -> the members' multipliers"""
+    if args.members is None or args.members < 1:
+        raise SystemExit("--members E must be >= 1 (--members_alph needs --members)")
+    if args.prec == "double":
+        raise SystemExit("--members runs in single precision only (the double-precision kernels take one network)")
+    if args.noise > 0 or args.adv > 0:
+        raise SystemExit("--members excludes --noise and --adv: the disturbed rollouts take one network")
+    if world > 1:
+        raise SystemExit("--members runs on one rank (one GPU)")
+    if args.resume is not None:
+        raise SystemExit("--members does not take --resume: a checkpoint holds one network")
+    if args.lr_reload == "clone":
+        raise SystemExit("--members keeps the reference's --lr_reload alias only")
+    if args.data not in PROBLEM_NAMES or args.data == "singlequad":
+        raise SystemExit("--members takes the point-agent problems only")
+    if len(args.alph) < 6:
+        raise SystemExit("--alph needs 6 entries")
+    rows = [list(args.alph[:6])] * args.members
+    if args.members_alph is not None:
+        with open(args.members_alph) as f:
+            rows = [[float(v) for v in ln.split(",")] for ln in f if ln.strip()]
+        if len(rows) != args.members or any(len(r_) != 6 for r_ in rows):
+            raise SystemExit("--members_alph: the file must hold --members lines of six comma-separated multipliers")
+    # the shape, known without a device: the ensemble runs on the small-network kernels, whose adjoint takes Cross2D agents (ensemble.LANE_LIMITS)
+    prob, x0, _x0v, _xInit = initProb(args.data, 1, 1, var0=args.var0, alph=args.alph, cvt=lambda t: t.float())
+    d = x0.size(1)
+    if not (args.nTh == 2 and 1 <= args.m <= 32 and d + 1 <= 32 and isinstance(prob, na.Cross2D) and prob.nAgents <= 16):
+        raise SystemExit("--members: {:} with m={:}, nTh={:} (d={:}) is outside the small-network kernels an ensemble runs on: {:}, Cross2D "
+                         "agents for training".format(args.data, args.m, args.nTh, d, na.ensemble.LANE_LIMITS))
+    return rows
+
+
+def train_members(args, rows):
+    """the training loop of main() for E networks at once (neuraloc_amd.ensemble): same schedule, one log line and one checkpoint per member"""
+    E = args.members
+    dev = torch.device("cuda", args.gpu)
+    assert torch.cuda.is_available(), "trainOC.py needs an MI355X: there is no CPU path"
+    cvt = lambda t: t.float().to(dev)                                  # noqa: E731
+    tspan = [0.0, 1.0]
+    # member e: the network the single-network run with --seed SEED+e builds (its generator has drawn that run's batches first); the batches
+    # and every later draw are member 0's, so member 0 of an ensemble run IS the single-network run with --seed SEED
+    nets, state0 = [], None
+    for e in range(E):
+        if args.seed is not None:
+            torch.manual_seed(args.seed + e)
+        p_e, x0_e, x0v_e, xInit_e = initProb(args.data, args.n_train, args.n_train, var0=args.var0, alph=rows[e], cvt=cvt)
+        nets.append(na.Phi(nTh=args.nTh, m=args.m, d=x0_e.size(1), alph=rows[e]))
+        if e == 0:
+            prob, x0, x0v, xInit = p_e, x0_e, x0v_e, xInit_e
+            state0 = torch.get_rng_state()
+    torch.set_rng_state(state0)
+    d, m, nTh = x0.size(1), args.m, args.nTh
+    ens = na.PhiEnsemble.from_members(nets, alph=rows).to(dev)
+    optim = torch.optim.Adam(ens.parameters(), lr=args.lr, weight_decay=args.weight_decay)
+    stamp = datetime.datetime.now().strftime("%Y_%m_%d_%H_%M_%S")
+    title = args.data + "_" + stamp + "_alph{:}_{:}_{:}_{:}_{:}_{:}_m{:}".format(*[int(v) for v in args.alph], m)
+    print("DIMENSION={:}  m={:}  nTh={:}   members={:}".format(d, m, nTh, E))
+    for e in range(E):
+        print("m{:}  alpha={:}".format(e, rows[e]))
+    print("nt={:}   nt_val={:}".format(args.nt, args.nt_val))
+    print("Number of trainable parameters: {} per member".format(sum(p.numel() for p in ens.parameters() if p.requires_grad) // E))
+    print("data={:} device={:} ranks=1".format(args.data, dev))
+    print("n_train={:}".format(args.n_train))
+    print("{:4s} {:5s} {:7s} {:6s}   {:9s}  {:8s}  {:8s}  {:8s}  {:8s}  {:8s}  {:8s}  {:8s}     {:9s}  {:8s}  {:8s}  {:8s}  {:8s}  {:8s}  {:8s}  {:8s}".format(
+        "mem", "iter", "lr", "  time", "loss", "L", "G", "HJt", "HJfin", "HJgrad", "Q", "W",
+        "valLoss", "valL", "valG", "valHJt", "valHJf", "valHJg", "valQ", "valW"))
+    n_change = int(args.new_alph[0]) if args.new_alph is not None else -1
+    best_loss, total = [float("inf")] * E, 0.0
+    prob.train()
+    end = time.time()
+    for itr in range(1, args.niters + 1):
+        optim.zero_grad()
+        Jc, cs = na.ensemble_ocflow_train(x0, ens, prob, tspan, args.nt, "rk4")
+        Jc.sum().backward()                               # (upstream gradient 1 for every member: E independent gradients)
+        torch.cuda.synchronize()
+        optim.step()
+        dt = time.time() - end
+        total += dt
+        Jh, ch = Jc.tolist(), cs.tolist()
+        lines = ["m{:<3d} {:05d} {:7.1e} {:6.2f}   {:9.3e}  {:8.2e}  {:8.2e}  {:8.2e}  {:8.2e}  {:8.2e}  {:8.2e}  {:8.2e}".format(
+            e, itr, optim.param_groups[0]["lr"], dt, Jh[e], *ch[e]) for e in range(E)]
+        if itr % args.val_freq == 0 or itr == args.niters:
+            with torch.no_grad():
+                prob.eval()
+                vl, vcs = na.ensemble_rollout(x0v, ens, prob, tspan, args.nt, "rk4")
+                vh, vch = vl.tolist(), vcs.tolist()
+                for e in range(E):
+                    lines[e] += "    {:9.2e}  {:8.2e}  {:8.2e}  {:8.2e}  {:8.2e}  {:8.2e}  {:8.2e}  {:8.2e} ".format(vh[e], *vch[e])
+                    if vh[e] < best_loss[e]:
+                        best_loss[e] = vh[e]
+                        os.makedirs(args.save, exist_ok=True)
+                        a_e = argparse.Namespace(**vars(args))
+                        a_e.alph, a_e.member = list(rows[e]), e
+                        torch.save({"args": a_e, "state_dict": {k: v.cpu() for k, v in ens.member_state_dict(e).items()}},
+                                   os.path.join(args.save, title + "_m{:}_checkpt.pth".format(e)))
+                prob.train()
+        if itr % args.log_freq == 0:
+            for ln in lines:
+                print(ln)
+        if itr % args.lr_freq == 0 and min(best_loss) < float("inf"):
+            for g in optim.param_groups:                  # (--lr_reload alias, the reference's behaviour: no roll-back)
+                g["lr"] *= args.lr_decay
+        if itr % args.sample_freq == 0:
+            x0 = resample(x0, xInit, args.var0, cvt)
+        if itr == n_change:
+            rows = [[r_[0]] + list(args.new_alph[2:4]) + list(r_[3:]) for r_ in rows]       # like main(): the Q / W weights change, the others stay
+            ens.alph = [list(r_) for r_ in rows]
+            print("alph values changed")
+        end = time.time()
+    print("Training Time: {:} seconds".format(total))
+    print("Training has finished.  " + os.path.join(args.save, title))
+    return best_loss
 
 
 def main(argv=None):
@@ -112,6 +235,8 @@ def main(argv=None):
         raise SystemExit("--adv_objective control needs --adv_mode pgd: the free adversary climbs the training loss itself")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
+    if args.members is not None or args.members_alph is not None:
+        return train_members(args, members_refusals(args, world))
     if world > 1:
         import torch.distributed as dist
         local = int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count())
