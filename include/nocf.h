@@ -496,6 +496,42 @@ int nocf_rollout_bwd_mid_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n
                              void* stream);
 
 /*
+ * Ensembles on the one-CU kernels: E = `members` networks of ONE shape with a one-CU plan (nTh = 2, m <= 128, d+1 <= 32, rank of A <= 16,
+ * every problem class; the adjoint: 32 < m) rolled out, and differentiated, in one launch each.  A 16-sample tile stays on its CU and a
+ * network in its workgroup, so member e simply takes workgroups [e * tiles, (e + 1) * tiles) of the launch; its last tile replicates ITS row
+ * n - 1, and its results carry the bits of nocf_rollout_f32 / nocf_rollout_record_act_f32 / nocf_rollout_bwd_mid_f32 on that member alone.
+ *   phi, n, x, x_member_stride, alph, cost_sums, cost_means    as for nocf_rollout_ensemble_f32 (stacked tensors, cb_dev required, alph the
+ *              DEVICE table [E, 6] standing for alph[0, 3, 4, 5] and the problem's alph_Q / alph_W)
+ *   every buffer is MEMBER-MAJOR -- member e's block has the single-network layout (this differs from the lane ensemble, which is time-major
+ *   over E*n rows):  z_out [E, n, d+4], persample [E, n, 7], zFull [E, nt+1, n, d+4], ctrlFull [E, nt+1, n, a], s_all [E, nt*nstage, n, d+1],
+ *              lam0 [E, n, d];  act_rec [E, S] with S = nocf_activation_record_floats(d, m, nTh, n, nt, stepper) rounded UP to a multiple
+ *              of 4 floats (the record is read in 16-byte pieces), nullable, written under the single-network rule (m % 16 == 0, m > 32:
+ *              *recorded = 1)
+ *   gpart      device [E, gpart_rows, nocf_small_grad_floats(d, m)] with gpart_rows == nocf_mid_grad_rows(d, m, nTh, r, agents, n) exactly:
+ *              workgroup j of member e walks the member's tiles j, j + gpart_rows, ... and writes gpart[e][j]; the caller adds each
+ *              member's partial vectors in order.  inv_n: 1 / n of a member
+ *   workspace  nocf_mid_ensemble_workspace_bytes(d, m, nTh, r, members) bytes, 0 when the shape has no one-CU plan; member e's block (images,
+ *              padded vectors, the plan record with its c.bias) begins e * (bytes / members) behind the base.  All members are packed by
+ *              ONE launch
+ * Refused before anything is enqueued: a shape without a one-CU plan (the adjoint: without an adjoint instantiation), NOCF_MONO=0, members
+ * < 1, a stride that is neither 0 nor n d, members * n >= 2^31 (NOCF_E_SHAPE); a workspace that is too small, gpart_rows != the query's
+ * (NOCF_E_WORKSPACE); cb_dev == NULL (NOCF_E_NULL).  nocf_last_rollout_kernel(): "rollout_mono_kernel<ens>" / "rollout_mono_bwd_kernel<ens>".
+ */
+size_t nocf_mid_ensemble_workspace_bytes(int32_t d, int32_t m, int32_t nTh, int32_t r, int32_t members);
+int nocf_rollout_mid_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members, int64_t x_member_stride,
+                                  double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                  float* z_out, float* persample, float* cost_sums, float* cost_means, float* zFull, float* ctrlFull,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+int nocf_rollout_record_mid_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members, int64_t x_member_stride,
+                                         double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                         float* z_out, float* persample, float* cost_sums, float* s_all, float* act_rec, int32_t* recorded,
+                                         void* workspace, size_t workspace_bytes, void* stream);
+int nocf_rollout_bwd_mid_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper, double t1,
+                                      const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
+                                      const float* act_rec, float* gpart, int64_t gpart_rows, float* lam0,
+                                      void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * The STATE-ONLY adjoint: the lambda recursion of the three adjoints above (nocf_rollout_bwd_small_f32 / _mid_f32 / _act_f32) with every
  * parameter-gradient operation compiled out -- no gradient rows or accumulators, no outer products, no partial vectors, no row streams --
  * and the per-step state cotangents written out.  The inner loop of a worst-case disturbance search (nocf_disturbance_ascent_f32) and

@@ -233,81 +233,11 @@ static bool plan_is(const DevPlan& run) {
 // weight packing: image[cb][kq][lane] = float4 of B[k = 4kq..4kq+3][col = 64cb + lane]
 // ------------------------------------------------------------------------------------------
 __global__ void pack_kernel(DevPlan pl, DevPhi P, float* __restrict__ ws) {
-    float4* ws4 = reinterpret_cast<float4*>(ws);
-    const long nW0f = (long)pl.MB * pl.KQ1 * 64;       // opening:  B[k][j] = K0[j][k]
-    const long nW0b = (long)pl.DB * pl.KQm * 64;       // closing:  B[k][i] = K0[k][i]
-    const long nWl = (long)pl.MB * pl.KQm * 64;
-    const long nLayers = pl.nTh - 1;
-    const long total4 = nW0f + nW0b + 2 * nLayers * nWl;
-    const long stride = (long)gridDim.x * blockDim.x;
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total4; idx += stride) {
-        float v[4];
-        long dst;
-        if (idx < nW0f) {
-            long q = idx;
-            const int lane = q & 63; q >>= 6;
-            const int kq = q % pl.KQ1, cb = q / pl.KQ1;
-            const int j = cb * 64 + lane;
-            for (int e = 0; e < 4; ++e) {
-                const int k = kq * 4 + e;
-                v[e] = (j < pl.m && k < pl.D1) ? P.K0[(long)j * pl.D1 + k] : 0.f;
-            }
-            dst = pl.oW0f + idx;
-        } else if (idx < nW0f + nW0b) {
-            long q = idx - nW0f;
-            const int lane = q & 63; q >>= 6;
-            const int kq = q % pl.KQm, cb = q / pl.KQm;
-            const int i = cb * 64 + lane;
-            for (int e = 0; e < 4; ++e) {
-                const int k = kq * 4 + e;
-                v[e] = (k < pl.m && i < pl.D1) ? P.K0[(long)k * pl.D1 + i] : 0.f;
-            }
-            dst = pl.oW0b + (idx - nW0f);
-        } else {
-            const long q = idx - nW0f - nW0b;
-            const int layer = q / (2 * nWl);             // 0 -> reference layer 1
-            long w = q - (long)layer * 2 * nWl;
-            const int back = w >= nWl;
-            if (back) w -= nWl;
-            const int lane = w & 63; const long ww = w >> 6;
-            const int kq = ww % pl.KQm, cb = ww / pl.KQm;
-            const float* Kl = P.K + (long)layer * pl.m * pl.m;
-            const int a = cb * 64 + lane;
-            for (int e = 0; e < 4; ++e) {
-                const int k = kq * 4 + e;
-                float val = 0.f;
-                if (a < pl.m && k < pl.m) val = back ? Kl[(long)k * pl.m + a]    // backward: B[j][col] = K[j][col]
-                                                     : Kl[(long)a * pl.m + k];   // forward:  B[k][j]   = K[j][k]
-                v[e] = val;
-            }
-            dst = (back ? pl.oWb : pl.oWf) + (long)layer * pl.strideW + w;
-        }
-        ws4[dst] = make_float4(v[0], v[1], v[2], v[3]);
-    }
-    // padded vectors
-    const long nb0 = (long)pl.MB * 64, nb = nLayers * pl.MB * 64, nw = (long)pl.MB * 64, ncw = (long)pl.DB * 64;
-    const long totalv = nb0 + nb + nw + ncw;
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < totalv; idx += stride) {
-        float val = 0.f;
-        long dst;
-        if (idx < nb0) { if (idx < pl.m) val = P.b0[idx]; dst = pl.ob0 + idx; }
-        else if (idx < nb0 + nb) {
-            const long q = idx - nb0; const int layer = q / (pl.MB * 64); const int c = q % (pl.MB * 64);
-            if (c < pl.m) val = P.b[(long)layer * pl.m + c];
-            dst = pl.ob + q;
-        } else if (idx < nb0 + nb + nw) { const long q = idx - nb0 - nb; if (q < pl.m) val = P.w[q]; dst = pl.ow + q; }
-        else { const long q = idx - nb0 - nb - nw; if (q < pl.D1) val = P.cw[q]; dst = pl.ocw + q; }
-        ws[dst] = val;
-    }
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < (long)pl.r * pl.D1; idx += stride)
-        ws[pl.oA + idx] = P.A[idx];
-    // the plan itself, for the kernels that read it through a pointer
-    if (blockIdx.x == 0 && threadIdx.x < sizeof(DevPlan) / 4) {
-        const unsigned* src = reinterpret_cast<const unsigned*>(&pl);
-        unsigned v = src[threadIdx.x];
-        if (P.cbp && threadIdx.x == offsetof(DevPlan, cb) / 4) v = __float_as_uint(*P.cbp);
-        reinterpret_cast<unsigned*>(ws + pl.oPlan)[threadIdx.x] = v;
-    }
+#define PACK_BID blockIdx.x
+#define PACK_NBLK gridDim.x
+#include "nocf_pack_body.inc"
+#undef PACK_BID
+#undef PACK_NBLK
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2315,7 +2245,9 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
         // activation record: the one-CU kernel writes it too, for the widths nocf_activation_record_floats sizes a record for
         const bool mono_rec = act && s_all && !tapeSc && (phi->m % 16) == 0 && phi->m > 32;
         if (mono_rec) { ra.act = act; ra.actRows = (long)nt * ((stepper == NOCF_RK4) ? 4 : 1) * n; }
-        void* args[] = {(void*)&mpp, (void*)&pb, (void*)&ws, (void*)&ra};
+        MonoEnsArgs noEns;                            // (read by the ENS instantiations only: nocf_rollout_mid_ensemble_f32)
+        memset(&noEns, 0, sizeof(noEns));
+        void* args[] = {(void*)&mpp, (void*)&pb, (void*)&ws, (void*)&ra, (void*)&noEns};
         e = hipLaunchKernel(fk, dim3((int)((n + 15) / 16)), dim3(256), args, ldsBytes, st); if (e) return (int)e;
         ra.act = nullptr; ra.actRows = 0;
         if (mono_rec && act_recorded) *act_recorded = 1;
@@ -2899,7 +2831,9 @@ static int bwd_mid_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n, int
         if (hipEventCreate(&ev0) || hipEventCreate(&ev1)) return (int)hipErrorUnknown;
         (void)hipEventRecord(ev0, st);
     }
-    void* args[] = {(void*)&mpp, (void*)&pb, (void*)&wsc, (void*)&ba};
+    MonoEnsArgs noEns;                                // (read by the ENS instantiations only: nocf_rollout_bwd_mid_ensemble_f32)
+    memset(&noEns, 0, sizeof(noEns));
+    void* args[] = {(void*)&mpp, (void*)&pb, (void*)&wsc, (void*)&ba, (void*)&noEns};
     e = hipLaunchKernel(fk, dim3((unsigned)rows), dim3(256), args, ldsBytes, st);
     if (e) return (int)e;
     if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
@@ -2923,6 +2857,217 @@ int nocf_rollout_bwd_mid_w_f32(const NocfPhi* phi, const NocfProb* prob, int64_t
                                void* workspace, size_t workspace_bytes, void* stream) {
     return bwd_mid_impl(phi, prob, n, nt, stepper, t1, alph, inv_n, s_all, z_final, hs, act_rec, gpart, gpart_rows, lam0, lamW, lamW ? 2 : 0,
                         workspace, workspace_bytes, stream);
+}
+
+// ---- ensembles on the one-CU kernels (include/nocf.h): E networks of one shape, member e on workgroups [e * tiles, (e + 1) * tiles)
+// of one launch, every buffer member-major.  This family or nothing: every other shape is refused before anything is enqueued
+#ifndef NOCF_JIT_ONLY
+static size_t mono_ens_ws_stride(const MonoPlan& mp) {        // bytes of one member's workspace block (whole 256-byte lines)
+    return (mono_ws_bytes(mp) + 255) / 256 * 256;
+}
+
+static size_t mono_ens_act_stride(const NocfPhi* phi, int64_t n, int32_t nt, int32_t stepper) {      // floats; the record's rows are read as float4
+    return (nocf_activation_record_floats(phi->d, phi->m, phi->nTh, n, nt, stepper) + 3) / 4 * 4;
+}
+
+// every refusal the three launches share -> the problem, the plans (bwd: the adjoint's LDS layout) and the member stride of the workspace
+static int mid_ensemble_check(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper, bool bwd,
+                              const void* workspace, size_t workspace_bytes, DevProb* pb, DevPlan* pl, MonoPlan* mpl) {
+    int rc = check_phi(phi);
+    if (rc) return rc;
+    if (!phi->cb_dev) return NOCF_E_NULL;                  // (c.bias [E] is read on the device: there is no host value per member)
+    if (!workspace) return NOCF_E_NULL;
+    if (n < 1 || nt < 1 || members < 1 || (int64_t)members * n > 0x7fffffffl) return NOCF_E_SHAPE;
+    if (stepper != NOCF_RK4 && stepper != NOCF_RK1) return NOCF_E_STEPPER;
+    rc = fill_prob(prob, phi->d, pb);
+    if (rc) return rc;
+    if (env_int("NOCF_MONO", 1) == 0) return NOCF_E_SHAPE;
+    rc = make_plan(phi->d, phi->m, phi->nTh, phi->r, pb->nAgents, pl, 0);
+    if (rc) return rc;
+    rc = make_mono_plan(*pl, pb->nAgents, mpl, bwd);
+    if (rc) return rc;
+    if (workspace_bytes / (size_t)members < mono_ens_ws_stride(*mpl)) return NOCF_E_WORKSPACE;
+    return 0;
+}
+
+static int mid_ensemble_pack(const NocfPhi* phi, const DevPlan& pl, const MonoPlan& mpl, int32_t members, float* ws, hipStream_t st) {
+    DevPhi P{phi->K0, phi->b0, phi->K, phi->b, phi->w, phi->A, phi->cw, phi->cb_dev};
+    hipLaunchKernelGGL(mono_ens_pack_kernel, dim3(64, (unsigned)members), dim3(256), 0, st, pl, mpl, P, ws, (long)(mono_ens_ws_stride(mpl) / 4));
+    return (int)hipGetLastError();
+}
+
+static int rollout_mid_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members, int64_t x_member_stride,
+                                     double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                     float* z_out, float* persample, float* cost_sums, float* cost_means, float* zFull, float* ctrlFull,
+                                     float* s_all, float* act, int32_t* act_recorded, void* workspace, size_t workspace_bytes, void* stream) {
+    if (act_recorded) *act_recorded = 0;
+    DevProb pb;
+    DevPlan pl;
+    MonoPlan mpl;
+    int rc = mid_ensemble_check(phi, prob, n, members, nt, stepper, false, workspace, workspace_bytes, &pb, &pl, &mpl);
+    if (rc) return rc;
+    if (!x || !alph) return NOCF_E_NULL;
+    if ((zFull != nullptr) != (ctrlFull != nullptr)) return NOCF_E_NULL;
+    if ((cost_sums && !persample) || (cost_means && !cost_sums)) return NOCF_E_NULL;
+    if (x_member_stride != 0 && x_member_stride != n * phi->d) return NOCF_E_SHAPE;
+    if (s_all && env_int("NOCF_MONO_REC", 1) == 0) return NOCF_E_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    float* ws = (float*)workspace;
+    rc = mid_ensemble_pack(phi, pl, mpl, members, ws, st);
+    if (rc) return rc;
+    const int nstage = (stepper == NOCF_RK4) ? 4 : 1;
+    RollArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    ra.x = x; ra.n = n; ra.t0 = t0; ra.t1 = t1; ra.h = (t1 - t0) / nt; ra.nt = nt; ra.stepper = stepper;
+    ra.z_out = z_out; ra.persample = persample; ra.zFull = zFull; ra.ctrlFull = ctrlFull;
+    ra.cdim = nocf_ctrl_dim(prob, phi->d);
+    ra.sAll = s_all;
+    // the activation record under the single-network rule (rollout_impl): the ensemble takes the arithmetic path of the call it stands for
+    const bool mono_rec = act && s_all && (phi->m % 16) == 0 && phi->m > 32;
+    if (mono_rec) { ra.act = act; ra.actRows = (long)nt * nstage * n; }
+    MonoEnsArgs en;
+    memset(&en, 0, sizeof(en));
+    en.n = (unsigned)n; en.tiles = (unsigned)((n + 15) / 16); en.xs = (long)x_member_stride; en.wss = (long)(mono_ens_ws_stride(mpl) / 4);
+    en.alph = alph;
+    en.zfs = (long)(nt + 1) * n * (phi->d + 4); en.cfs = (long)(nt + 1) * n * ra.cdim; en.sas = (long)nt * nstage * n * (phi->d + 1);
+    en.acts = (long)mono_ens_act_stride(phi, n, nt, stepper);
+    const size_t ldsBytes = (size_t)mpl.pp.ldsFloats * 4;
+    const void* fk = nullptr;
+#define NOCF_MONO_ENS_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) fk = s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, 0, true>) \
+                                                                                   : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 0, true>);
+    MONO_SHAPES(NOCF_MONO_ENS_PICK)
+#undef NOCF_MONO_ENS_PICK
+    if (!fk) return NOCF_E_SHAPE;
+    hipError_t e = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes);
+    if (e) return (int)e;
+    if (env_int("NOCF_DEBUG", 0)) fprintf(stderr, "[nocf] mono kernel: %d hidden / %d input k-blocks, LDS %zu B/workgroup\n", mpl.KBM, mpl.KBD, ldsBytes);
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    if (g_prof_on) {
+        if (hipEventCreate(&ev0) || hipEventCreate(&ev1)) return (int)hipErrorUnknown;
+        (void)hipEventRecord(ev0, st);
+    }
+    const MonoPlan* mpp = reinterpret_cast<const MonoPlan*>(ws + mpl.pp.oPlan);
+    void* args[] = {(void*)&mpp, (void*)&pb, (void*)&ws, (void*)&ra, (void*)&en};
+    e = hipLaunchKernel(fk, dim3((unsigned)((long)members * en.tiles)), dim3(256), args, ldsBytes, st);
+    if (e) return (int)e;
+    if (mono_rec && act_recorded) *act_recorded = 1;
+    g_last_kernel = "rollout_mono_kernel<ens>";
+    g_last_errp = nullptr;
+    e = hipGetLastError();
+    if (e) return (int)e;
+    if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
+    if (cost_sums) {                                      // (persample is member-contiguous: the lane ensemble's reduction as it is)
+        hipLaunchKernelGGL(cost_sum_ens_kernel, dim3(members), dim3(256), 0, st, persample, (long)n, cost_sums, cost_means, alph);
+        e = hipGetLastError();
+        if (e) return (int)e;
+    }
+    return 0;
+}
+#endif
+
+size_t nocf_mid_ensemble_workspace_bytes(int32_t d, int32_t m, int32_t nTh, int32_t r, int32_t members) {
+#ifdef NOCF_JIT_ONLY
+    (void)d; (void)m; (void)nTh; (void)r; (void)members;
+    return 0;
+#else
+    if (members < 1) return 0;
+    DevPlan pl;
+    if (make_plan(d, m, nTh, r, 1, &pl, 0)) return 0;       // (no workspace offset depends on the number of agents)
+    MonoPlan mpl;
+    if (make_mono_plan(pl, 1, &mpl)) return 0;
+    return (size_t)members * mono_ens_ws_stride(mpl);
+#endif
+}
+
+int nocf_rollout_mid_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members, int64_t x_member_stride,
+                                  double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                  float* z_out, float* persample, float* cost_sums, float* cost_means, float* zFull, float* ctrlFull,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+#ifdef NOCF_JIT_ONLY
+    (void)phi; (void)prob; (void)x; (void)n; (void)members; (void)x_member_stride; (void)t0; (void)t1; (void)nt; (void)stepper; (void)alph;
+    (void)z_out; (void)persample; (void)cost_sums; (void)cost_means; (void)zFull; (void)ctrlFull; (void)workspace; (void)workspace_bytes; (void)stream;
+    return NOCF_E_SHAPE;
+#else
+    return rollout_mid_ensemble_impl(phi, prob, x, n, members, x_member_stride, t0, t1, nt, stepper, alph, z_out, persample, cost_sums, cost_means,
+                                     zFull, ctrlFull, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
+#endif
+}
+
+int nocf_rollout_record_mid_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members, int64_t x_member_stride,
+                                         double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                         float* z_out, float* persample, float* cost_sums, float* s_all, float* act_rec, int32_t* recorded,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+#ifdef NOCF_JIT_ONLY
+    (void)phi; (void)prob; (void)x; (void)n; (void)members; (void)x_member_stride; (void)t0; (void)t1; (void)nt; (void)stepper; (void)alph;
+    (void)z_out; (void)persample; (void)cost_sums; (void)s_all; (void)act_rec; (void)workspace; (void)workspace_bytes; (void)stream;
+    if (recorded) *recorded = 0;
+    return NOCF_E_SHAPE;
+#else
+    if (recorded) *recorded = 0;
+    if (!s_all || !z_out) return NOCF_E_NULL;
+    return rollout_mid_ensemble_impl(phi, prob, x, n, members, x_member_stride, t0, t1, nt, stepper, alph, z_out, persample, cost_sums, nullptr,
+                                     nullptr, nullptr, s_all, act_rec, recorded, workspace, workspace_bytes, stream);
+#endif
+}
+
+int nocf_rollout_bwd_mid_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper, double t1,
+                                      const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
+                                      const float* act_rec, float* gpart, int64_t gpart_rows, float* lam0,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+#ifdef NOCF_JIT_ONLY
+    (void)phi; (void)prob; (void)n; (void)members; (void)nt; (void)stepper; (void)t1; (void)alph; (void)inv_n; (void)s_all; (void)z_final; (void)hs;
+    (void)act_rec; (void)gpart; (void)gpart_rows; (void)lam0; (void)workspace; (void)workspace_bytes; (void)stream;
+    return NOCF_E_SHAPE;
+#else
+    DevProb pb;
+    DevPlan pl;
+    MonoPlan mpl;
+    int rc = mid_ensemble_check(phi, prob, n, members, nt, stepper, true, workspace, workspace_bytes, &pb, &pl, &mpl);
+    if (rc) return rc;
+    if (!alph || !s_all || !z_final || !hs || !gpart) return NOCF_E_NULL;
+    const int64_t rows = nocf_mid_grad_rows(phi->d, phi->m, phi->nTh, phi->r, pb.nAgents, n);
+    if (rows == 0) return NOCF_E_SHAPE;
+    if (gpart_rows != rows) return NOCF_E_WORKSPACE;       // (gpart [E, rows, P]: the member blocks sit rows partial vectors apart)
+    hipStream_t st = (hipStream_t)stream;
+    float* ws = (float*)workspace;
+    rc = mid_ensemble_pack(phi, mpl.pp, mpl, members, ws, st);
+    if (rc) return rc;
+    BwdArgs ba;
+    memset(&ba, 0, sizeof(ba));
+    ba.sAll = s_all; ba.zT = z_final; ba.hs = hs; ba.n = n; ba.nt = nt; ba.nstage = (stepper == NOCF_RK4) ? 4 : 1;
+    ba.t1 = (float)t1;
+    ba.inv_n = (float)inv_n;
+    ba.lam0 = lam0; ba.lamW = nullptr;
+    ba.gpart = gpart; ba.gstride = nocf_small_grad_floats(phi->d, phi->m);
+    ba.act = (act_rec && (phi->m % 16) == 0) ? act_rec : nullptr; ba.actRows = (long)nt * ba.nstage * n;
+    MonoEnsArgs en;
+    memset(&en, 0, sizeof(en));
+    en.n = (unsigned)n; en.tiles = (unsigned)rows; en.wss = (long)(mono_ens_ws_stride(mpl) / 4); en.alph = alph;
+    en.sas = (long)nt * ba.nstage * n * (phi->d + 1); en.acts = (long)mono_ens_act_stride(phi, n, nt, stepper);
+    const size_t ldsBytes = (size_t)mpl.pp.ldsFloats * 4;
+    const void* fk = nullptr;
+#define NOCF_MBW_ENS_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) fk = reinterpret_cast<const void*>(rollout_mono_bwd_kernel<M_, D_, 0, true>);
+    NOCF_MBW_ENS_PICK(8, 1) NOCF_MBW_ENS_PICK(6, 1) NOCF_MBW_ENS_PICK(4, 1) NOCF_MBW_ENS_PICK(8, 2) NOCF_MBW_ENS_PICK(6, 2) NOCF_MBW_ENS_PICK(4, 2)
+#undef NOCF_MBW_ENS_PICK
+    if (!fk) return NOCF_E_SHAPE;
+    hipError_t e = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes);
+    if (e) return (int)e;
+    if (env_int("NOCF_DEBUG", 0)) fprintf(stderr, "[nocf] mono adjoint kernel: %d hidden k-blocks, LDS %zu B/workgroup\n", mpl.KBM, ldsBytes);
+    const MonoPlan* mpp = reinterpret_cast<const MonoPlan*>(ws + mpl.pp.oPlan);
+    const float* wsc = ws;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    if (g_prof_on) {
+        if (hipEventCreate(&ev0) || hipEventCreate(&ev1)) return (int)hipErrorUnknown;
+        (void)hipEventRecord(ev0, st);
+    }
+    void* args[] = {(void*)&mpp, (void*)&pb, (void*)&wsc, (void*)&ba, (void*)&en};
+    e = hipLaunchKernel(fk, dim3((unsigned)((long)members * rows)), dim3(256), args, ldsBytes, st);
+    if (e) return (int)e;
+    if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
+    g_last_kernel = "rollout_mono_bwd_kernel<ens>";
+    g_last_errp = nullptr;
+    return (int)hipGetLastError();
+#endif
 }
 
 // ---- the state-only adjoint (include/nocf.h): lane, then one-CU, then per-tile -- nocf_rollout_record_disturbed_f32's order.  A family says

@@ -99,68 +99,45 @@ constexpr MonoFwdLds mono_fwd_lds(int KBM, int KBD) {
 //   K1[mt][kb][lane] = K0[16mt + lane%16][16kb + 4(lane/16) + q]      K4[dt][kb][lane] = K0[16kb + 4(lane/16) + q][16dt + lane%16]
 //   AZ[kb][lane]     = A[lane%16][16kb + 4(lane/16) + q]              AT[dt][lane]     = A[4(lane/16) + q][16dt + lane%16]
 __global__ void mono_pack_kernel(MonoPlan mp, DevPhi P, float* __restrict__ ws) {
-    float4* ws4 = reinterpret_cast<float4*>(ws);
-    const int m = mp.pp.m, D1 = mp.pp.D1, r = mp.pp.r, KBM = mp.KBM, KBD = mp.KBD;
-    const long nW = (long)KBM * KBM * 64, nK1 = (long)KBM * KBD * 64, nK4 = (long)KBD * KBM * 64, nAZ = (long)KBD * 64, nAT = (long)KBD * 64;
-    const long total = 2 * nW + nK1 + nK4 + nAZ + nAT;
-    const long stride = (long)gridDim.x * blockDim.x;
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += stride) {
-        float v[4] = {0.f, 0.f, 0.f, 0.f};
-        long q = idx, dst;
-        const int lane = idx & 63;
-        if (idx < 2 * nW) {
-            const bool third = idx >= nW;
-            q = (third ? idx - nW : idx) >> 6;
-            const int kb = q % KBM, mt = q / KBM;
-            const int o = 16 * mt + (lane & 15);
-            for (int e = 0; e < 4; ++e) {
-                const int k = 16 * kb + 4 * (lane >> 4) + e;
-                if (o < m && k < m) v[e] = third ? P.K[(long)k * m + o] : P.K[(long)o * m + k];
-            }
-            dst = (third ? mp.oW3 : mp.oW2) + (third ? idx - nW : idx);
-        } else if (idx < 2 * nW + nK1) {
-            q = (idx - 2 * nW) >> 6;
-            const int kb = q % KBD, mt = q / KBD;
-            const int o = 16 * mt + (lane & 15);
-            for (int e = 0; e < 4; ++e) {
-                const int k = 16 * kb + 4 * (lane >> 4) + e;
-                if (o < m && k < D1) v[e] = P.K0[(long)o * D1 + k];
-            }
-            dst = mp.oK1 + (idx - 2 * nW);
-        } else if (idx < 2 * nW + nK1 + nK4) {
-            q = (idx - 2 * nW - nK1) >> 6;
-            const int kb = q % KBM, dt = q / KBM;
-            const int dim = 16 * dt + (lane & 15);
-            for (int e = 0; e < 4; ++e) {
-                const int i = 16 * kb + 4 * (lane >> 4) + e;
-                if (i < m && dim < D1) v[e] = P.K0[(long)i * D1 + dim];
-            }
-            dst = mp.oK4 + (idx - 2 * nW - nK1);
-        } else if (idx < 2 * nW + nK1 + nK4 + nAZ) {
-            const int kb = (idx - 2 * nW - nK1 - nK4) >> 6;
-            const int row = lane & 15;
-            for (int e = 0; e < 4; ++e) {
-                const int k = 16 * kb + 4 * (lane >> 4) + e;
-                if (row < r && k < D1) v[e] = P.A[(long)row * D1 + k];
-            }
-            dst = mp.oAZ + (idx - 2 * nW - nK1 - nK4);
-        } else {
-            const int dt = (idx - 2 * nW - nK1 - nK4 - nAZ) >> 6;
-            const int dim = 16 * dt + (lane & 15);
-            for (int e = 0; e < 4; ++e) {
-                const int row = 4 * (lane >> 4) + e;
-                if (row < r && dim < D1) v[e] = P.A[(long)row * D1 + dim];
-            }
-            dst = mp.oAT + (idx - 2 * nW - nK1 - nK4 - nAZ);
-        }
-        ws4[dst] = make_float4(v[0], v[1], v[2], v[3]);
+#define PACK_BID blockIdx.x
+#define PACK_NBLK gridDim.x
+#include "nocf_mono_pack_body.inc"
+#undef PACK_BID
+#undef PACK_NBLK
+}
+
+// Ensembles on this family (include/nocf.h, nocf_rollout_mid_ensemble_f32; DESIGN 3.13): E networks of one shape, member e on workgroups
+// [e * tiles, (e + 1) * tiles) of ONE launch.  A tile never leaves its CU and a network never leaves its workgroup, so an ENS kernel offsets
+// its pointers to member e's blocks at its top and runs the single-network statements on them.  The member information is a LAST kernel
+// argument (no new field in RollArgs / BwdArgs / MonoPlan: the offsets of the existing arguments stay where they are).  All strides in floats.
+struct MonoEnsArgs {
+    unsigned n;                      // rows of ONE member
+    unsigned tiles;                  // workgroups per member: ceil(n / 16) (forward), nocf_mid_grad_rows (adjoint)
+    long xs;                         // member stride of x: 0 (shared starts) or n d
+    long wss;                        // member stride of the workspace (images, padded vectors, the plan record with the member's c.bias)
+    const float* alph;               // device [E, 6]: [0] -> a0, [1] -> alph_Q, [2] -> alph_W, [3..5] -> a3..a5
+    long zfs, cfs, sas, acts;        // member strides of zFull [nt+1, n, d+4], ctrlFull [nt+1, n, cdim], s_all [nt*nstage, n, d+1], the activation record
+};
+
+// packs all members in one launch: member blockIdx.y, the two single-network pack bodies on that member's tensors and workspace block
+// (pack_kernel's padded vectors and copy of A, then the images and the plan record of mono_pack_kernel; both write the plan words, the same
+// thread the same word, the one-CU record last)
+__global__ void mono_ens_pack_kernel(DevPlan pl, MonoPlan mp, DevPhi Pst, float* __restrict__ ws0, long wss) {
+    const long e = blockIdx.y;
+    const long m = pl.m, D1 = pl.D1;
+    const DevPhi P{Pst.K0 + e * m * D1, Pst.b0 + e * m, Pst.K + e * (pl.nTh - 1) * m * m, Pst.b + e * (pl.nTh - 1) * m, Pst.w + e * m,
+                   Pst.A + e * pl.r * D1, Pst.cw + e * D1, Pst.cbp + e};
+    float* __restrict__ ws = ws0 + e * wss;
+#define PACK_BID blockIdx.x
+#define PACK_NBLK gridDim.x
+    {
+#include "nocf_pack_body.inc"
     }
-    if (blockIdx.x == 0 && threadIdx.x < sizeof(MonoPlan) / 4) {
-        const unsigned* src = reinterpret_cast<const unsigned*>(&mp);
-        unsigned v = src[threadIdx.x];
-        if (P.cbp && threadIdx.x == (offsetof(MonoPlan, pp) + offsetof(DevPlan, cb)) / 4) v = __float_as_uint(*P.cbp);
-        reinterpret_cast<unsigned*>(ws + mp.pp.oPlan)[threadIdx.x] = v;
+    {
+#include "nocf_mono_pack_body.inc"
     }
+#undef PACK_BID
+#undef PACK_NBLK
 }
 
 // acc[mi] = sum over NKB k-blocks of W[mi][kb] (A operand, registers) x the fragments at LDS float4 index bq + kb*64 (B operand),
@@ -222,11 +199,26 @@ __device__ __forceinline__ void mono_sincos(float x, float& sn, float& cs) {
 // disturbed training): the state rows SB hold the displaced state when the next step's first stage input and activations are recorded
 // DIST == 2: the entries are drawn (nocf_noise.inc: RollArgs::nzScale / nzSeed / nzRow0) where DIST == 1 ADDS them, behind the last stage, into the
 // same variable: nothing is held across the step's evaluations (drawn at the top of the step like the loads, the (4, 2) instantiation lost a wave)
-template <int KBM, int KBD, bool REC, int DIST = 0>
-__global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __restrict__ mpp, DevProb pb, float* ws, RollArgs ra) {
+// ENS (DIST = 0): an ensemble, see MonoEnsArgs.  ra.n is a member's row count; member e = blockIdx.x / en.tiles is workgroup-uniform, the
+// member's last tile replicates the member's row n - 1.  Every ENS test is a compile-time choice at its place of use.
+template <int KBM, int KBD, bool REC, int DIST = 0, bool ENS = false>
+__global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __restrict__ mpp, DevProb pb, float* ws, RollArgs ra, MonoEnsArgs en) {
+    static_assert(!ENS || DIST == 0, "ensembles are undisturbed rollouts");
     constexpr int MT = (KBM + 3) / 4;              // hidden M-tiles per wave: tiles w, w+4, ...
     constexpr int T = 16;
     constexpr MonoFwdLds LL = mono_fwd_lds(KBM, KBD);
+    unsigned etile = 0;                            // ENS: this workgroup's tile inside its member
+    if constexpr (ENS) {
+        const unsigned e = blockIdx.x / en.tiles;
+        etile = blockIdx.x - e * en.tiles;
+        ws += e * en.wss;
+        mpp = reinterpret_cast<const MonoPlan*>(reinterpret_cast<const float*>(mpp) + e * en.wss);
+        const float* at = en.alph + e * 6;
+        ra.a0 = at[0]; pb.alphQ = (double)at[1]; pb.alphW = (double)at[2];
+        ra.x += e * en.xs;
+        if (ra.zFull) { ra.zFull += e * en.zfs; ra.ctrlFull += e * en.cfs; }
+        if (REC) { if (ra.sAll) ra.sAll += e * en.sas; if (ra.act) ra.act += e * en.acts; }
+    }
     MonoPlan mp = *mpp;                    // local copy; the LDS layout is a compile-time constant, the shape words sit in scalar registers
     mp.lSF = LL.lSF; mp.lUF = LL.lUF; mp.lVF = LL.lVF; mp.lK4 = LL.lK4; mp.lAT = LL.lAT; mp.lVO = LL.lVO; mp.lCW = LL.lCW; mp.lZP = LL.lZP;
     mp.lGP = LL.lGP; mp.lPHIP = LL.lPHIP;
@@ -244,12 +236,17 @@ __global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __res
     const int d = pl.d, D1 = pl.D1, r = pl.r, ZLD = pl.ZLD, GLD = pl.GLD, LDs = pl.LDs;
     const int wave = c.wave, lane = c.lane, tid = c.tid;
     const int slot = lane >> 4;
-    const long row0 = (long)blockIdx.x * T;
+    const long row0 = (long)(ENS ? etile : blockIdx.x) * T;
+    if constexpr (ENS) {                           // the member's blocks of persample [E, n, 7] and z_out [E, n, d+4]
+        const long eo = (long)(blockIdx.x / en.tiles) * en.n;
+        if (ra.persample) ra.persample += eo * 7;
+        if (ra.z_out) ra.z_out += eo * (d + 4);
+    }
     // time parameters of this tile's rows: the launch's, or its segment's (SegTab: segments are whole tiles)
     double sg_t0 = ra.t0, sg_h = ra.h;
     int sg_nt = ra.nt;
     long sg_slot = 0;                                                  // first time slot of these rows in zFull / ctrlFull
-    if (ra.seg.n > 0) {
+    if (!ENS && ra.seg.n > 0) {                    // (ENS: no segments; and the table is not indexed in a kernel that writes to its copy of `ra`)
         int k = (int)(row0 / ra.seg.rows); if (k >= ra.seg.n) k = ra.seg.n - 1;
         sg_t0 = ra.seg.t0[k]; sg_nt = ra.seg.nt[k]; sg_h = (ra.t1 - sg_t0) / sg_nt; sg_slot = ra.seg.slot0[k];
     }

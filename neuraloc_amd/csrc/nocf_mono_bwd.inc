@@ -142,12 +142,28 @@ __device__ __forceinline__ void mono_lowrank(const MonoPlan& mp, const f32x4& AZ
     L4[(mp.lZP >> 2) + wave * 64 + lane] = make_float4(zacc[0], zacc[1], zacc[2], zacc[3]);
 }
 
-template <int KBM, int KBD, int STATES = 0>
-__global__ void __launch_bounds__(256) rollout_mono_bwd_kernel(const MonoPlan* __restrict__ mpp, DevProb pb, const float* __restrict__ ws, BwdArgs ba) {
+// ENS (STATES = 0; nocf_rollout_bwd_mid_ensemble_f32): the adjoint of an ensemble rollout (nocf_mono.inc, MonoEnsArgs).  en.tiles =
+// nocf_mid_grad_rows workgroups per member; workgroup j of member e walks the member's tiles j, j + en.tiles, ... (the single-network tile
+// order) and writes partial vector gpart[e][j] = row blockIdx.x.  Every ENS test is a compile-time choice at its place of use.
+template <int KBM, int KBD, int STATES = 0, bool ENS = false>
+__global__ void __launch_bounds__(256) rollout_mono_bwd_kernel(const MonoPlan* __restrict__ mpp, DevProb pb, const float* __restrict__ ws, BwdArgs ba,
+                                                               MonoEnsArgs en) {
     static_assert(KBD == 1 || KBD == 2, "d + 1 <= 32: the (sample, entry) threads take KBD entries each; dM is KBD x KBD tiles on the four waves");
+    static_assert(!ENS || STATES == 0, "ensembles take the full adjoint");
     constexpr int MT = (KBM + 3) / 4;
     constexpr int T = 16;
     constexpr MonoBwdLds LL = mono_bwd_lds(KBM, KBD);
+    unsigned etile = 0;                  // ENS: this workgroup's index inside its member
+    if constexpr (ENS) {
+        const unsigned e = blockIdx.x / en.tiles;
+        etile = blockIdx.x - e * en.tiles;
+        ws += e * en.wss;
+        mpp = reinterpret_cast<const MonoPlan*>(reinterpret_cast<const float*>(mpp) + e * en.wss);
+        const float* at = en.alph + e * 6;
+        ba.a0 = at[0]; pb.alphQ = (double)at[1]; pb.alphW = (double)at[2]; ba.a3 = at[3]; ba.a4 = at[4]; ba.a5 = at[5];
+        ba.sAll += e * en.sas;
+        if (ba.act) ba.act += e * en.acts;
+    }
     MonoPlan mp = *mpp;
     mp.lSF = LL.lSF; mp.lUF = LL.lUF; mp.lVF = LL.lVF; mp.lK4 = LL.lK4; mp.lAT = LL.lAT; mp.lVO = LL.lVO; mp.lCW = LL.lCW; mp.lZP = LL.lZP;
     mp.lGP = LL.lGP; mp.lPHIP = LL.lPHIP; mp.lGF = LL.lGF; mp.lRV = LL.lRV; mp.lRAB = LL.lRAB; mp.lRQB = LL.lRQB; mp.lRU0 = LL.lRU0;
@@ -171,6 +187,11 @@ __global__ void __launch_bounds__(256) rollout_mono_bwd_kernel(const MonoPlan* _
     const float hN = pl.hN;
     const float4* ws4 = reinterpret_cast<const float4*>(ws);
     float4* L4 = reinterpret_cast<float4*>(lds);
+    if constexpr (ENS) {                 // the member's blocks of z_final [E, n, d+4] and lam0 [E, n, d]
+        const long eo = (long)(blockIdx.x / en.tiles) * en.n;
+        ba.zT += eo * (d + 4);
+        if (ba.lam0) ba.lam0 += eo * d;
+    }
 
     // ---- resident weights (as the forward kernel's)
     f32x4 W2[MT][KBM], W3[MT][KBM], K1[MT][KBD], AZ;
@@ -253,7 +274,7 @@ __global__ void __launch_bounds__(256) rollout_mono_bwd_kernel(const MonoPlan* _
     // ---- the 16-sample tiles of this workgroup (tile, tile + gridDim.x, ...: the launch caps the grid, so the partial gradient vectors stay
     // a bounded buffer for any batch size), every tile's evaluations latest first; the gradient sums run on across the tiles
     const long ntiles = (ba.n + T - 1) / T;
-    for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    for (long tile = ENS ? etile : blockIdx.x; tile < ntiles; tile += ENS ? en.tiles : gridDim.x) {
         const long row0 = tile * T;
         const long nvalid = (ba.n - row0 < T) ? (ba.n - row0) : T;
         __syncthreads();                                   // (the previous tile's last reads of the tables and rows)

@@ -10,9 +10,15 @@ rows and wave g reads network g // n; nothing else in the rollout changes, so me
     Jc, cs = ensemble_rollout(x, ens, prob, tspan, nt)                # Jc [E], cs [E, 7]
     Jc, cs = ensemble_ocflow_train(x, ens, prob, tspan, nt)           # Jc.sum().backward(): E independent gradients from one adjoint launch
 
-Single precision, one device, undisturbed rollouts, the lane family only.  There is no CPU or eager-torch fallback and no other kernel family
-behind these calls: everything else is refused before a launch."""
+Single precision, one device, undisturbed rollouts.  There is no CPU or eager-torch fallback behind these calls: everything else is refused
+before a launch.
+
+family="mid"  selects the one-CU weight-stationary kernels instead (csrc/nocf_mono.inc, csrc/nocf_mono_bwd.inc: nTh = 2,
+m <= 128, d+1 <= 32, all three problem classes -- singlequad among them).  There a 16-sample tile sits on one CU with the whole network in its
+registers, a rollout of n = 1024 rows occupies 64 of 256 CUs, and an ensemble fills the idle ones: member e takes workgroups [e * tiles,
+(e + 1) * tiles) of the launch and every buffer is member-major.  The default, family="lane", is the lane family and nothing else."""
 import ctypes as C
+import os
 
 import torch
 import torch.nn as nn
@@ -24,6 +30,10 @@ from .train import _STEPPERS, _step_sizes, _unpack_partials
 
 LANE_LIMITS = "nTh = 2, m <= 32, d + 1 <= 32, rank of A <= 16, a point-agent problem (Cross2D / SwarmTraj) with at most 16 agents"
 
+MID_LIMITS = ("nTh = 2, a width with a one-CU instantiation (m <= 128; training: 32 < m), d + 1 <= 32, rank of A <= 16, Cross2D / SwarmTraj / "
+              "Quadcopter with at most 8 agents when d + 1 <= 16 and at most 16 beyond (MONO_NAG)")
+FAMILIES = ("lane", "mid")
+
 _HEAD = [C.POINTER(_lib.NocfPhi), C.POINTER(_lib.NocfProb), C.c_void_p, C.c_int64, C.c_int32, C.c_int64,
          C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_void_p]
 _ARGTYPES = {
@@ -32,6 +42,53 @@ _ARGTYPES = {
     "nocf_rollout_bwd_small_ensemble_f32": [C.POINTER(_lib.NocfPhi), C.POINTER(_lib.NocfProb), C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                             C.c_double, C.c_void_p, C.c_double] + [C.c_void_p] * 5 + [C.c_void_p],
 }
+
+
+_TAIL = [C.c_void_p, C.c_size_t, C.c_void_p]                       # workspace, its bytes, the stream
+_ARGTYPES_MID = {
+    "nocf_rollout_mid_ensemble_f32": _HEAD + [C.c_void_p] * 6 + _TAIL,
+    "nocf_rollout_record_mid_ensemble_f32": _HEAD + [C.c_void_p] * 5 + [C.POINTER(C.c_int32)] + _TAIL,
+    "nocf_rollout_bwd_mid_ensemble_f32": [C.POINTER(_lib.NocfPhi), C.POINTER(_lib.NocfProb), C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_double, C.c_void_p, C.c_double] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p] + _TAIL,
+}
+
+
+def _entries_mid(L):
+    """(nocf_rollout_mid_ensemble_f32, nocf_rollout_record_mid_ensemble_f32, nocf_rollout_bwd_mid_ensemble_f32) of library L with their
+    prototypes set (and nocf_mid_ensemble_workspace_bytes'), or None when L lacks one of the four"""
+    if not hasattr(L, "nocf_mid_ensemble_workspace_bytes"):
+        return None
+    q = L.nocf_mid_ensemble_workspace_bytes
+    if q.argtypes is None:
+        q.restype = C.c_size_t
+        q.argtypes = [C.c_int32] * 5
+    out = []
+    for name, argtypes in _ARGTYPES_MID.items():
+        if not hasattr(L, name):
+            return None
+        f = getattr(L, name)
+        if f.argtypes is None:
+            f.restype = C.c_int
+            f.argtypes = argtypes
+        out.append(f)
+    return tuple(out)
+
+
+def _shipped_mid():
+    """the shipped library and its three one-CU ensemble entries"""
+    L = _lib.lib()
+    f = _entries_mid(L)
+    if f is None:
+        raise RuntimeError("ensemble: the HIP library does not export nocf_mid_ensemble_workspace_bytes / nocf_rollout_mid_ensemble_f32 / "
+                           "nocf_rollout_record_mid_ensemble_f32 / nocf_rollout_bwd_mid_ensemble_f32; rebuild it")
+    return L, f
+
+
+def _mid_eligible(nTh, m, d, r, n_agents, train=False):
+    """the shape has a one-CU plan (make_mono_plan of csrc/nocf_kernels.hip); train: and an adjoint instantiation (nocf_mid_grad_rows != 0)"""
+    kbd = -(-(d + 1) // 16)
+    return (nTh == 2 and 1 <= m <= 128 and 1 <= d and d + 1 <= 32 and 1 <= r <= min(16, d + 1) and 1 <= n_agents <= (8 if kbd == 1 else 16)
+            and (m > 32 or not train))
 
 
 def _entries(L):
@@ -134,6 +191,7 @@ class PhiEnsemble(nn.Module):
                                 for i in range(p0.nTh)])
         self._tables = {}
         self._plist = None
+        self._mid_ws = {}
 
     def _params(self):
         """[(name, parameter)] in named_parameters() order, cached: the walk over the module tree costs more than a small rollout's launch"""
@@ -174,6 +232,20 @@ class PhiEnsemble(nn.Module):
             t = self._tables[key] = torch.tensor(rows, dtype=torch.float32).to(self.A.device)
         return t
 
+    def mid_workspace(self, L, dev):
+        """the workspace of the one-CU family (nocf_mid_ensemble_workspace_bytes: every member's images, padded vectors and plan record), one
+        per device and stream (as Phi's), cached: the launches of one stream are ordered, and every launch packs it anew"""
+        key = (dev, torch.cuda.current_stream(dev).cuda_stream)
+        ws = self._mid_ws.get(key)
+        if ws is None:
+            if len(self._mid_ws) > 8:
+                self._mid_ws.clear()
+            nbytes = int(L.nocf_mid_ensemble_workspace_bytes(self.d, self.m, self.nTh, self.r, self.members))
+            if nbytes == 0:
+                raise RuntimeError(f"ensemble: no one-CU plan for nTh = {self.nTh}, m = {self.m}, d = {self.d}, rank {self.r}")
+            ws = self._mid_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        return ws
+
     def forward(self, x):
         raise NotImplementedError("PhiEnsemble is evaluated inside the ensemble rollouts (ensemble_rollout / ensemble_ocflow_train); "
                                   "ens.member(e) is a Phi")
@@ -196,8 +268,10 @@ class PhiEnsemble(nn.Module):
         return st, pl
 
 
-def _refuse(fn, x, ens, prob, nt, stepper, train, noMean=False, W=None):
+def _refuse(fn, x, ens, prob, nt, stepper, train, noMean=False, W=None, family="lane"):
     """every refusal of an ensemble call, raised before the library is reached.  -> (E, n, d, own)"""
+    if family not in FAMILIES:
+        raise ValueError(f"{fn}: family must be 'lane' (the small-network lane kernels) or 'mid' (the one-CU kernels), got {family!r}")
     if not isinstance(ens, PhiEnsemble):
         raise TypeError(f"{fn}: ens must be a PhiEnsemble")
     if not isinstance(x, torch.Tensor):
@@ -208,11 +282,16 @@ def _refuse(fn, x, ens, prob, nt, stepper, train, noMean=False, W=None):
         if isinstance(t, torch.Tensor) and t.dtype == torch.float64:
             raise RuntimeError(f"{fn}: {name} is float64; ensembles are single precision only (the double-precision kernels take one network)")
     kind, n_agents = getattr(prob, "KIND", None), int(getattr(prob, "nAgents", 0))
-    if not (ens.nTh == 2 and 1 <= ens.m <= 32 and ens.d + 1 <= 32 and 1 <= ens.r <= 16
+    if family == "mid":
+        if not (kind in (_lib.PROB_CROSS2D, _lib.PROB_SWARMTRAJ, _lib.PROB_QUADCOPTER)
+                and _mid_eligible(ens.nTh, ens.m, ens.d, ens.r, n_agents, train)):
+            raise ValueError(f"{fn}: family='mid' runs on the one-CU kernels only: {MID_LIMITS}; got nTh = {ens.nTh}, m = {ens.m}, "
+                             f"d = {ens.d}, rank {ens.r}, {type(prob).__name__} with {n_agents} agents" + (", training" if train else ""))
+    elif not (ens.nTh == 2 and 1 <= ens.m <= 32 and ens.d + 1 <= 32 and 1 <= ens.r <= 16
             and kind in (_lib.PROB_CROSS2D, _lib.PROB_SWARMTRAJ) and 1 <= n_agents <= 16):
         raise ValueError(f"{fn}: an ensemble runs on the small-network lane kernels only: {LANE_LIMITS}; got nTh = {ens.nTh}, m = {ens.m}, "
                          f"d = {ens.d}, rank {ens.r}, {type(prob).__name__} with {n_agents} agents")
-    if train and not (kind == _lib.PROB_CROSS2D and 2 * n_agents == ens.d):
+    if family == "lane" and train and not (kind == _lib.PROB_CROSS2D and 2 * n_agents == ens.d):
         raise ValueError(f"{fn}: the lane adjoint takes Cross2D agents only ({LANE_LIMITS}); got {type(prob).__name__}")
     if noMean:
         raise NotImplementedError(f"{fn}: noMean is not built for ensembles (per-sample costs: OCflow on ens.member(e))")
@@ -298,17 +377,93 @@ def _launch(x, ens, prob, tspan, nt, stepper, alph=None, intermediates=False, re
     return b
 
 
-def ensemble_rollout(x, ens, prob, tspan, nt, stepper="rk4", alph=None, intermediates=False, *, noMean=False, W=None):
+def _act_stride(L, ens, n, nt, stepper):
+    """member stride of the one-CU ensemble's activation record, in floats: nocf_activation_record_floats rounded up to whole 16-byte pieces
+    (0: the shape records nothing, the adjoint recomputes; NOCF_ACT_REC=0 as for the single-network call)"""
+    if os.environ.get("NOCF_ACT_REC", "1") in ("0", ""):
+        return 0
+    return (int(L.nocf_activation_record_floats(ens.d, ens.m, ens.nTh, int(n), int(nt), _STEPPERS[stepper])) + 3) // 4 * 4
+
+
+def _launch_mid(x, ens, prob, tspan, nt, stepper, alph=None, intermediates=False, record=False, bufs=None):
+    """one launch of the one-CU family (nocf_rollout_mid_ensemble_f32, or nocf_rollout_record_mid_ensemble_f32 with record) -> dict of its
+    buffers, all MEMBER-MAJOR: persample [E, n, 7], z_out [E, n, d+4], sums [E, 8], means [E, 8] (evaluation), zFull [E, nt+1, n, d+4] /
+    ctrlFull [E, nt+1, n, a] (intermediates), s_all [E, nt*nstage, n, d+1] and act [E, stride] or None (record; "recorded": the kernel wrote
+    it).  bufs: buffers to write into instead of fresh ones (same keys)"""
+    E = ens.members
+    own = x.dim() == 3
+    n, d = x.shape[-2], x.shape[-1]
+    x = _lib.require_device_f32(x.detach(), "x")
+    dev = x.device
+    _lib.check_errors()
+    L, (f_eval, f_rec, _f_bwd) = _shipped_mid()
+    phi_st, keep1 = ens._c_struct()
+    prob_st, keep2 = prob._c_struct(dev)
+    table = ens.alph_table(alph)
+    ws = ens.mid_workspace(L, dev)
+    b = dict(bufs or {})
+    nstage = 4 if stepper == "rk4" else 1
+
+    def buf(key, *shape):
+        t = b.get(key)
+        if t is None:
+            t = b[key] = torch.empty(*shape, dtype=torch.float32, device=dev)
+        if tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.dtype != torch.float32 or t.device != dev:
+            raise ValueError(f"{key} must be a contiguous float32 tensor of shape {tuple(shape)} on {dev}")
+        return t
+
+    persample, z_out, sums = buf("persample", E, n, 7), buf("z_out", E, n, d + 4), buf("sums", E, 8)
+    head = (C.byref(phi_st), C.byref(prob_st), _lib.ptr(x), n, E, n * d if own else 0,
+            float(tspan[0]), float(tspan[1]), int(nt), _STEPPERS[stepper], _lib.ptr(table))
+    tail = (_lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+    with torch.cuda.device(dev):
+        if record:
+            s_all = buf("s_all", E, nt * nstage, n, d + 1)
+            stride = _act_stride(L, ens, n, nt, stepper)
+            act = None
+            if stride:
+                try:
+                    act = buf("act", E, stride)
+                except torch.OutOfMemoryError:                 # the record is an optimisation: without it the adjoint recomputes
+                    act = None
+            recorded = C.c_int32(0)
+            rc = f_rec(*head, _lib.ptr(z_out), _lib.ptr(persample), _lib.ptr(sums), _lib.ptr(s_all), _lib.ptr(act), C.byref(recorded), *tail)
+            what = "nocf_rollout_record_mid_ensemble_f32"
+            b["recorded"] = bool(recorded.value)
+            b["act"] = act if recorded.value else None
+        else:
+            means = buf("means", E, 8)
+            zF = cF = None
+            if intermediates:
+                cdim = L.nocf_ctrl_dim(C.byref(prob_st), d)
+                zF, cF = buf("zFull", E, nt + 1, n, d + 4), buf("ctrlFull", E, nt + 1, n, cdim)
+            rc = f_eval(*head, _lib.ptr(z_out), _lib.ptr(persample), _lib.ptr(sums), _lib.ptr(means), _lib.ptr(zF), _lib.ptr(cF), *tail)
+            what = "nocf_rollout_mid_ensemble_f32"
+    _lib.check(rc, what)
+    b["table"] = table
+    return b
+
+
+def ensemble_rollout(x, ens, prob, tspan, nt, stepper="rk4", alph=None, intermediates=False, *, noMean=False, W=None, family="lane"):
     """OCflow for every member of an ensemble in one launch.
     :param x:     nex-by-d (every member integrates the same starts) or E-by-nex-by-d (every member its own), float32 on the MI355X
     :param ens:   PhiEnsemble
     :param prob:  Cross2D / SwarmTraj; its target, obstacle, r and mode are common to the members, its alph_Q / alph_W are NOT read:
                   member e takes entries 1 and 2 of its row of alph
     :param alph:  one list of six or E rows of six (default: ens.alph)
+    :param family: "lane" (default): the small-network lane kernels, LANE_LIMITS.  "mid": the one-CU kernels, MID_LIMITS -- also a Quadcopter
+                  problem, e.g. singlequad; member e's values are then OCflow's on the one-CU kernel
     :return: (Jc [E], cs [E, 7]); with intermediates also the trajectories [E, nex, d+4, nt+1] and the controls [E, nex, a, nt+1].
              Member e's values are bit for bit OCflow's on ens.member(e) with a problem of that member's alph_Q / alph_W.
              An evaluation: nothing here is differentiable (ensemble_ocflow_train is)."""
-    E, n, d, _own = _refuse("ensemble_rollout", x, ens, prob, nt, stepper, False, noMean, W)
+    E, n, d, _own = _refuse("ensemble_rollout", x, ens, prob, nt, stepper, False, noMean, W, family)
+    if family == "mid":
+        b = _launch_mid(x, ens, prob, tspan, int(nt), stepper, alph, intermediates)
+        Jc, cs = b["means"][:, 7], b["means"][:, :7]
+        if not intermediates:
+            return Jc, cs
+        # kernel layout is member-major [E, nt+1, nex, .]; the reference's, per member, is [nex, ., nt+1]
+        return Jc, cs, b["zFull"].permute(0, 2, 3, 1), b["ctrlFull"].permute(0, 2, 3, 1)
     b = _launch(x, ens, prob, tspan, int(nt), stepper, alph, intermediates)
     Jc, cs = b["means"][:, 7], b["means"][:, :7]
     if not intermediates:
@@ -380,12 +535,73 @@ class _EnsembleTrain(torch.autograd.Function):
         return (gx,) + (None,) * 6 + tuple(out)
 
 
-def ensemble_ocflow_train(x, ens, prob, tspan, nt, stepper="rk4", alph=None, *, noMean=False, W=None):
+class _EnsembleTrainMid(torch.autograd.Function):
+    """_EnsembleTrain on the one-CU family: one recording forward (nocf_rollout_record_mid_ensemble_f32, with the activation record where the
+    single-network call writes one) and one adjoint launch (nocf_rollout_bwd_mid_ensemble_f32, nocf_mid_grad_rows partial vectors per member)"""
+
+    @staticmethod
+    def forward(ctx, x, ens, prob, tspan, nt, stepper, alph, *params):
+        ctx.x_needs_grad = bool(x.requires_grad)
+        b = _launch_mid(x, ens, prob, tspan, nt, stepper, alph, record=True)
+        ctx.ens, ctx.prob, ctx.tspan, ctx.nt, ctx.stepper, ctx.table = ens, prob, tspan, nt, stepper, b["table"]
+        ctx.act = b["act"]
+        ctx.save_for_backward(b["s_all"], b["z_out"])
+        ctx.param_versions = [p._version for _, p in ens._params()]
+        sums, a = b["sums"], b["table"]
+        means = sums[:, :7] / sums[:, 7:8]
+        Jc = means[:, 0] + a[:, 0] * means[:, 1] + a[:, 3] * means[:, 2] + a[:, 4] * means[:, 3] + a[:, 5] * means[:, 4]
+        cs = means.detach()
+        ctx.mark_non_differentiable(cs)
+        return Jc, cs
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gJ, _gmeans):
+        s_all, z_out = ctx.saved_tensors
+        ens, prob, nt = ctx.ens, ctx.prob, ctx.nt
+        if [p._version for _, p in ens._params()] != ctx.param_versions:
+            raise RuntimeError("ensemble backward: a parameter of the ensemble was modified in place (optimizer step, load_state_dict) "
+                               "between this forward and its backward; call backward() before changing the parameters.")
+        dev = s_all.device
+        E, m, d = ens.members, ens.m, ens.d
+        D1 = d + 1
+        n = z_out.shape[1]
+        L, (_f_eval, _f_rec, f_bwd) = _shipped_mid()
+        phi_st, keep1 = ens._c_struct()
+        prob_st, keep2 = prob._c_struct(dev)
+        ws = ens.mid_workspace(L, dev)
+        hs = _step_sizes(ctx.tspan, nt).to(dev)
+        P = int(L.nocf_small_grad_floats(d, m))
+        rows = int(L.nocf_mid_grad_rows(d, m, ens.nTh, ens.r, int(prob_st.n_agents), n))
+        if rows == 0:
+            raise RuntimeError("ensemble backward: the one-CU adjoint does not take this shape (NOCF_MONO / NOCF_MONO_BWD switched off?)")
+        gpart = torch.empty(E, rows, P, device=dev)
+        lam0 = torch.empty(E, n, d, device=dev) if ctx.x_needs_grad else None
+        with torch.cuda.device(dev):
+            rc = f_bwd(C.byref(phi_st), C.byref(prob_st), n, E, int(nt), _STEPPERS[ctx.stepper], float(ctx.tspan[1]),
+                       _lib.ptr(ctx.table), 1.0 / float(n), _lib.ptr(s_all), _lib.ptr(z_out), _lib.ptr(hs), _lib.ptr(ctx.act),
+                       _lib.ptr(gpart), rows, _lib.ptr(lam0), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+        _lib.check(rc, "nocf_rollout_bwd_mid_ensemble_f32")
+        ctx.act = None
+        # per member the sum and the products of the single-network adjoint: train._unpack_partials on the member's contiguous [rows, P] block
+        A = ens.A.detach()
+        per = [_unpack_partials(gpart[e], m, D1, _MemberA(A[e])) for e in range(E)]
+        out = []
+        for name, p in ens._params():
+            g = torch.stack([per[e][name] for e in range(E)])
+            out.append(gJ.reshape((E,) + (1,) * (g.dim() - 1)) * g)
+        gx = gJ.reshape(E, 1, 1) * lam0 if lam0 is not None else None
+        return (gx,) + (None,) * 6 + tuple(out)
+
+
+def ensemble_ocflow_train(x, ens, prob, tspan, nt, stepper="rk4", alph=None, *, noMean=False, W=None, family="lane"):
     """(Jc [E], cs [E, 7]) with Jc differentiable in every stacked parameter of `ens` (and in x when every member has its own starts):
     one recording forward and one adjoint launch for all members.  Member e's Jc, gradients and x.grad[e] are bit for bit those of
     ocflow_train + backward() on ens.member(e) alone; an upstream gradient gJ [E] scales each member's, the members do not interact.
-    Cross2D problems (the lane adjoint's); arguments as for ensemble_rollout."""
-    _refuse("ensemble_ocflow_train", x, ens, prob, nt, stepper, True, noMean, W)
+    Cross2D problems (the lane adjoint's); family="mid": all three problem classes, 32 < m (the one-CU adjoint's).  Arguments as for
+    ensemble_rollout."""
+    _refuse("ensemble_ocflow_train", x, ens, prob, nt, stepper, True, noMean, W, family)
     params = [p for _, p in ens._params()]
-    Jc, means = _EnsembleTrain.apply(x, ens, prob, [float(tspan[0]), float(tspan[1])], int(nt), stepper, alph, *params)
+    fn = _EnsembleTrainMid if family == "mid" else _EnsembleTrain
+    Jc, means = fn.apply(x, ens, prob, [float(tspan[0]), float(tspan[1])], int(nt), stepper, alph, *params)
     return Jc, means

@@ -27,7 +27,9 @@ undisturbed.  EPS = 0 (default) is the run without the flag.
 for all of them (neuraloc_amd.ensemble).  Member e is the network the run with --seed SEED+e builds; all members see
 member 0's batches.  FILE: E lines of six comma-separated multipliers, one member each (default: every member uses --alph).  One log line per
 member and iteration, the usual line prefixed by "m<e>"; one checkpoint per member in the reference's layout, ..._m<e>_checkpt.pth, each
-keeping that member's own best.  The small-network shapes only; not with --prec double, --noise, --adv, --resume or more than one rank."""
+keeping that member's own best.  The small-network shapes only; not with --prec double, --noise, --adv, --resume or more than one rank.
+--members_family mid (addition, with --members): the ensemble runs on the one-CU kernels instead: 32 < m <= 128,
+d + 1 <= 32, every problem class -- --data singlequad, and --m 64 / 128 on the point-agent problems.  The default, lane, is the above."""
 import argparse
 import datetime
 import os
@@ -82,9 +84,11 @@ _FLAGS = [
     ("members", int, None, "(addition) E >= 1: train E networks of this shape in one process, one launch per rollout for all of them "
                         "(neuraloc_amd.ensemble); member e is seeded --seed + e; single precision, one rank, the small-network shapes only"),
     ("members_alph", str, None, "(addition, with --members) file of E lines of six comma-separated multipliers, one member each (default: --alph)"),
+    ("members_family", str, "lane", "(addition, with --members) lane: the small-network lane kernels; mid: the one-CU kernels "
+                                    "(32 < m <= 128, d + 1 <= 32, every problem class, singlequad among them)"),
 ]
 _CHOICES = {"data": PROBLEM_NAMES, "optim": ["adam"], "prec": ["single", "double"], "approach": ["ocflow"], "noise_rng": ["torch", "counter"],
-            "adv_mode": ["free", "pgd"], "adv_objective": ["Jc", "control"]}
+            "adv_mode": ["free", "pgd"], "adv_objective": ["Jc", "control"], "members_family": list(na.ensemble.FAMILIES)}
 
 
 def parse_args(argv=None):
@@ -112,7 +116,8 @@ def members_refusals(args, world):
         raise SystemExit("--members does not take --resume: a checkpoint holds one network")
     if args.lr_reload == "clone":
         raise SystemExit("--members keeps the reference's --lr_reload alias only")
-    if args.data not in PROBLEM_NAMES or args.data == "singlequad":
+    mid = args.members_family == "mid"
+    if args.data not in PROBLEM_NAMES or (args.data == "singlequad" and not mid):
         raise SystemExit("--members takes the point-agent problems only")
     if len(args.alph) < 6:
         raise SystemExit("--alph needs 6 entries")
@@ -125,6 +130,12 @@ def members_refusals(args, world):
     # the shape, known without a device: the ensemble runs on the small-network kernels, whose adjoint takes Cross2D agents (ensemble.LANE_LIMITS)
     prob, x0, _x0v, _xInit = initProb(args.data, 1, 1, var0=args.var0, alph=args.alph, cvt=lambda t: t.float())
     d = x0.size(1)
+    if mid:
+        # (the one-CU kernels and their adjoint: ensemble.MID_LIMITS; Phi's default rank of A is min(10, d + 1))
+        if not na.ensemble._mid_eligible(args.nTh, args.m, d, min(10, d + 1), int(prob.nAgents), train=True):
+            raise SystemExit("--members --members_family mid: {:} with m={:}, nTh={:} (d={:}) is outside the one-CU kernels this ensemble runs "
+                             "on: {:}".format(args.data, args.m, args.nTh, d, na.ensemble.MID_LIMITS))
+        return rows
     if not (args.nTh == 2 and 1 <= args.m <= 32 and d + 1 <= 32 and isinstance(prob, na.Cross2D) and prob.nAgents <= 16):
         raise SystemExit("--members: {:} with m={:}, nTh={:} (d={:}) is outside the small-network kernels an ensemble runs on: {:}, Cross2D "
                          "agents for training".format(args.data, args.m, args.nTh, d, na.ensemble.LANE_LIMITS))
@@ -171,7 +182,7 @@ def train_members(args, rows):
     end = time.time()
     for itr in range(1, args.niters + 1):
         optim.zero_grad()
-        Jc, cs = na.ensemble_ocflow_train(x0, ens, prob, tspan, args.nt, "rk4")
+        Jc, cs = na.ensemble_ocflow_train(x0, ens, prob, tspan, args.nt, "rk4", family=args.members_family)
         Jc.sum().backward()                               # (upstream gradient 1 for every member: E independent gradients)
         torch.cuda.synchronize()
         optim.step()
@@ -183,7 +194,7 @@ def train_members(args, rows):
         if itr % args.val_freq == 0 or itr == args.niters:
             with torch.no_grad():
                 prob.eval()
-                vl, vcs = na.ensemble_rollout(x0v, ens, prob, tspan, args.nt, "rk4")
+                vl, vcs = na.ensemble_rollout(x0v, ens, prob, tspan, args.nt, "rk4", family=args.members_family)
                 vh, vch = vl.tolist(), vcs.tolist()
                 for e in range(E):
                     lines[e] += "    {:9.2e}  {:8.2e}  {:8.2e}  {:8.2e}  {:8.2e}  {:8.2e}  {:8.2e}  {:8.2e} ".format(vh[e], *vch[e])
@@ -235,7 +246,7 @@ def main(argv=None):
         raise SystemExit("--adv_objective control needs --adv_mode pgd: the free adversary climbs the training loss itself")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
-    if args.members is not None or args.members_alph is not None:
+    if args.members is not None or args.members_alph is not None or args.members_family != "lane":
         return train_members(args, members_refusals(args, world))
     if world > 1:
         import torch.distributed as dist
