@@ -532,6 +532,44 @@ int nocf_rollout_bwd_mid_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, 
                                       void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Ensembles under in-kernel Brownian noise: the four forward launches above (nocf_rollout_ensemble_f32 / nocf_rollout_record_ensemble_f32 on
+ * the lane kernels, nocf_rollout_mid_ensemble_f32 / nocf_rollout_record_mid_ensemble_f32 on the one-CU kernels) with the per-step disturbance
+ * of nocf_rollout_noisy_f32 drawn inside the kernel, every member at ITS OWN noise level and seed.  Behind x_member_stride they take
+ *   scale      device [E, d], float32: row e = fp32(sigma_i sqrt(h)) of member e, the `scale` of nocf_rollout_noisy_f32 (a row of zeros: that
+ *              member's rollout is the undisturbed one)
+ *   seeds      device [E], uint64: member e's seed
+ *   row0       >= 0: the key of row 0 of EVERY member.  Row j of member e meets the disturbance of (seeds[e], row0 + j, k, i) -- the row INSIDE
+ *              the member, so members given one seed meet identical noise (common random numbers across the levels), and a member's rows may
+ *              be cut into chunks as the rows of nocf_rollout_noisy_f32 may
+ * and every other argument, buffer layout (lane: time-major over E*n rows; one-CU: member-major) and refusal is the undisturbed sibling's.
+ * Member e's results carry the bits of nocf_rollout_noisy_f32 / nocf_rollout_record_noisy_f32 with (scale + e d, seeds[e], row0) on that
+ * member alone, on the same kernel family.  The adjoints are the undisturbed ensembles' (nocf_rollout_bwd_small_ensemble_f32 /
+ * nocf_rollout_bwd_mid_ensemble_f32) on the recorded displaced states: the disturbance does not depend on the parameters.
+ * scale == NULL or seeds == NULL: NOCF_E_NULL; row0 < 0: NOCF_E_SHAPE.  nocf_last_rollout_kernel(): "rollout_lane_kernel<ens,noisy>" /
+ * "rollout_mono_kernel<ens,noisy>".  Probe for the symbols: nocf_version() did not change with them.
+ */
+int nocf_rollout_noisy_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members, int64_t x_member_stride,
+                                    const float* scale, const uint64_t* seeds, int64_t row0,
+                                    double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                    float* z_out, float* persample, float* cost_sums, float* cost_means, float* zFull, float* ctrlFull,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+int nocf_rollout_record_noisy_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members,
+                                           int64_t x_member_stride, const float* scale, const uint64_t* seeds, int64_t row0,
+                                           double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                           float* z_out, float* persample, float* cost_sums, float* s_all,
+                                           void* workspace, size_t workspace_bytes, void* stream);
+int nocf_rollout_noisy_mid_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members, int64_t x_member_stride,
+                                        const float* scale, const uint64_t* seeds, int64_t row0,
+                                        double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                        float* z_out, float* persample, float* cost_sums, float* cost_means, float* zFull, float* ctrlFull,
+                                        void* workspace, size_t workspace_bytes, void* stream);
+int nocf_rollout_record_noisy_mid_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members,
+                                               int64_t x_member_stride, const float* scale, const uint64_t* seeds, int64_t row0,
+                                               double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                               float* z_out, float* persample, float* cost_sums, float* s_all, float* act_rec, int32_t* recorded,
+                                               void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * The STATE-ONLY adjoint: the lambda recursion of the three adjoints above (nocf_rollout_bwd_small_f32 / _mid_f32 / _act_f32) with every
  * parameter-gradient operation compiled out -- no gradient rows or accumulators, no outer products, no partial vectors, no row streams --
  * and the per-step state cotangents written out.  The inner loop of a worst-case disturbance search (nocf_disturbance_ascent_f32) and

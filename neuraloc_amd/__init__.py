@@ -15,6 +15,7 @@ from .adversary import disturbance_gradient, worst_case_disturbances
 from .noise import counter_disturbances, noisy_rollout, noisy_ocflow_train
 from .minmax import minmax_ocflow_train, ascend_disturbances, adversarial_step, pgd_ocflow_train
 from .ensemble import PhiEnsemble, ensemble_rollout, ensemble_ocflow_train
+from .ensemble_noise import ensemble_noisy_rollout, ensemble_noisy_ocflow_train, ensemble_noise_study
 
 __all__ = ["Phi", "ResNN", "antiderivTanh", "derivTanh", "OCflow", "ocG", "Cross2D", "SwarmTraj",
            "Quadcopter", "initProb", "resample", "OCflow_sharded", "shard_rows", "reduce_cost_sums", "check_errors",
@@ -23,4 +24,5 @@ __all__ = ["Phi", "ResNN", "antiderivTanh", "derivTanh", "OCflow", "ocG", "Cross
            "disturbed_rollout", "brownian_disturbances", "noise_study", "disturbed_ocflow_train",
            "disturbance_gradient", "worst_case_disturbances",
            "minmax_ocflow_train", "ascend_disturbances", "adversarial_step", "pgd_ocflow_train",
-           "PhiEnsemble", "ensemble_rollout", "ensemble_ocflow_train"]
+           "PhiEnsemble", "ensemble_rollout", "ensemble_ocflow_train",
+           "ensemble_noisy_rollout", "ensemble_noisy_ocflow_train", "ensemble_noise_study"]

@@ -1836,10 +1836,14 @@ static int ensemble_check(const NocfPhi* phi, const NocfProb* prob, int64_t n, i
     return 0;
 }
 
+// the noise of a noisy ensemble (nocf_rollout_noisy_ensemble_f32, nocf_rollout_noisy_mid_ensemble_f32): device tables scale [E, d] and seeds [E],
+// and the key of every member's row 0
+struct EnsNoiseSpec { const float* scale; const uint64_t* seeds; int64_t row0; };
+
 static int rollout_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members, int64_t x_member_stride,
                                  double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
                                  float* z_out, float* persample, float* cost_sums, float* cost_means, float* zFull, float* ctrlFull,
-                                 float* s_all, void* stream) {
+                                 float* s_all, void* stream, const EnsNoiseSpec* noise = nullptr) {
     DevProb pb;
     const int rc = ensemble_check(phi, prob, n, members, nt, stepper, false, &pb);
     if (rc) return rc;
@@ -1855,11 +1859,13 @@ static int rollout_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, const
     ra.z_out = z_out; ra.persample = persample; ra.zFull = zFull; ra.ctrlFull = ctrlFull;
     ra.cdim = nocf_ctrl_dim(prob, phi->d);
     ra.sAll = s_all;
+    if (noise) ra.nzRow0 = (long)noise->row0;             // (the scale and the seed are per member: EnsNoiseArgs)
     LaneArgs la;
     memset(&la, 0, sizeof(la));
     la.P = DevPhi{phi->K0, phi->b0, phi->K, phi->b, phi->w, phi->A, phi->cw, phi->cb_dev};
     la.d = phi->d; la.m = phi->m; la.r = phi->r; la.nAg = pb.nAgents;
     const EnsArgs ea{(unsigned)n, (long)x_member_stride, alph};
+    const EnsNoiseArgs nz{noise ? noise->scale : nullptr, noise ? reinterpret_cast<const unsigned long long*>(noise->seeds) : nullptr};
     const int grid = (int)((rows + 3) / 4);
     const int MPsel = phi->m <= 16 ? 16 : 32;
     const int DPsel = phi->d + 1 <= 8 ? 8 : (phi->d + 1 <= 16 ? 16 : 32);
@@ -1868,14 +1874,16 @@ static int rollout_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, const
         if (hipEventCreate(&ev0) || hipEventCreate(&ev1)) return (int)hipErrorUnknown;
         (void)hipEventRecord(ev0, st);
     }
-#define NOCF_LANE_ENS_LAUNCH(MPV, DPV) do { if (s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 0, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea); \
-                                             else hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 0, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea); } while (0)
+#define NOCF_LANE_ENS_LAUNCH(MPV, DPV) do { if (noise && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 2, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz); \
+                                             else if (noise) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 2, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz); \
+                                             else if (s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 0, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz); \
+                                             else hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 0, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz); } while (0)
     if (MPsel == 16) { if (DPsel == 8) { NOCF_LANE_ENS_LAUNCH(16, 8); } else if (DPsel == 16) { NOCF_LANE_ENS_LAUNCH(16, 16); } else { NOCF_LANE_ENS_LAUNCH(16, 32); } }
     else             { if (DPsel == 8) { NOCF_LANE_ENS_LAUNCH(32, 8); } else if (DPsel == 16) { NOCF_LANE_ENS_LAUNCH(32, 16); } else { NOCF_LANE_ENS_LAUNCH(32, 32); } }
 #undef NOCF_LANE_ENS_LAUNCH
     hipError_t e = hipGetLastError();
     if (e) return (int)e;
-    g_last_kernel = "rollout_lane_kernel<ens>";
+    g_last_kernel = noise ? "rollout_lane_kernel<ens,noisy>" : "rollout_lane_kernel<ens>";
     g_last_errp = nullptr;
     if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
     if (cost_sums) {
@@ -1903,6 +1911,33 @@ int nocf_rollout_record_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, c
     if (!s_all || !z_out) return NOCF_E_NULL;
     return rollout_ensemble_impl(phi, prob, x, n, members, x_member_stride, t0, t1, nt, stepper, alph, z_out, persample, cost_sums, nullptr,
                                  nullptr, nullptr, s_all, stream);
+}
+
+// the same two under in-kernel Brownian noise, every member at its own level and seed
+int nocf_rollout_noisy_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members, int64_t x_member_stride,
+                                    const float* scale, const uint64_t* seeds, int64_t row0,
+                                    double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                    float* z_out, float* persample, float* cost_sums, float* cost_means, float* zFull, float* ctrlFull,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+    (void)workspace; (void)workspace_bytes;
+    if (!scale || !seeds) return NOCF_E_NULL;
+    if (row0 < 0) return NOCF_E_SHAPE;
+    const EnsNoiseSpec nz{scale, seeds, row0};
+    return rollout_ensemble_impl(phi, prob, x, n, members, x_member_stride, t0, t1, nt, stepper, alph, z_out, persample, cost_sums, cost_means,
+                                 zFull, ctrlFull, nullptr, stream, &nz);
+}
+
+int nocf_rollout_record_noisy_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members,
+                                           int64_t x_member_stride, const float* scale, const uint64_t* seeds, int64_t row0,
+                                           double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                           float* z_out, float* persample, float* cost_sums, float* s_all,
+                                           void* workspace, size_t workspace_bytes, void* stream) {
+    (void)workspace; (void)workspace_bytes;
+    if (!scale || !seeds || !s_all || !z_out) return NOCF_E_NULL;
+    if (row0 < 0) return NOCF_E_SHAPE;
+    const EnsNoiseSpec nz{scale, seeds, row0};
+    return rollout_ensemble_impl(phi, prob, x, n, members, x_member_stride, t0, t1, nt, stepper, alph, z_out, persample, cost_sums, nullptr,
+                                 nullptr, nullptr, s_all, stream, &nz);
 }
 
 int nocf_rollout_bwd_small_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper, double t1,
@@ -2165,13 +2200,13 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
             (void)hipEventRecord(ev0, st);
         }
         const size_t laneLds = ticket ? (size_t)(256 * 7 * 8 + 16) : 0;      // (the last-workgroup reduction's scratch: only with a ticket)
-#define NOCF_LANE_LAUNCH(MPV, DPV) do { if (dmode == 2 && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 2>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}); \
-                                         else if (dmode == 2) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 2>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}); \
-                                         else if (dist && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 1>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}); \
-                                         else if (dist) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 1>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}); \
-                                         else if (s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}); \
-                                         else if (ticket) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, true>), dim3(grid), dim3(256), laneLds, st, la, pb, ra, EnsArgs{}); \
-                                         else hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}); } while (0)
+#define NOCF_LANE_LAUNCH(MPV, DPV) do { if (dmode == 2 && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 2>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}); \
+                                         else if (dmode == 2) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 2>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}); \
+                                         else if (dist && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 1>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}); \
+                                         else if (dist) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 1>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}); \
+                                         else if (s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}); \
+                                         else if (ticket) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, true>), dim3(grid), dim3(256), laneLds, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}); \
+                                         else hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}); } while (0)
         if (MPsel == 16) { if (DPsel == 8) { NOCF_LANE_LAUNCH(16, 8); } else if (DPsel == 16) { NOCF_LANE_LAUNCH(16, 16); } else { NOCF_LANE_LAUNCH(16, 32); } }
         else             { if (DPsel == 8) { NOCF_LANE_LAUNCH(32, 8); } else if (DPsel == 16) { NOCF_LANE_LAUNCH(32, 16); } else { NOCF_LANE_LAUNCH(32, 32); } }
 #undef NOCF_LANE_LAUNCH
@@ -2247,7 +2282,8 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
         if (mono_rec) { ra.act = act; ra.actRows = (long)nt * ((stepper == NOCF_RK4) ? 4 : 1) * n; }
         MonoEnsArgs noEns;                            // (read by the ENS instantiations only: nocf_rollout_mid_ensemble_f32)
         memset(&noEns, 0, sizeof(noEns));
-        void* args[] = {(void*)&mpp, (void*)&pb, (void*)&ws, (void*)&ra, (void*)&noEns};
+        EnsNoiseArgs noNz{nullptr, nullptr};          // (read by the noisy ENS instantiations only: nocf_rollout_noisy_mid_ensemble_f32)
+        void* args[] = {(void*)&mpp, (void*)&pb, (void*)&ws, (void*)&ra, (void*)&noEns, (void*)&noNz};
         e = hipLaunchKernel(fk, dim3((int)((n + 15) / 16)), dim3(256), args, ldsBytes, st); if (e) return (int)e;
         ra.act = nullptr; ra.actRows = 0;
         if (mono_rec && act_recorded) *act_recorded = 1;
@@ -2899,7 +2935,8 @@ static int mid_ensemble_pack(const NocfPhi* phi, const DevPlan& pl, const MonoPl
 static int rollout_mid_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members, int64_t x_member_stride,
                                      double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
                                      float* z_out, float* persample, float* cost_sums, float* cost_means, float* zFull, float* ctrlFull,
-                                     float* s_all, float* act, int32_t* act_recorded, void* workspace, size_t workspace_bytes, void* stream) {
+                                     float* s_all, float* act, int32_t* act_recorded, void* workspace, size_t workspace_bytes, void* stream,
+                                     const EnsNoiseSpec* noise = nullptr) {
     if (act_recorded) *act_recorded = 0;
     DevProb pb;
     DevPlan pl;
@@ -2925,6 +2962,8 @@ static int rollout_mid_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, c
     // the activation record under the single-network rule (rollout_impl): the ensemble takes the arithmetic path of the call it stands for
     const bool mono_rec = act && s_all && (phi->m % 16) == 0 && phi->m > 32;
     if (mono_rec) { ra.act = act; ra.actRows = (long)nt * nstage * n; }
+    if (noise) ra.nzRow0 = (long)noise->row0;             // (the scale and the seed are per member: EnsNoiseArgs)
+    EnsNoiseArgs nz{noise ? noise->scale : nullptr, noise ? reinterpret_cast<const unsigned long long*>(noise->seeds) : nullptr};
     MonoEnsArgs en;
     memset(&en, 0, sizeof(en));
     en.n = (unsigned)n; en.tiles = (unsigned)((n + 15) / 16); en.xs = (long)x_member_stride; en.wss = (long)(mono_ens_ws_stride(mpl) / 4);
@@ -2933,8 +2972,10 @@ static int rollout_mid_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, c
     en.acts = (long)mono_ens_act_stride(phi, n, nt, stepper);
     const size_t ldsBytes = (size_t)mpl.pp.ldsFloats * 4;
     const void* fk = nullptr;
-#define NOCF_MONO_ENS_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) fk = s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, 0, true>) \
-                                                                                   : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 0, true>);
+#define NOCF_MONO_ENS_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) fk = noise ? (s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, 2, true>) \
+                                                                                                 : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 2, true>)) \
+                                                                                 : s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, 0, true>) \
+                                                                                         : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 0, true>);
     MONO_SHAPES(NOCF_MONO_ENS_PICK)
 #undef NOCF_MONO_ENS_PICK
     if (!fk) return NOCF_E_SHAPE;
@@ -2947,11 +2988,11 @@ static int rollout_mid_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, c
         (void)hipEventRecord(ev0, st);
     }
     const MonoPlan* mpp = reinterpret_cast<const MonoPlan*>(ws + mpl.pp.oPlan);
-    void* args[] = {(void*)&mpp, (void*)&pb, (void*)&ws, (void*)&ra, (void*)&en};
+    void* args[] = {(void*)&mpp, (void*)&pb, (void*)&ws, (void*)&ra, (void*)&en, (void*)&nz};
     e = hipLaunchKernel(fk, dim3((unsigned)((long)members * en.tiles)), dim3(256), args, ldsBytes, st);
     if (e) return (int)e;
     if (mono_rec && act_recorded) *act_recorded = 1;
-    g_last_kernel = "rollout_mono_kernel<ens>";
+    g_last_kernel = noise ? "rollout_mono_kernel<ens,noisy>" : "rollout_mono_kernel<ens>";
     g_last_errp = nullptr;
     e = hipGetLastError();
     if (e) return (int)e;
@@ -3007,6 +3048,47 @@ int nocf_rollout_record_mid_ensemble_f32(const NocfPhi* phi, const NocfProb* pro
     if (!s_all || !z_out) return NOCF_E_NULL;
     return rollout_mid_ensemble_impl(phi, prob, x, n, members, x_member_stride, t0, t1, nt, stepper, alph, z_out, persample, cost_sums, nullptr,
                                      nullptr, nullptr, s_all, act_rec, recorded, workspace, workspace_bytes, stream);
+#endif
+}
+
+// the same two under in-kernel Brownian noise, every member at its own level and seed
+int nocf_rollout_noisy_mid_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members, int64_t x_member_stride,
+                                        const float* scale, const uint64_t* seeds, int64_t row0,
+                                        double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                        float* z_out, float* persample, float* cost_sums, float* cost_means, float* zFull, float* ctrlFull,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+#ifdef NOCF_JIT_ONLY
+    (void)phi; (void)prob; (void)x; (void)n; (void)members; (void)x_member_stride; (void)scale; (void)seeds; (void)row0;
+    (void)t0; (void)t1; (void)nt; (void)stepper; (void)alph;
+    (void)z_out; (void)persample; (void)cost_sums; (void)cost_means; (void)zFull; (void)ctrlFull; (void)workspace; (void)workspace_bytes; (void)stream;
+    return NOCF_E_SHAPE;
+#else
+    if (!scale || !seeds) return NOCF_E_NULL;
+    if (row0 < 0) return NOCF_E_SHAPE;
+    const EnsNoiseSpec nz{scale, seeds, row0};
+    return rollout_mid_ensemble_impl(phi, prob, x, n, members, x_member_stride, t0, t1, nt, stepper, alph, z_out, persample, cost_sums, cost_means,
+                                     zFull, ctrlFull, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream, &nz);
+#endif
+}
+
+int nocf_rollout_record_noisy_mid_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members,
+                                               int64_t x_member_stride, const float* scale, const uint64_t* seeds, int64_t row0,
+                                               double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                               float* z_out, float* persample, float* cost_sums, float* s_all, float* act_rec, int32_t* recorded,
+                                               void* workspace, size_t workspace_bytes, void* stream) {
+#ifdef NOCF_JIT_ONLY
+    (void)phi; (void)prob; (void)x; (void)n; (void)members; (void)x_member_stride; (void)scale; (void)seeds; (void)row0;
+    (void)t0; (void)t1; (void)nt; (void)stepper; (void)alph;
+    (void)z_out; (void)persample; (void)cost_sums; (void)s_all; (void)act_rec; (void)workspace; (void)workspace_bytes; (void)stream;
+    if (recorded) *recorded = 0;
+    return NOCF_E_SHAPE;
+#else
+    if (recorded) *recorded = 0;
+    if (!scale || !seeds || !s_all || !z_out) return NOCF_E_NULL;
+    if (row0 < 0) return NOCF_E_SHAPE;
+    const EnsNoiseSpec nz{scale, seeds, row0};
+    return rollout_mid_ensemble_impl(phi, prob, x, n, members, x_member_stride, t0, t1, nt, stepper, alph, z_out, persample, cost_sums, nullptr,
+                                     nullptr, nullptr, s_all, act_rec, recorded, workspace, workspace_bytes, stream, &nz);
 #endif
 }
 

@@ -40,13 +40,18 @@ struct EnsArgs { unsigned n; long xs; const float* alph; };
 // recording forward of disturbed training): the next step's first stage input is formed from the displaced z, so it is recorded displaced
 // DIST == 2: the same with the entry drawn here (nocf_noise.inc: RollArgs::nzScale / nzSeed / nzRow0) where DIST == 1 loads it -- into the same
 // register, at the top of the step, so every instruction behind it is shared.  Tail waves draw the noise of the row they replicate
-// ENS: an ensemble of E networks of one shape in one launch (DIST = 0, ONE = false).  A wave is a whole sample and nothing in a workgroup is
+// ENS: an ensemble of E networks of one shape in one launch (DIST = 0 or 2, ONE = false).  A wave is a whole sample and nothing in a workgroup is
 // shared, so the only change is WHICH network, multipliers and start a wave reads: the member e = row / ensN is wave-uniform and is kept, with
 // the member's eight tensor pointers and its row of the multiplier table, in scalar registers; every statement of the rollout behind these
 // reads is the single-network one, so member e's rows carry the bits of the single-network call on that member.  Every ENS test is
 // `if constexpr`: the other instantiations carry no trace of it
+// ENS with DIST == 2: every member under its own noise level and seed (EnsNoiseArgs, nocf_noise.inc).  Both are wave-uniform like the member's
+// pointers: lane j < d reads scale[e * d + j], the seed is seeds[e], and the key of a row is RollArgs::nzRow0 + the row INSIDE the member --
+// members given one seed meet the same noise.  Behind these reads the DIST == 2 statements, so member e carries the bits of the single-network
+// noisy call
 template <int MP, int DP, bool REC, bool ONE = false, int DIST = 0, bool ENS = false>
-__global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb pb, RollArgs ra, EnsArgs ea) {
+__global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb pb, RollArgs ra, EnsArgs ea, EnsNoiseArgs nz) {
+    static_assert(!ENS || DIST != 1, "a disturbed ensemble draws its noise (DIST == 2): there is no tensor-W ensemble");
     const int lane = threadIdx.x & 63;
     const long sample = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const bool live = sample < ra.n;
@@ -56,6 +61,8 @@ __global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb 
     const float* xrow = ra.x;                           // (ENS: the member's block of starts, indexed by the row inside the member)
     long xr = row;
     float eA0 = 0.f, eAQ = 0.f, eAW = 0.f;              // ENS: the member's alph[0], alph_Q, alph_W
+    const float* nzScale = ra.nzScale;                  // DIST == 2: the noise scale [d] and seed of this wave's rows (ENS: the member's)
+    unsigned long long nzSeed = ra.nzSeed;
     if constexpr (ENS) {
         const unsigned e = (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)row / ea.n));
         P.K0 += (long)e * m * D1; P.b0 += (long)e * m; P.K += (long)e * m * m; P.b += (long)e * m; P.w += (long)e * m;
@@ -63,6 +70,7 @@ __global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb 
         xrow += (long)e * ea.xs; xr = row - (long)e * ea.n;
         const float* at = ea.alph + (long)e * 6;
         eA0 = at[0]; eAQ = at[1]; eAW = at[2];
+        if constexpr (DIST == 2) { nzScale = nz.scale + (long)e * d; nzSeed = nz.seeds[e]; }
     }
     // the multipliers and the decisions they take: the problem's (one network), the member's (ENS) -- wave-uniform either way
     auto wantWp = [&]() -> bool { if constexpr (ENS) return eAW != 0.f; else return want_W(pb); };
@@ -92,7 +100,7 @@ __global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb 
     const float cw = lane < D1 ? P.cw[lane] : 0.f;
     const float xt = lane < d ? pb.xtarget[lane] : 0.f;
     float nzs = 0.f;                                    // this lane's component of sigma sqrt(h)
-    if constexpr (DIST == 2) nzs = lane < d ? ra.nzScale[lane] : 0.f;
+    if constexpr (DIST == 2) nzs = lane < d ? nzScale[lane] : 0.f;
 
     // ---- agent pairs handled by this lane (two trips cover up to 128 pairs; eligibility keeps N <= 15)
     const int npairs = (N * (N - 1)) / 2;
@@ -201,7 +209,7 @@ __global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb 
         const double hsd = t1k - tk;                      // stepRK4 re-derives h = t1 - t0 (src/OCflow.py:170)
         const float hs = (float)hsd;
         float wk = 0.f;
-        if constexpr (DIST == 2) wk = lane < d ? noise_value(nzs, ra.nzSeed, ra.nzRow0 + row, k, lane) : 0.f;
+        if constexpr (DIST == 2) wk = lane < d ? noise_value(nzs, nzSeed, ra.nzRow0 + (ENS ? xr : row), k, lane) : 0.f;
         else if constexpr (DIST == 1) wk = lane < d ? ra.dist[((long)k * ra.n + row) * d + lane] : 0.f;
         // training: the stage input s = [x, t] of every evaluation goes to sAll[(k*nstage + st)][sample][0..d] (one row per lane group)
         auto record = [&](int st, int nstage, float s) {

@@ -199,11 +199,15 @@ __device__ __forceinline__ void mono_sincos(float x, float& sn, float& cs) {
 // disturbed training): the state rows SB hold the displaced state when the next step's first stage input and activations are recorded
 // DIST == 2: the entries are drawn (nocf_noise.inc: RollArgs::nzScale / nzSeed / nzRow0) where DIST == 1 ADDS them, behind the last stage, into the
 // same variable: nothing is held across the step's evaluations (drawn at the top of the step like the loads, the (4, 2) instantiation lost a wave)
-// ENS (DIST = 0): an ensemble, see MonoEnsArgs.  ra.n is a member's row count; member e = blockIdx.x / en.tiles is workgroup-uniform, the
+// ENS (DIST = 0 or 2): an ensemble, see MonoEnsArgs.  ra.n is a member's row count; member e = blockIdx.x / en.tiles is workgroup-uniform, the
 // member's last tile replicates the member's row n - 1.  Every ENS test is a compile-time choice at its place of use.
+// ENS with DIST == 2 (nocf_rollout_noisy_mid_ensemble_f32, DESIGN 3.14): member e under its own noise level and seed, EnsNoiseArgs (nocf_noise.inc)
+// as a further last argument that no other instantiation reads.  row0 is the tile's first row INSIDE the member, so ra.nzRow0 + row0 + s_ is
+// already the key of a row; the kernel's copy of `ra` takes the member's scale row and seed, and both places that draw read them from there
 template <int KBM, int KBD, bool REC, int DIST = 0, bool ENS = false>
-__global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __restrict__ mpp, DevProb pb, float* ws, RollArgs ra, MonoEnsArgs en) {
-    static_assert(!ENS || DIST == 0, "ensembles are undisturbed rollouts");
+__global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __restrict__ mpp, DevProb pb, float* ws, RollArgs ra, MonoEnsArgs en,
+                                                           EnsNoiseArgs nz) {
+    static_assert(!ENS || DIST != 1, "a disturbed ensemble draws its noise (DIST == 2): there is no tensor-W ensemble");
     constexpr int MT = (KBM + 3) / 4;              // hidden M-tiles per wave: tiles w, w+4, ...
     constexpr int T = 16;
     constexpr MonoFwdLds LL = mono_fwd_lds(KBM, KBD);
@@ -241,6 +245,10 @@ __global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __res
         const long eo = (long)(blockIdx.x / en.tiles) * en.n;
         if (ra.persample) ra.persample += eo * 7;
         if (ra.z_out) ra.z_out += eo * (d + 4);
+        if constexpr (DIST == 2) {                 // the member's row of the scale table [E, d] and its seed (workgroup-uniform)
+            const unsigned e = blockIdx.x / en.tiles;
+            ra.nzScale = nz.scale + (long)e * d; ra.nzSeed = nz.seeds[e];
+        }
     }
     // time parameters of this tile's rows: the launch's, or its segment's (SegTab: segments are whole tiles)
     double sg_t0 = ra.t0, sg_h = ra.h;

@@ -40,6 +40,12 @@ __device__ __forceinline__ float noise_value(float scale, unsigned long long see
     return v;
 }
 
+// Noisy ENSEMBLES (nocf_rollout_noisy_ensemble_f32 / nocf_rollout_noisy_mid_ensemble_f32, DESIGN.md section 3.14): every member under its own
+// level and seed -- scale [E, d] (member e's fp32 sigma_i sqrt(h)) and seeds [E], device tables.  The LAST argument of the lane and the one-CU
+// rollout kernels, behind EnsArgs / MonoEnsArgs and for their reason (the offsets of the arguments in front of it stay where they are), and
+// read by the ENS instantiations with DIST == 2 alone.  The key of a row is RollArgs::nzRow0 + the row INSIDE its member
+struct EnsNoiseArgs { const float* scale; const unsigned long long* seeds; };
+
 // W[k][row][i] = noise_value(scale[i], seed, row0 + row, k, i): one thread per element, rows < n and d floats per row only
 __global__ void __launch_bounds__(256) noise_fill_kernel(float* __restrict__ W, long n, int nt, int d, const float* __restrict__ scale,
                                                          unsigned long long seed, long row0) {

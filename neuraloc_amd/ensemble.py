@@ -10,8 +10,8 @@ rows and wave g reads network g // n; nothing else in the rollout changes, so me
     Jc, cs = ensemble_rollout(x, ens, prob, tspan, nt)                # Jc [E], cs [E, 7]
     Jc, cs = ensemble_ocflow_train(x, ens, prob, tspan, nt)           # Jc.sum().backward(): E independent gradients from one adjoint launch
 
-Single precision, one device, undisturbed rollouts.  There is no CPU or eager-torch fallback behind these calls: everything else is refused
-before a launch.
+Single precision, one device, undisturbed rollouts (under in-kernel Brownian noise: ensemble_noise.py, which launches through this module).
+There is no CPU or eager-torch fallback behind these calls: everything else is refused before a launch.
 
 family="mid"  selects the one-CU weight-stationary kernels instead (csrc/nocf_mono.inc, csrc/nocf_mono_bwd.inc: nTh = 2,
 m <= 128, d+1 <= 32, all three problem classes -- singlequad among them).  There a 16-sample tile sits on one CU with the whole network in its
@@ -329,10 +329,11 @@ def _refuse(fn, x, ens, prob, nt, stepper, train, noMean=False, W=None, family="
     return E, int(n), int(d), own
 
 
-def _launch(x, ens, prob, tspan, nt, stepper, alph=None, intermediates=False, record=False, bufs=None):
+def _launch(x, ens, prob, tspan, nt, stepper, alph=None, intermediates=False, record=False, bufs=None, noise=None):
     """one ensemble launch (nocf_rollout_ensemble_f32, or nocf_rollout_record_ensemble_f32 with record) -> dict of its buffers: persample
     [E*n, 7], z_out [E*n, d+4], sums [E, 8], means [E, 8] (evaluation), zFull / ctrlFull (time-major over E*n rows, intermediates), s_all
-    [nt*nstage, E*n, d+1] (record).  bufs: buffers to write into instead of fresh ones (same keys)"""
+    [nt*nstage, E*n, d+1] (record).  bufs: buffers to write into instead of fresh ones (same keys).  noise: an ensemble_noise._Noise -- the
+    launch is the noisy sibling's (nocf_rollout_noisy_ensemble_f32 / nocf_rollout_record_noisy_ensemble_f32), same buffers"""
     E = ens.members
     own = x.dim() == 3
     n, d = x.shape[-2], x.shape[-1]
@@ -340,6 +341,9 @@ def _launch(x, ens, prob, tspan, nt, stepper, alph=None, intermediates=False, re
     dev = x.device
     _lib.check_errors()
     L, (f_eval, f_rec, _f_bwd) = _shipped()
+    names = ("nocf_rollout_ensemble_f32", "nocf_rollout_record_ensemble_f32")
+    if noise is not None:
+        f_eval, f_rec, names = noise.entries(L, "lane")
     phi_st, keep1 = ens._c_struct()
     prob_st, keep2 = prob._c_struct(dev)
     table = ens.alph_table(alph)
@@ -356,13 +360,13 @@ def _launch(x, ens, prob, tspan, nt, stepper, alph=None, intermediates=False, re
         return t
 
     persample, z_out, sums = buf("persample", rows, 7), buf("z_out", rows, d + 4), buf("sums", E, 8)
-    head = (C.byref(phi_st), C.byref(prob_st), _lib.ptr(x), n, E, n * d if own else 0,
-            float(tspan[0]), float(tspan[1]), int(nt), _STEPPERS[stepper], _lib.ptr(table))
+    head = (C.byref(phi_st), C.byref(prob_st), _lib.ptr(x), n, E, n * d if own else 0) + (noise.args(dev) if noise is not None else ()) + \
+           (float(tspan[0]), float(tspan[1]), int(nt), _STEPPERS[stepper], _lib.ptr(table))
     with torch.cuda.device(dev):
         if record:
             s_all = buf("s_all", nt * nstage, rows, d + 1)
             rc = f_rec(*head, _lib.ptr(z_out), _lib.ptr(persample), _lib.ptr(sums), _lib.ptr(s_all), None, 0, _lib.stream_ptr(dev))
-            what = "nocf_rollout_record_ensemble_f32"
+            what = names[1]
         else:
             means = buf("means", E, 8)
             zF = cF = None
@@ -371,7 +375,7 @@ def _launch(x, ens, prob, tspan, nt, stepper, alph=None, intermediates=False, re
                 zF, cF = buf("zFull", nt + 1, rows, d + 4), buf("ctrlFull", nt + 1, rows, cdim)
             rc = f_eval(*head, _lib.ptr(z_out), _lib.ptr(persample), _lib.ptr(sums), _lib.ptr(means), _lib.ptr(zF), _lib.ptr(cF),
                         None, 0, _lib.stream_ptr(dev))
-            what = "nocf_rollout_ensemble_f32"
+            what = names[0]
     _lib.check(rc, what)
     b["table"] = table
     return b
@@ -385,11 +389,12 @@ def _act_stride(L, ens, n, nt, stepper):
     return (int(L.nocf_activation_record_floats(ens.d, ens.m, ens.nTh, int(n), int(nt), _STEPPERS[stepper])) + 3) // 4 * 4
 
 
-def _launch_mid(x, ens, prob, tspan, nt, stepper, alph=None, intermediates=False, record=False, bufs=None):
+def _launch_mid(x, ens, prob, tspan, nt, stepper, alph=None, intermediates=False, record=False, bufs=None, noise=None):
     """one launch of the one-CU family (nocf_rollout_mid_ensemble_f32, or nocf_rollout_record_mid_ensemble_f32 with record) -> dict of its
     buffers, all MEMBER-MAJOR: persample [E, n, 7], z_out [E, n, d+4], sums [E, 8], means [E, 8] (evaluation), zFull [E, nt+1, n, d+4] /
     ctrlFull [E, nt+1, n, a] (intermediates), s_all [E, nt*nstage, n, d+1] and act [E, stride] or None (record; "recorded": the kernel wrote
-    it).  bufs: buffers to write into instead of fresh ones (same keys)"""
+    it).  bufs: buffers to write into instead of fresh ones (same keys).  noise: as for _launch (nocf_rollout_noisy_mid_ensemble_f32 /
+    nocf_rollout_record_noisy_mid_ensemble_f32)"""
     E = ens.members
     own = x.dim() == 3
     n, d = x.shape[-2], x.shape[-1]
@@ -397,6 +402,9 @@ def _launch_mid(x, ens, prob, tspan, nt, stepper, alph=None, intermediates=False
     dev = x.device
     _lib.check_errors()
     L, (f_eval, f_rec, _f_bwd) = _shipped_mid()
+    names = ("nocf_rollout_mid_ensemble_f32", "nocf_rollout_record_mid_ensemble_f32")
+    if noise is not None:
+        f_eval, f_rec, names = noise.entries(L, "mid")
     phi_st, keep1 = ens._c_struct()
     prob_st, keep2 = prob._c_struct(dev)
     table = ens.alph_table(alph)
@@ -413,8 +421,8 @@ def _launch_mid(x, ens, prob, tspan, nt, stepper, alph=None, intermediates=False
         return t
 
     persample, z_out, sums = buf("persample", E, n, 7), buf("z_out", E, n, d + 4), buf("sums", E, 8)
-    head = (C.byref(phi_st), C.byref(prob_st), _lib.ptr(x), n, E, n * d if own else 0,
-            float(tspan[0]), float(tspan[1]), int(nt), _STEPPERS[stepper], _lib.ptr(table))
+    head = (C.byref(phi_st), C.byref(prob_st), _lib.ptr(x), n, E, n * d if own else 0) + (noise.args(dev) if noise is not None else ()) + \
+           (float(tspan[0]), float(tspan[1]), int(nt), _STEPPERS[stepper], _lib.ptr(table))
     tail = (_lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
     with torch.cuda.device(dev):
         if record:
@@ -428,7 +436,7 @@ def _launch_mid(x, ens, prob, tspan, nt, stepper, alph=None, intermediates=False
                     act = None
             recorded = C.c_int32(0)
             rc = f_rec(*head, _lib.ptr(z_out), _lib.ptr(persample), _lib.ptr(sums), _lib.ptr(s_all), _lib.ptr(act), C.byref(recorded), *tail)
-            what = "nocf_rollout_record_mid_ensemble_f32"
+            what = names[1]
             b["recorded"] = bool(recorded.value)
             b["act"] = act if recorded.value else None
         else:
@@ -438,7 +446,7 @@ def _launch_mid(x, ens, prob, tspan, nt, stepper, alph=None, intermediates=False
                 cdim = L.nocf_ctrl_dim(C.byref(prob_st), d)
                 zF, cF = buf("zFull", E, nt + 1, n, d + 4), buf("ctrlFull", E, nt + 1, n, cdim)
             rc = f_eval(*head, _lib.ptr(z_out), _lib.ptr(persample), _lib.ptr(sums), _lib.ptr(means), _lib.ptr(zF), _lib.ptr(cF), *tail)
-            what = "nocf_rollout_mid_ensemble_f32"
+            what = names[0]
     _lib.check(rc, what)
     b["table"] = table
     return b
@@ -486,8 +494,13 @@ class _EnsembleTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, ens, prob, tspan, nt, stepper, alph, *params):
+        return _EnsembleTrain._forward(ctx, x, ens, prob, tspan, nt, stepper, alph)
+
+    @staticmethod
+    def _forward(ctx, x, ens, prob, tspan, nt, stepper, alph, noise=None):
+        """(noise: the recording forward draws its disturbances, ensemble_noise.py; everything saved is what the undisturbed forward saves)"""
         ctx.x_needs_grad = bool(x.requires_grad)
-        b = _launch(x, ens, prob, tspan, nt, stepper, alph, record=True)
+        b = _launch(x, ens, prob, tspan, nt, stepper, alph, record=True, noise=noise)
         ctx.ens, ctx.prob, ctx.tspan, ctx.nt, ctx.stepper, ctx.table = ens, prob, tspan, nt, stepper, b["table"]
         ctx.save_for_backward(b["s_all"], b["z_out"])
         # the adjoint re-reads the weights from the module: they must still be the ones this forward ran with
@@ -502,6 +515,10 @@ class _EnsembleTrain(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gJ, _gmeans):
+        return _EnsembleTrain._adjoint(ctx, gJ)
+
+    @staticmethod
+    def _adjoint(ctx, gJ):
         s_all, z_out = ctx.saved_tensors
         ens, prob, nt = ctx.ens, ctx.prob, ctx.nt
         if [p._version for _, p in ens._params()] != ctx.param_versions:
@@ -541,8 +558,12 @@ class _EnsembleTrainMid(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, ens, prob, tspan, nt, stepper, alph, *params):
+        return _EnsembleTrainMid._forward(ctx, x, ens, prob, tspan, nt, stepper, alph)
+
+    @staticmethod
+    def _forward(ctx, x, ens, prob, tspan, nt, stepper, alph, noise=None):
         ctx.x_needs_grad = bool(x.requires_grad)
-        b = _launch_mid(x, ens, prob, tspan, nt, stepper, alph, record=True)
+        b = _launch_mid(x, ens, prob, tspan, nt, stepper, alph, record=True, noise=noise)
         ctx.ens, ctx.prob, ctx.tspan, ctx.nt, ctx.stepper, ctx.table = ens, prob, tspan, nt, stepper, b["table"]
         ctx.act = b["act"]
         ctx.save_for_backward(b["s_all"], b["z_out"])
@@ -557,6 +578,10 @@ class _EnsembleTrainMid(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gJ, _gmeans):
+        return _EnsembleTrainMid._adjoint(ctx, gJ)
+
+    @staticmethod
+    def _adjoint(ctx, gJ):
         s_all, z_out = ctx.saved_tensors
         ens, prob, nt = ctx.ens, ctx.prob, ctx.nt
         if [p._version for _, p in ens._params()] != ctx.param_versions:

@@ -29,7 +29,13 @@ member 0's batches.  FILE: E lines of six comma-separated multipliers, one membe
 member and iteration, the usual line prefixed by "m<e>"; one checkpoint per member in the reference's layout, ..._m<e>_checkpt.pth, each
 keeping that member's own best.  The small-network shapes only; not with --prec double, --noise, --adv, --resume or more than one rank.
 --members_family mid (addition, with --members): the ensemble runs on the one-CU kernels instead: 32 < m <= 128,
-d + 1 <= 32, every problem class -- --data singlequad, and --m 64 / 128 on the point-agent problems.  The default, lane, is the above."""
+d + 1 <= 32, every problem class -- --data singlequad, and --m 64 / 128 on the point-agent problems.  The default, lane, is the above.
+--members_sigma S0,S1,... [--noise_seed S] (addition, with --members): E noise levels >= 0, one per member -- a sweep over the noise level in
+one process.  Member e trains under per-step Brownian state disturbances sigma_e dB drawn inside the kernels
+(neuraloc_amd.ensemble_noisy_ocflow_train), one launch per rollout and per adjoint for all members, on either family.
+The seed is noise_seed << 32 | iteration for ALL members (the --noise_rng counter convention, 0 <= noise_seed < 2**32): every member meets
+the same noise realisations scaled by its own level, so the members' costs are a paired comparison across sigma.  A level of 0 is the
+undisturbed member; validation stays undisturbed.  --members with --noise stays refused: this flag is the way in."""
 import argparse
 import datetime
 import os
@@ -86,6 +92,9 @@ _FLAGS = [
     ("members_alph", str, None, "(addition, with --members) file of E lines of six comma-separated multipliers, one member each (default: --alph)"),
     ("members_family", str, "lane", "(addition, with --members) lane: the small-network lane kernels; mid: the one-CU kernels "
                                     "(32 < m <= 128, d + 1 <= 32, every problem class, singlequad among them)"),
+    ("members_sigma", str, None, "(addition, with --members) S0,S1,...: E noise levels >= 0, member e trains under Brownian state disturbances "
+                                 "sigma_e dB drawn inside the kernels (neuraloc_amd.ensemble_noisy_ocflow_train), all members under the seed "
+                                 "noise_seed << 32 | iteration; validation stays undisturbed"),
 ]
 _CHOICES = {"data": PROBLEM_NAMES, "optim": ["adam"], "prec": ["single", "double"], "approach": ["ocflow"], "noise_rng": ["torch", "counter"],
             "adv_mode": ["free", "pgd"], "adv_objective": ["Jc", "control"], "members_family": list(na.ensemble.FAMILIES)}
@@ -142,8 +151,28 @@ def members_refusals(args, world):
     return rows
 
 
-def train_members(args, rows):
-    """the training loop of main() for E networks at once (neuraloc_amd.ensemble): same schedule, one log line and one checkpoint per member"""
+def members_sigma_levels(args):
+    """--members_sigma: the members' noise levels, refused before anything runs or is written.  -> E floats, or None without the flag"""
+    if args.members_sigma is None:
+        return None
+    if args.members is None or args.members < 1:
+        raise SystemExit("--members_sigma needs --members E: one noise level per member")
+    try:
+        levels = [float(v) for v in args.members_sigma.split(",")]
+    except ValueError:
+        raise SystemExit("--members_sigma S0,S1,...: a comma-separated list of numbers, got {!r}".format(args.members_sigma))
+    if len(levels) != args.members:
+        raise SystemExit("--members_sigma needs one level per member: --members {:} but {:} values".format(args.members, len(levels)))
+    if any(not 0 <= v < float("inf") for v in levels):
+        raise SystemExit("--members_sigma: every level must be a finite number >= 0")
+    if not 0 <= args.noise_seed < 2 ** 32:
+        raise SystemExit("--members_sigma needs 0 <= --noise_seed < 2**32 (the iteration takes the seed's low word)")
+    return levels
+
+
+def train_members(args, rows, sigmas=None):
+    """the training loop of main() for E networks at once (neuraloc_amd.ensemble): same schedule, one log line and one checkpoint per member.
+    sigmas (--members_sigma): member e's training rollouts run under Brownian disturbances of level sigmas[e]"""
     E = args.members
     dev = torch.device("cuda", args.gpu)
     assert torch.cuda.is_available(), "trainOC.py needs an MI355X: there is no CPU path"
@@ -182,7 +211,11 @@ def train_members(args, rows):
     end = time.time()
     for itr in range(1, args.niters + 1):
         optim.zero_grad()
-        Jc, cs = na.ensemble_ocflow_train(x0, ens, prob, tspan, args.nt, "rk4", family=args.members_family)
+        if sigmas is not None:                            # one seed for all members: the same noise realisations at E levels
+            Jc, cs = na.ensemble_noisy_ocflow_train(x0, ens, prob, tspan, args.nt, [[s_] for s_ in sigmas], (args.noise_seed << 32) | itr,
+                                                    "rk4", family=args.members_family)
+        else:
+            Jc, cs = na.ensemble_ocflow_train(x0, ens, prob, tspan, args.nt, "rk4", family=args.members_family)
         Jc.sum().backward()                               # (upstream gradient 1 for every member: E independent gradients)
         torch.cuda.synchronize()
         optim.step()
@@ -246,8 +279,9 @@ def main(argv=None):
         raise SystemExit("--adv_objective control needs --adv_mode pgd: the free adversary climbs the training loss itself")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
-    if args.members is not None or args.members_alph is not None or args.members_family != "lane":
-        return train_members(args, members_refusals(args, world))
+    if args.members is not None or args.members_alph is not None or args.members_family != "lane" or args.members_sigma is not None:
+        sigmas = members_sigma_levels(args)
+        return train_members(args, members_refusals(args, world), sigmas)
     if world > 1:
         import torch.distributed as dist
         local = int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count())
