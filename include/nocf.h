@@ -621,6 +621,37 @@ int nocf_rollout_bwd_act_w_f32(const NocfPhi* phi, const NocfProb* prob, int64_t
                                void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The WEIGHTED adjoints: nocf_rollout_bwd_small_f32 / _mid_f32 / _act_f32 with one weight per sample in place of the scalar inv_n.
+ * The gradient of a risk measure of the per-sample costs (CVaR, entropic risk), of an importance-weighted batch or of any other weighted
+ * sum is sum_i w_i grad J_i; the existing entries seed every sample's cotangents with the one value inv_n and cannot form it.  The
+ * kernels are the existing ones' further instantiation: wrow[row] stands where inv_n stands at that row's cotangent seeds (the terminal
+ * state cotangent, the cotangent of grad Phi(z(T)), the cotangent of Phi(z(T), T), and the running-cost factor of every RK evaluation).
+ *   wrow   device [n] float32, contiguous, not modified.  Any finite values, negative and zero included; nothing checks them on the
+ *          device.  Tail rows of the last tile, which replicate a valid sample, keep weight 0
+ *   every output is the existing entry's with wrow[row] for inv_n: the parameter gradient (gpart / the partial rows / the row streams
+ *          Y ... PHIb) is sum_i wrow[i] grad J_i, and lam0[i] = wrow[i] dJ_i/dx_i.  wrow filled with (float)inv_n gives the existing
+ *          entry's bits
+ *   every other argument, the workspace, the dispatch (NOCF_E_SHAPE hands a shape on to the next family) and every refusal: the
+ *          existing entry's;  wrow == NULL: NOCF_E_NULL.  Every refusal returns before anything is enqueued
+ * nocf_last_rollout_kernel() reports "rollout_lane_bwd_kernel<weighted>", "rollout_mono_bwd_kernel<weighted>" or
+ * "rollout_bwd_kernel<weighted>".  The per-tile weighted kernel is instantiated for the generic plan and for the shapes whose disturbed
+ * forward is specialised, like the joint one.  The split-role kernel and the tape adjoint take no weights: a weighted call follows a
+ * disturbed or noisy recording forward, which never runs them.  nocf_version() is unchanged: callers probe for the symbols.  float32 only.
+ */
+int nocf_rollout_bwd_small_rw_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t nt, int32_t stepper, double t1,
+                                  const float* alph, const float* wrow, const float* s_all, const float* z_final, const float* hs,
+                                  float* gpart, float* lam0, void* stream);
+int nocf_rollout_bwd_mid_rw_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t nt, int32_t stepper, double t1,
+                                const float* alph, const float* wrow, const float* s_all, const float* z_final, const float* hs,
+                                const float* act_rec, float* gpart, int64_t gpart_rows, float* lam0,
+                                void* workspace, size_t workspace_bytes, void* stream);
+int nocf_rollout_bwd_act_rw_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t nt, int32_t stepper, double t1,
+                                const float* alph, const float* wrow, const float* s_all, const float* z_final, const float* hs,
+                                float* Y, float* Ob, float* V, float* Ab, float* Qb, float* U0, float* Wb, float* Gb, float* Sx,
+                                float* PHIb, float* lam0, const float* act_rec,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * One step of projected gradient ascent on per-row disturbance paths, in place: for every row i, over its [nt, d] path of W,
  *     W_i += step (mask o g_i) / ||mask o g_i||_2          (the row is left untouched when that norm is 0 or not finite)
  *     W_i *= eps / ||W_i||_2   when ||W_i||_2 > eps         (projection onto the ball over the whole path)

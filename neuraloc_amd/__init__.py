@@ -16,6 +16,7 @@ from .noise import counter_disturbances, noisy_rollout, noisy_ocflow_train
 from .minmax import minmax_ocflow_train, ascend_disturbances, adversarial_step, pgd_ocflow_train
 from .ensemble import PhiEnsemble, ensemble_rollout, ensemble_ocflow_train
 from .ensemble_noise import ensemble_noisy_rollout, ensemble_noisy_ocflow_train, ensemble_noise_study
+from .risk import risk_weights, weighted_ocflow_train, risk_ocflow_train
 
 __all__ = ["Phi", "ResNN", "antiderivTanh", "derivTanh", "OCflow", "ocG", "Cross2D", "SwarmTraj",
            "Quadcopter", "initProb", "resample", "OCflow_sharded", "shard_rows", "reduce_cost_sums", "check_errors",
@@ -25,4 +26,5 @@ __all__ = ["Phi", "ResNN", "antiderivTanh", "derivTanh", "OCflow", "ocG", "Cross
            "disturbance_gradient", "worst_case_disturbances",
            "minmax_ocflow_train", "ascend_disturbances", "adversarial_step", "pgd_ocflow_train",
            "PhiEnsemble", "ensemble_rollout", "ensemble_ocflow_train",
-           "ensemble_noisy_rollout", "ensemble_noisy_ocflow_train", "ensemble_noise_study"]
+           "ensemble_noisy_rollout", "ensemble_noisy_ocflow_train", "ensemble_noise_study",
+           "risk_weights", "weighted_ocflow_train", "risk_ocflow_train"]

@@ -48,6 +48,9 @@ struct BwdArgs {
     // step k begins = dJ/dW[k] of a disturbed rollout (z_{k+1} = step(z_k) + W[k]); lamW[nt-1] is the terminal cotangent dJ/dx(T).
     // STATES is a mode: 0 full, 1 state-only, 2 joint (nocf_rollout_bwd_*_w_f32: mode 0's statements plus this store)
     float* lamW;
+    // weighted instantiations (RW, nocf_rollout_bwd_*_rw_f32): [n], one weight per sample, standing where inv_n stands for that sample's
+    // cotangent seeds (LAM, gbar, phib, kL / kh); read by those instantiations only (the last field: no existing offset moves)
+    const float* wrow;
 };
 
 // d(raw obstacle cost of agent a)/dx at the sample x, added into gq[3]: the per-agent math of physics_xgrad's obstacle part
@@ -384,7 +387,14 @@ __device__ void phi_vjp(const Ctx& c, const DevPlan& pl, Ring& rg, const BwdArgs
     }
 }
 
-template <int S, int STATES = 0>
+// RW (STATES = 0; nocf_rollout_bwd_act_rw_f32): the per-sample weight ba.wrow[row] stands where ba.inv_n stands at the four cotangent seeds
+// below (LAM, GB, phib, kL / kh); a tail row, which replicates a valid sample, takes weight 0.  The three seeds of the terminal evaluation load
+// it per row from global memory, once.  The kL seed recurs in every RK evaluation, where a global load put one memory latency into each of them
+// (1.3 % of swarm50's adjoint, profiles/risk), and four registers held across the loop cost spills: the per-sample LDS slot SC[t][3], which
+// carries e_f through the terminal evaluation and is idle afterwards, keeps the weight instead -- written at the end of the terminal
+// evaluation by the thread that reads it at every kL site.  Every RW test is a compile-time choice at its place of use: the other
+// instantiations keep their statements.
+template <int S, int STATES = 0, bool RW = false>
 __device__ __forceinline__ void rollout_bwd_body(const DevPlan& pl, const DevPlan* __restrict__ plp, const DevProb& pb,
                                                  const float* __restrict__ ws, const BwdArgs& ba) {
     Ctx c;
@@ -519,8 +529,10 @@ __device__ __forceinline__ void rollout_bwd_body(const DevPlan& pl, const DevPla
                 const float dg = gi - ba.a0 * res;
                 const float eg = (dg > 0.f) ? 1.f : (dg < 0.f ? -1.f : 0.f);
                 const float ef = SC[t * 4 + 3];
-                LAM[t * ZLD + i] = ba.inv_n * (ba.a0 * res + ba.a4 * ef * dg - ba.a5 * ba.a0 * eg);
-                GB[t * pl.LDs + i] = ba.inv_n * ba.a5 * eg;
+                float wI = 0.f;
+                if constexpr (RW) { if (t < nvalid) wI = ba.wrow[row0 + t]; }
+                LAM[t * ZLD + i] = (RW ? wI : ba.inv_n) * (ba.a0 * res + ba.a4 * ef * dg - ba.a5 * ba.a0 * eg);
+                GB[t * pl.LDs + i] = (RW ? wI : ba.inv_n) * ba.a5 * eg;
                 XD[t * ZLD + i] = 0.f;
             }
             if (c.tid < T) GB[c.tid * pl.LDs + d] = 0.f;
@@ -534,7 +546,7 @@ __device__ __forceinline__ void rollout_bwd_body(const DevPlan& pl, const DevPla
             const int Lr = pl.nTh - 1, TLD = T * LD;
             for (int t = 0; t < T; ++t) {
                 if (t >= nvalid) break;
-                const float phib = ba.value_only ? ba.PHIb[row0 + t] : ba.inv_n * ba.a4 * SC[t * 4 + 3];
+                const float phib = ba.value_only ? ba.PHIb[row0 + t] : (RW ? ba.wrow[row0 + t] : ba.inv_n) * ba.a4 * SC[t * 4 + 3];
                 const long row = vrow0 + t;
                 for (int col = c.tid; col < m; col += c.nthreads) {
                     for (int i = 1; i <= Lr; ++i) {
@@ -564,7 +576,8 @@ __device__ __forceinline__ void rollout_bwd_body(const DevPlan& pl, const DevPla
                 const Costs cs = physics_finish(c, pl, pb, s);
                 const float dh = G[s * pl.GLD + d] - cs.H;
                 const float eh = (dh > 0.f) ? 1.f : (dh < 0.f ? -1.f : 0.f);
-                const float kL = hs * wst * ba.inv_n, kh = hs * wst * ba.a3 * ba.inv_n;
+                const float wI = RW ? SC[s * 4 + 3] : 0.f;      // (RW: the row's weight, kept in e_f's slot since the terminal evaluation)
+                const float kL = hs * wst * (RW ? wI : ba.inv_n), kh = hs * wst * ba.a3 * (RW ? wI : ba.inv_n);
                 SC[s * 4 + 0] = quad ? kL : kL + eh * kh;   // point agents: multiplies d(alphQ Q + alphW W)/dx
                 SC[s * 4 + 1] = eh * kh;                 // cotangent of dPhi/dt
                 SC[s * 4 + 2] = kL - eh * kh;            // multiplies p in the cotangent of grad_x Phi
@@ -605,6 +618,9 @@ __device__ __forceinline__ void rollout_bwd_body(const DevPlan& pl, const DevPla
                 if (st == 0) LAM[t * ZLD + i] += xs;                     // all stages of step k are in
             }
         }
+        if constexpr (RW) {                  // e_f's last readers are behind phi_vjp's barriers: its slot takes the row's weight for the kL seeds
+            if (fin && c.tid < T) SC[c.tid * 4 + 3] = (c.tid < nvalid) ? ba.wrow[row0 + c.tid] : 0.f;
+        }
         __syncthreads();
     }
     if (ba.lam0)
@@ -614,13 +630,14 @@ __device__ __forceinline__ void rollout_bwd_body(const DevPlan& pl, const DevPla
         }
 }
 
-template <int S, class SP, int STATES = 0>
+template <int S, class SP, int STATES = 0, bool RW = false>
 __global__ void __launch_bounds__(NOCF_MAXTHREADS) rollout_bwd_kernel(const DevPlan* __restrict__ plp, DevProb pb,
                                                                       const float* __restrict__ ws, BwdArgs ba) {
+    static_assert(!RW || STATES == 0, "the weighted variant is the parameter-and-lam0 adjoint");
     if constexpr (SP::fixed) {
         constexpr DevPlan plc = SP::make();
-        rollout_bwd_body<S, STATES>(plc, plp, pb, ws, ba);
+        rollout_bwd_body<S, STATES, RW>(plc, plp, pb, ws, ba);
     } else {
-        rollout_bwd_body<S, STATES>(*plp, plp, pb, ws, ba);
+        rollout_bwd_body<S, STATES, RW>(*plp, plp, pb, ws, ba);
     }
 }

@@ -1759,14 +1759,15 @@ int64_t nocf_small_grad_floats(int32_t d, int32_t m) {
 }
 
 // mode 1: the state-only instantiation (nocf_rollout_bwd_states_f32) -- no gpart, lam0 and / or lamW; mode 2: the joint one
-// (nocf_rollout_bwd_small_w_f32) -- gpart and lamW, lam0 nullable
+// (nocf_rollout_bwd_small_w_f32) -- gpart and lamW, lam0 nullable; mode 3: the weighted one (nocf_rollout_bwd_small_rw_f32) -- mode 0 with
+// wrow [n] in place of inv_n
 static int bwd_small_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t nt, int32_t stepper, double t1,
                           const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
-                          float* gpart, float* lam0, float* lamW, int mode, void* stream) {
+                          float* gpart, float* lam0, float* lamW, int mode, void* stream, const float* wrow = nullptr) {
     int rc = check_phi(phi);
     if (rc) return rc;
     const bool states = mode == 1;
-    if (!alph || !s_all || !z_final || !hs || (!states && !gpart) || (states && !lam0 && !lamW) || (mode == 2 && !lamW)) return NOCF_E_NULL;
+    if (!alph || !s_all || !z_final || !hs || (!states && !gpart) || (states && !lam0 && !lamW) || (mode == 2 && !lamW) || (mode == 3 && !wrow)) return NOCF_E_NULL;
     if (n < 1 || nt < 1) return NOCF_E_SHAPE;
     if (stepper != NOCF_RK4 && stepper != NOCF_RK1) return NOCF_E_STEPPER;
     DevProb pb;
@@ -1782,7 +1783,8 @@ static int bwd_small_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n, i
     la.d = phi->d; la.m = phi->m; la.r = phi->r; la.nAg = pb.nAgents; la.cb = phi->cb;
     la.sAll = s_all; la.zT = z_final; la.hs = hs; la.n = n; la.nt = nt; la.nstage = (stepper == NOCF_RK4) ? 4 : 1;
     la.t1 = (float)t1; la.a0 = alph[0]; la.a3 = alph[3]; la.a4 = alph[4]; la.a5 = alph[5]; la.inv_n = (float)inv_n;
-    la.gpart = gpart; la.P_total = nocf_small_grad_floats(phi->d, phi->m); la.lam0 = lam0; la.lamW = mode ? lamW : nullptr;
+    la.gpart = gpart; la.P_total = nocf_small_grad_floats(phi->d, phi->m); la.lam0 = lam0; la.lamW = (mode == 1 || mode == 2) ? lamW : nullptr;
+    la.wrow = mode == 3 ? wrow : nullptr;
     hipStream_t st = (hipStream_t)stream;
     const int grid = (int)((n + 3) / 4);
     const int MPsel = phi->m <= 16 ? 16 : 32;
@@ -1790,6 +1792,7 @@ static int bwd_small_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n, i
     if (env_int("NOCF_DEBUG", 0)) fprintf(stderr, "[nocf] lane adjoint kernel\n");
 #define NOCF_LANEB_LAUNCH(MPV, DPV) do { if (mode == 1) hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV, 1>), dim3(grid), dim3(256), 0, st, la, pb, EnsArgs{}); \
                                           else if (mode == 2) hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV, 2>), dim3(grid), dim3(256), 0, st, la, pb, EnsArgs{}); \
+                                          else if (mode == 3) hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV, 0, false, true>), dim3(grid), dim3(256), 0, st, la, pb, EnsArgs{}); \
                                           else hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV>), dim3(grid), dim3(256), 0, st, la, pb, EnsArgs{}); } while (0)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (g_prof_on) {
@@ -1800,7 +1803,8 @@ static int bwd_small_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n, i
     else             { if (DPsel == 8) { NOCF_LANEB_LAUNCH(32, 8); } else if (DPsel == 16) { NOCF_LANEB_LAUNCH(32, 16); } else { NOCF_LANEB_LAUNCH(32, 32); } }
 #undef NOCF_LANEB_LAUNCH
     if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
-    g_last_kernel = mode == 1 ? "rollout_lane_bwd_kernel<states>" : (mode == 2 ? "rollout_lane_bwd_kernel<joint>" : "rollout_lane_bwd_kernel");
+    g_last_kernel = mode == 1 ? "rollout_lane_bwd_kernel<states>" : (mode == 2 ? "rollout_lane_bwd_kernel<joint>" :
+                    (mode == 3 ? "rollout_lane_bwd_kernel<weighted>" : "rollout_lane_bwd_kernel"));
     g_last_errp = nullptr;
     return (int)hipGetLastError();
 }
@@ -1815,6 +1819,12 @@ int nocf_rollout_bwd_small_w_f32(const NocfPhi* phi, const NocfProb* prob, int64
                                  const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
                                  float* gpart, float* lam0, float* lamW, void* stream) {
     return bwd_small_impl(phi, prob, n, nt, stepper, t1, alph, inv_n, s_all, z_final, hs, gpart, lam0, lamW, lamW ? 2 : 0, stream);
+}
+
+int nocf_rollout_bwd_small_rw_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t nt, int32_t stepper, double t1,
+                                  const float* alph, const float* wrow, const float* s_all, const float* z_final, const float* hs,
+                                  float* gpart, float* lam0, void* stream) {
+    return bwd_small_impl(phi, prob, n, nt, stepper, t1, alph, 0.0, s_all, z_final, hs, gpart, lam0, nullptr, 3, stream, wrow);
 }
 
 // ---- ensembles on the lane kernels (include/nocf.h): E networks of one shape, one launch.  The lane family or nothing: every other shape is
@@ -1954,7 +1964,7 @@ int nocf_rollout_bwd_small_ensemble_f32(const NocfPhi* phi, const NocfProb* prob
     la.d = phi->d; la.m = phi->m; la.r = phi->r; la.nAg = pb.nAgents;
     la.sAll = s_all; la.zT = z_final; la.hs = hs; la.n = rows; la.nt = nt; la.nstage = (stepper == NOCF_RK4) ? 4 : 1;
     la.t1 = (float)t1; la.inv_n = (float)inv_n;
-    la.gpart = gpart; la.P_total = nocf_small_grad_floats(phi->d, phi->m); la.lam0 = lam0; la.lamW = nullptr;
+    la.gpart = gpart; la.P_total = nocf_small_grad_floats(phi->d, phi->m); la.lam0 = lam0; la.lamW = nullptr; la.wrow = nullptr;
     const EnsArgs ea{(unsigned)n, 0l, alph};
     hipStream_t st = (hipStream_t)stream;
     const int grid = (int)((rows + 3) / 4);
@@ -2523,7 +2533,8 @@ static int rollout_bwd_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n,
                             const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
                             float* Y, float* Ob, float* V, float* Ab, float* Qb, float* U0, float* Wb, float* Gb, float* Sx,
                             float* PHIb, float* lam0, const float* act_rec, void* workspace, size_t workspace_bytes, void* stream,
-                            int value_only = 0, const float* gbar_in = nullptr, float* sbar_out = nullptr, int mode = 0, float* lamW = nullptr);
+                            int value_only = 0, const float* gbar_in = nullptr, float* sbar_out = nullptr, int mode = 0, float* lamW = nullptr,
+                            const float* wrow = nullptr);
 
 // ---- training tape + split-role adjoint (nocf_duo_bwd.inc)
 static void tape_offsets(int32_t d, int32_t m, int64_t n, int32_t nt, int32_t stepper, size_t* oU1, size_t* oSc, size_t* total) {
@@ -2676,6 +2687,14 @@ int nocf_rollout_bwd_act_w_f32(const NocfPhi* phi, const NocfProb* prob, int64_t
                             act_rec, workspace, workspace_bytes, stream, 0, nullptr, nullptr, lamW ? 2 : 0, lamW);
 }
 
+int nocf_rollout_bwd_act_rw_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t nt, int32_t stepper, double t1,
+                                const float* alph, const float* wrow, const float* s_all, const float* z_final, const float* hs,
+                                float* Y, float* Ob, float* V, float* Ab, float* Qb, float* U0, float* Wb, float* Gb, float* Sx,
+                                float* PHIb, float* lam0, const float* act_rec, void* workspace, size_t workspace_bytes, void* stream) {
+    return rollout_bwd_impl(phi, prob, n, nt, stepper, t1, alph, 0.0, s_all, z_final, hs, Y, Ob, V, Ab, Qb, U0, Wb, Gb, Sx, PHIb, lam0,
+                            act_rec, workspace, workspace_bytes, stream, 0, nullptr, nullptr, 3, nullptr, wrow);
+}
+
 int nocf_phi_grad_bwd_f32(const NocfPhi* phi, const float* s, int64_t n, const float* gbar, float* sbar,
                           float* Y, float* Ob, float* V, float* Ab, float* Qb, float* U0, float* Wb, float* Gb, float* Sx,
                           void* workspace, size_t workspace_bytes, void* stream) {
@@ -2696,13 +2715,15 @@ static int rollout_bwd_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n,
                             const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
                             float* Y, float* Ob, float* V, float* Ab, float* Qb, float* U0, float* Wb, float* Gb, float* Sx,
                             float* PHIb, float* lam0, const float* act_rec, void* workspace, size_t workspace_bytes, void* stream,
-                            int value_only, const float* gbar_in, float* sbar_out, int mode, float* lamW) {
+                            int value_only, const float* gbar_in, float* sbar_out, int mode, float* lamW, const float* wrow) {
     // mode 1: the state-only instantiation (nocf_rollout_bwd_states_f32) -- no row stream, lam0 and / or lamW; mode 2: the joint one
-    // (nocf_rollout_bwd_act_w_f32) -- every row stream and lamW
+    // (nocf_rollout_bwd_act_w_f32) -- every row stream and lamW; mode 3: the weighted one (nocf_rollout_bwd_act_rw_f32) -- mode 0 with
+    // wrow [n] in place of inv_n
     int rc = check_phi(phi);
     if (rc) return rc;
     const bool states = mode == 1;
     if (mode == 2 && (value_only || !lamW)) return NOCF_E_NULL;
+    if (mode == 3 && (value_only || !wrow)) return NOCF_E_NULL;
     if (value_only) { if (!s_all || nt != 0 || (value_only == 2 && (!gbar_in || !sbar_out))) return NOCF_E_NULL; }
     else if (!alph || !z_final || !hs) return NOCF_E_NULL;
     if (states) { if (value_only || !s_all || (!lam0 && !lamW) || !workspace) return NOCF_E_NULL; }
@@ -2736,7 +2757,7 @@ static int rollout_bwd_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n,
     if (alph) { ba.a0 = alph[0]; ba.a3 = alph[3]; ba.a4 = alph[4]; ba.a5 = alph[5]; } else { ba.a0 = ba.a3 = ba.a4 = ba.a5 = 0.f; }
     ba.inv_n = (float)inv_n; ba.value_only = value_only; ba.gbar_in = gbar_in; ba.sbar_out = sbar_out;
     ba.Y = Y; ba.Ob = Ob; ba.V = V; ba.Ab = Ab; ba.Qb = Qb; ba.U0 = U0; ba.Wb = Wb; ba.Gb = Gb; ba.Sx = Sx;
-    ba.PHIb = PHIb; ba.lam0 = lam0; ba.lamW = mode ? lamW : nullptr;
+    ba.PHIb = PHIb; ba.lam0 = lam0; ba.lamW = (mode == 1 || mode == 2) ? lamW : nullptr; ba.wrow = mode == 3 ? wrow : nullptr;
     ba.act = (act_rec && phi->nTh == 2) ? act_rec : nullptr; ba.actRows = (long)nt * ba.nstage * n;
     ba.lstride = ((long)nt * ba.nstage + 2) * n * phi->m;
     ba.gpart = nullptr; ba.gstride = 0;
@@ -2755,6 +2776,13 @@ static int rollout_bwd_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n,
         FIXED_SHAPES(NOCF_TRY_FIXED)
         FIXED_SHAPES_EXTRA(NOCF_TRY_FIXED)
 #undef NOCF_TRY_FIXED
+    } else if (mode == 3 && env_int("NOCF_FIXED", 1)) {
+        // (the shapes of the joint one: a weighted call follows a disturbed or noisy recording forward)
+#define NOCF_TRY_FIXED(D, M, NTH, R, NAG) \
+        if (!fk && plan_is<FixedPlan<D, M, NTH, R, NAG, 1>>(pl)) fk = reinterpret_cast<const void*>(rollout_bwd_kernel<1, FixedPlan<D, M, NTH, R, NAG, 1>, 0, true>);
+        FIXED_SHAPES(NOCF_TRY_FIXED)
+        FIXED_SHAPES_EXTRA(NOCF_TRY_FIXED)
+#undef NOCF_TRY_FIXED
     } else if (env_int("NOCF_FIXED", 1)) {
 #define NOCF_TRY_FIXED(D, M, NTH, R, NAG) \
         if (!fk && plan_is<FixedPlan<D, M, NTH, R, NAG, 1>>(pl)) fk = reinterpret_cast<const void*>(rollout_bwd_kernel<1, FixedPlan<D, M, NTH, R, NAG, 1>>);
@@ -2765,7 +2793,8 @@ static int rollout_bwd_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n,
     }
     const bool specialised = fk != nullptr;
     if (!fk) fk = states ? reinterpret_cast<const void*>(rollout_bwd_kernel<1, DynPlan, true>)
-                  : (mode == 2 ? reinterpret_cast<const void*>(rollout_bwd_kernel<1, DynPlan, 2>) : reinterpret_cast<const void*>(rollout_bwd_kernel<1, DynPlan>));
+                  : (mode == 2 ? reinterpret_cast<const void*>(rollout_bwd_kernel<1, DynPlan, 2>)
+                  : (mode == 3 ? reinterpret_cast<const void*>(rollout_bwd_kernel<1, DynPlan, 0, true>) : reinterpret_cast<const void*>(rollout_bwd_kernel<1, DynPlan>)));
     if (env_int("NOCF_DEBUG", 0))
         fprintf(stderr, "[nocf] %s rollout adjoint kernel: T %d, %d waves, SK1/SK6/SKm %d/%d/%d, cap %d, LDS %zu B/workgroup, activations %s\n",
                 specialised ? "specialised" : "generic", pl.T, pl.nwaves, pl.SK1, pl.SK6, pl.SKm, skCap, ldsBytes,
@@ -2782,7 +2811,8 @@ static int rollout_bwd_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n,
         e = hipLaunchKernel(fk, dim3((int)((n + 3) / 4)), dim3(pl.nwaves * 64), args, ldsBytes, st);
         if (e) return (int)e;
         if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
-        g_last_kernel = states ? "rollout_bwd_kernel<states>" : (mode == 2 ? "rollout_bwd_kernel<joint>" : "rollout_bwd_kernel");
+        g_last_kernel = states ? "rollout_bwd_kernel<states>" : (mode == 2 ? "rollout_bwd_kernel<joint>" :
+                        (mode == 3 ? "rollout_bwd_kernel<weighted>" : "rollout_bwd_kernel"));
         g_last_errp = nullptr;
     }
     return (int)hipGetLastError();
@@ -2805,12 +2835,14 @@ int64_t nocf_mid_grad_rows(int32_t d, int32_t m, int32_t nTh, int32_t r, int32_t
 }
 
 // mode 1: the state-only instantiation (nocf_rollout_bwd_states_f32) -- no gpart, lam0 and / or lamW; mode 2: the joint one
-// (nocf_rollout_bwd_mid_w_f32) -- gpart and lamW, lam0 nullable
+// (nocf_rollout_bwd_mid_w_f32) -- gpart and lamW, lam0 nullable; mode 3: the weighted one (nocf_rollout_bwd_mid_rw_f32) -- mode 0 with
+// wrow [n] in place of inv_n
 static int bwd_mid_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t nt, int32_t stepper, double t1,
                         const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
                         const float* act_rec, float* gpart, int64_t gpart_rows, float* lam0, float* lamW, int mode,
-                        void* workspace, size_t workspace_bytes, void* stream) {
+                        void* workspace, size_t workspace_bytes, void* stream, const float* wrow = nullptr) {
 #ifdef NOCF_JIT_ONLY
+    (void)wrow;
     (void)phi; (void)prob; (void)n; (void)nt; (void)stepper; (void)t1; (void)alph; (void)inv_n; (void)s_all; (void)z_final; (void)hs;
     (void)act_rec; (void)gpart; (void)gpart_rows; (void)lam0; (void)lamW; (void)mode; (void)workspace; (void)workspace_bytes; (void)stream;
     return NOCF_E_SHAPE;
@@ -2818,7 +2850,8 @@ static int bwd_mid_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n, int
     int rc = check_phi(phi);
     if (rc) return rc;
     const bool states = mode == 1;
-    if (!alph || !s_all || !z_final || !hs || (!states && !gpart) || (states && !lam0 && !lamW) || (mode == 2 && !lamW) || !workspace) return NOCF_E_NULL;
+    if (!alph || !s_all || !z_final || !hs || (!states && !gpart) || (states && !lam0 && !lamW) || (mode == 2 && !lamW) || (mode == 3 && !wrow) ||
+        !workspace) return NOCF_E_NULL;
     if (n < 1 || nt < 1) return NOCF_E_SHAPE;
     if (stepper != NOCF_RK4 && stepper != NOCF_RK1) return NOCF_E_STEPPER;
     DevProb pb;
@@ -2846,14 +2879,15 @@ static int bwd_mid_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n, int
     ba.sAll = s_all; ba.zT = z_final; ba.hs = hs; ba.n = n; ba.nt = nt; ba.nstage = (stepper == NOCF_RK4) ? 4 : 1;
     ba.t1 = (float)t1;
     ba.a0 = alph[0]; ba.a3 = alph[3]; ba.a4 = alph[4]; ba.a5 = alph[5]; ba.inv_n = (float)inv_n;
-    ba.lam0 = lam0; ba.lamW = mode ? lamW : nullptr;
+    ba.lam0 = lam0; ba.lamW = (mode == 1 || mode == 2) ? lamW : nullptr; ba.wrow = mode == 3 ? wrow : nullptr;
     ba.gpart = gpart; ba.gstride = nocf_small_grad_floats(phi->d, phi->m);
     ba.act = (act_rec && (phi->m % 16) == 0) ? act_rec : nullptr; ba.actRows = (long)nt * ba.nstage * n;
     const size_t ldsBytes = (size_t)mpl.pp.ldsFloats * 4;
     const void* fk = nullptr;
 #define NOCF_MBW_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) fk = states ? reinterpret_cast<const void*>(rollout_mono_bwd_kernel<M_, D_, true>) \
                                                                        : (mode == 2 ? reinterpret_cast<const void*>(rollout_mono_bwd_kernel<M_, D_, 2>) \
-                                                                                    : reinterpret_cast<const void*>(rollout_mono_bwd_kernel<M_, D_>));
+                                                                       : (mode == 3 ? reinterpret_cast<const void*>(rollout_mono_bwd_kernel<M_, D_, 0, false, true>) \
+                                                                                    : reinterpret_cast<const void*>(rollout_mono_bwd_kernel<M_, D_>)));
     NOCF_MBW_PICK(8, 1) NOCF_MBW_PICK(6, 1) NOCF_MBW_PICK(4, 1) NOCF_MBW_PICK(8, 2) NOCF_MBW_PICK(6, 2) NOCF_MBW_PICK(4, 2)
 #undef NOCF_MBW_PICK
     if (!fk) return NOCF_E_SHAPE;
@@ -2873,7 +2907,8 @@ static int bwd_mid_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n, int
     e = hipLaunchKernel(fk, dim3((unsigned)rows), dim3(256), args, ldsBytes, st);
     if (e) return (int)e;
     if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
-    g_last_kernel = states ? "rollout_mono_bwd_kernel<states>" : (mode == 2 ? "rollout_mono_bwd_kernel<joint>" : "rollout_mono_bwd_kernel");
+    g_last_kernel = states ? "rollout_mono_bwd_kernel<states>" : (mode == 2 ? "rollout_mono_bwd_kernel<joint>" :
+                    (mode == 3 ? "rollout_mono_bwd_kernel<weighted>" : "rollout_mono_bwd_kernel"));
     g_last_errp = nullptr;
     return (int)hipGetLastError();
 #endif
@@ -2893,6 +2928,14 @@ int nocf_rollout_bwd_mid_w_f32(const NocfPhi* phi, const NocfProb* prob, int64_t
                                void* workspace, size_t workspace_bytes, void* stream) {
     return bwd_mid_impl(phi, prob, n, nt, stepper, t1, alph, inv_n, s_all, z_final, hs, act_rec, gpart, gpart_rows, lam0, lamW, lamW ? 2 : 0,
                         workspace, workspace_bytes, stream);
+}
+
+int nocf_rollout_bwd_mid_rw_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t nt, int32_t stepper, double t1,
+                                const float* alph, const float* wrow, const float* s_all, const float* z_final, const float* hs,
+                                const float* act_rec, float* gpart, int64_t gpart_rows, float* lam0, void* workspace, size_t workspace_bytes,
+                                void* stream) {
+    return bwd_mid_impl(phi, prob, n, nt, stepper, t1, alph, 0.0, s_all, z_final, hs, act_rec, gpart, gpart_rows, lam0, nullptr, 3,
+                        workspace, workspace_bytes, stream, wrow);
 }
 
 // ---- ensembles on the one-CU kernels (include/nocf.h): E networks of one shape, member e on workgroups [e * tiles, (e + 1) * tiles)

@@ -25,6 +25,7 @@ struct LaneBwdArgs {
     float* gpart; long P_total;
     float* lam0;
     float* lamW;              // [nt][n][d] (nullable): the state cotangent behind every step, dJ/dW of a disturbed rollout (STATES modes 1 and 2)
+    const float* wrow;        // [n] (RW instantiations only): one weight per sample, standing where inv_n stands (nocf_rollout_bwd_small_rw_f32)
 };
 
 __device__ __forceinline__ float sgnf(float v) { return (v > 0.f) ? 1.f : (v < 0.f ? -1.f : 0.f); }
@@ -34,8 +35,13 @@ __device__ __forceinline__ float sgnf(float v) { return (v > 0.f) ? 1.f : (v < 0
 // (entries 0, 3, 4, 5) and for the problem's alph_Q / alph_W (1, 2); la.inv_n is 1 / ea.n, the mean over ONE member's samples.  As there: the member of a wave is uniform,
 // its pointers and multipliers sit in scalar registers, every statement behind those reads is the single-network one, and every ENS test is
 // `if constexpr`.  Row g's gradient vector goes to gpart[g]: member e's partials are the contiguous rows [e ea.n, (e + 1) ea.n)
-template <int MP, int DP, int STATES = 0, bool ENS = false>
+//
+// RW (STATES = 0, no ensemble; nocf_rollout_bwd_small_rw_f32): the per-sample weight la.wrow[sample] stands where la.inv_n stands at the four
+// cotangent seeds (LAM, gbar, phib, kL): gpart[sample] = wrow[sample] grad J_sample, lam0[sample] = wrow[sample] dJ_sample/dx.  The sample of
+// a wave is uniform, so the weight is read once into a scalar register; every RW test is a compile-time choice at its place of use.
+template <int MP, int DP, int STATES = 0, bool ENS = false, bool RW = false>
 __global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, DevProb pb, EnsArgs ea) {
+    static_assert(!RW || (STATES == 0 && !ENS), "the weighted variant is the parameter-and-lam0 adjoint of one network");
     const int lane = threadIdx.x & 63;
     const long sample = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const bool live = sample < la.n;
@@ -51,6 +57,8 @@ __global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, D
         eA0 = at[0]; eAQ = at[1]; eAW = at[2]; eA3 = at[3]; eA4 = at[4]; eA5 = at[5];
     }
     // (below, `ENS ? member's : the call's` is a compile-time choice at the place of use: the other instantiations keep their statements)
+    float wI = 0.f;                                                 // RW: this wave's sample weight (a tail wave reads the last row's and writes nothing)
+    if constexpr (RW) wI = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, la.wrow[row])));
 
     // ---- weights: my row and my column of every matrix (as in the forward lane kernel)
     float k0row[DP], symA[DP], k1row[MP], k1col[MP], k0col[MP];
@@ -144,12 +152,12 @@ __global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, D
             const float dg = g - (ENS ? eA0 : la.a0) * res;
             const float eg = sgnf(dg);
             if (lane < d) {
-                LAM = la.inv_n * ((ENS ? eA0 : la.a0) * res + (ENS ? eA4 : la.a4) * ef * dg - (ENS ? eA5 : la.a5) * (ENS ? eA0 : la.a0) * eg);
-                gbar = la.inv_n * (ENS ? eA5 : la.a5) * eg;
+                LAM = (RW ? wI : la.inv_n) * ((ENS ? eA0 : la.a0) * res + (ENS ? eA4 : la.a4) * ef * dg - (ENS ? eA5 : la.a5) * (ENS ? eA0 : la.a0) * eg);
+                gbar = (RW ? wI : la.inv_n) * (ENS ? eA5 : la.a5) * eg;
             }
             // the value cotangent reuses the forward quantities: ubar = phib a, qbar = phib v, obar = phib y
             if constexpr (STATES != 1) {
-            const float phib = la.inv_n * (ENS ? eA4 : la.a4) * ef;
+            const float phib = (RW ? wI : la.inv_n) * (ENS ? eA4 : la.a4) * ef;
 #pragma unroll
             for (int kk = 0; kk < MP; ++kk) gK1[kk] = fmaf(phib * v, lane_bcast(u0, kk), gK1[kk]);
 #pragma unroll
@@ -216,7 +224,7 @@ __global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, D
             const float H = -Lg + sp2;
             const float gt = lane_bcast_u(g, d);
             const float eh = sgnf(gt - H);
-            const float kL = hs * wst * la.inv_n, kh = kL * (ENS ? eA3 : la.a3);
+            const float kL = hs * wst * (RW ? wI : la.inv_n), kh = kL * (ENS ? eA3 : la.a3);
             if (lane < d) {
                 const float fbar = hs * (wst * LAM + cpl * XP);
                 gbar = -fbar + (kL - eh * kh) * g;

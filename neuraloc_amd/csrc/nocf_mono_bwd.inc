@@ -145,11 +145,15 @@ __device__ __forceinline__ void mono_lowrank(const MonoPlan& mp, const f32x4& AZ
 // ENS (STATES = 0; nocf_rollout_bwd_mid_ensemble_f32): the adjoint of an ensemble rollout (nocf_mono.inc, MonoEnsArgs).  en.tiles =
 // nocf_mid_grad_rows workgroups per member; workgroup j of member e walks the member's tiles j, j + en.tiles, ... (the single-network tile
 // order) and writes partial vector gpart[e][j] = row blockIdx.x.  Every ENS test is a compile-time choice at its place of use.
-template <int KBM, int KBD, int STATES = 0, bool ENS = false>
+//
+// RW (STATES = 0, no ensemble; nocf_rollout_bwd_mid_rw_f32): the per-sample table lINV, which every cotangent seed already reads, is filled
+// with BwdArgs::wrow[row] instead of the one value inv_n (0 for the tail rows, as before): one load per sample and tile, nothing else differs.
+template <int KBM, int KBD, int STATES = 0, bool ENS = false, bool RW = false>
 __global__ void __launch_bounds__(256) rollout_mono_bwd_kernel(const MonoPlan* __restrict__ mpp, DevProb pb, const float* __restrict__ ws, BwdArgs ba,
                                                                MonoEnsArgs en) {
     static_assert(KBD == 1 || KBD == 2, "d + 1 <= 32: the (sample, entry) threads take KBD entries each; dM is KBD x KBD tiles on the four waves");
     static_assert(!ENS || STATES == 0, "ensembles take the full adjoint");
+    static_assert(!RW || (STATES == 0 && !ENS), "the weighted variant is the parameter-and-lam0 adjoint of one network");
     constexpr int MT = (KBM + 3) / 4;
     constexpr int T = 16;
     constexpr MonoBwdLds LL = mono_bwd_lds(KBM, KBD);
@@ -279,6 +283,8 @@ __global__ void __launch_bounds__(256) rollout_mono_bwd_kernel(const MonoPlan* _
         const long nvalid = (ba.n - row0 < T) ? (ba.n - row0) : T;
         __syncthreads();                                   // (the previous tile's last reads of the tables and rows)
         // per-sample tables: 1/N (0 for the tail rows that replicate a valid sample) and the cotangent of Phi(z(T), T) (terminal evaluation only)
+        if constexpr (RW) { if (tid < T) { lds[LL.lINV + tid] = (tid < nvalid) ? ba.wrow[row0 + tid] : 0.f; lds[LL.lPHIB + tid] = 0.f; } }
+        else
         if (tid < T) { lds[LL.lINV + tid] = (tid < nvalid) ? ba.inv_n : 0.f; lds[LL.lPHIB + tid] = 0.f; }
         __syncthreads();
         const float c16 = (float)(1.0 / 6.0), c26 = (float)(2.0 / 6.0);

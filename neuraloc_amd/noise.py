@@ -221,6 +221,7 @@ class _OCflowTrainNoisy(torch.autograd.Function):
                    _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
         _lib.check(rc, "nocf_rollout_record_noisy_f32")
         ctx.act = act if recorded.value else None
+        ctx.persample = persample                          # (the [n, 7] table: risk._OCflowTrainWeighted forms the per-sample costs from it)
         return _OCflowTrain._forward_tail(ctx, L, dev, net, prob, tspan, nt, stepper, alph, n_total, group, n, sums, s_all, z_out)
 
     @staticmethod

@@ -228,10 +228,12 @@ class _OCflowTrain(torch.autograd.Function):
         return _OCflowTrain._adjoint(ctx, gJ)
 
     @staticmethod
-    def _adjoint(ctx, gJ, want_w=False):
+    def _adjoint(ctx, gJ, want_w=False, wrow=None):
         """the backward of _OCflowTrain and of _OCflowTrainDisturbed: everything it reads is what either forward saved.
         want_w (minmax._OCflowTrainMinmax): the JOINT entry of the same family (nocf_rollout_bwd_small_w_f32 / _mid_w_f32 / _act_w_f32) runs in
-        place of the existing one and also writes lamW [nt, n, d] = dJc/dW; _finish returns it as W's gradient"""
+        place of the existing one and also writes lamW [nt, n, d] = dJc/dW; _finish returns it as W's gradient.
+        wrow (risk._OCflowTrainWeighted): [n] float32 on the device -- the WEIGHTED entry of the same family (nocf_rollout_bwd_small_rw_f32 /
+        _mid_rw_f32 / _act_rw_f32) runs in place of the existing one, with wrow where 1 / n_total stands: the gradients of sum_i wrow[i] J_i"""
         s_all, z_out = ctx.saved_tensors
         net, prob, nt, alph = ctx.net, ctx.prob, ctx.nt, ctx.alph
         if [p._version for p in net.parameters()] != ctx.param_versions:
@@ -265,15 +267,25 @@ class _OCflowTrain(torch.autograd.Function):
                                    "rebuild it")
             ctx.lamW = torch.empty(int(nt), n, d, device=dev)
             lamW = (_lib.ptr(ctx.lamW),)
-        f_small, f_mid, f_act = joint if want_w else (lib.nocf_rollout_bwd_small_f32, getattr(lib, "nocf_rollout_bwd_mid_f32", None),
-                                                      lib.nocf_rollout_bwd_act_f32)
+        inv_n = 1.0 / float(ctx.n_total)                            # the cotangent seed: one scalar, or (weighted entries) one weight per row
+        if wrow is not None:
+            weighted = _weighted_entries(lib)
+            if weighted is None:                           # a per-shape library cached by an older build: the shipped library has the entries
+                lib = _lib.lib()
+                weighted = _weighted_entries(lib)
+            if weighted is None:
+                raise RuntimeError("weighted_ocflow_train: the HIP library does not export nocf_rollout_bwd_small_rw_f32 / _mid_rw_f32 / "
+                                   "_act_rw_f32; rebuild it")
+            inv_n = _lib.ptr(wrow)
+        f_small, f_mid, f_act = joint if want_w else (weighted if wrow is not None else (
+            lib.nocf_rollout_bwd_small_f32, getattr(lib, "nocf_rollout_bwd_mid_f32", None), lib.nocf_rollout_bwd_act_f32))
         # small networks: the lane-style adjoint accumulates every gradient row in registers (one vector per sample)
         P = int(lib.nocf_small_grad_floats(d, m))
         gpart = torch.empty(n, P, device=dev) if (net.nTh == 2 and m <= 32 and D1 <= 32) else None
         if gpart is not None:
             with torch.cuda.device(dev):
                 rc = f_small(C.byref(phi_st), C.byref(prob_st), n, int(nt), _STEPPERS[ctx.stepper],
-                             float(ctx.tspan[1]), alph_c, 1.0 / float(ctx.n_total), _lib.ptr(s_all),
+                             float(ctx.tspan[1]), alph_c, inv_n, _lib.ptr(s_all),
                              _lib.ptr(z_out), _lib.ptr(hs), _lib.ptr(gpart), _lib.ptr(lam0), *lamW,
                              _lib.stream_ptr(dev))
             if rc == 0:
@@ -287,7 +299,7 @@ class _OCflowTrain(torch.autograd.Function):
             gmid = torch.empty(mid_rows, P, device=dev)
             with torch.cuda.device(dev):
                 rc = f_mid(C.byref(phi_st), C.byref(prob_st), n, int(nt), _STEPPERS[ctx.stepper],
-                           float(ctx.tspan[1]), alph_c, 1.0 / float(ctx.n_total), _lib.ptr(s_all),
+                           float(ctx.tspan[1]), alph_c, inv_n, _lib.ptr(s_all),
                            _lib.ptr(z_out), _lib.ptr(hs), _lib.ptr(getattr(ctx, "act", None)), _lib.ptr(gmid), mid_rows,
                            _lib.ptr(lam0), *lamW,
                            _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
@@ -308,7 +320,7 @@ class _OCflowTrain(torch.autograd.Function):
         PHIb = torch.zeros(n, device=dev)
         with torch.cuda.device(dev):
             rc = f_act(C.byref(phi_st), C.byref(prob_st), n, int(nt), _STEPPERS[ctx.stepper],
-                       float(ctx.tspan[1]), alph_c, 1.0 / float(ctx.n_total),
+                       float(ctx.tspan[1]), alph_c, inv_n,
                        _lib.ptr(s_all), _lib.ptr(z_out), _lib.ptr(hs),
                        _lib.ptr(Y), _lib.ptr(Ob), _lib.ptr(V), _lib.ptr(Ab), _lib.ptr(Qb),
                        _lib.ptr(U0), _lib.ptr(Wb), _lib.ptr(Gb), _lib.ptr(Sx),
@@ -478,6 +490,7 @@ class _OCflowTrainDisturbed(torch.autograd.Function):
                    _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
         _lib.check(rc, "nocf_rollout_record_disturbed_f32")
         ctx.act = act if recorded.value else None
+        ctx.persample = persample                          # (the [n, 7] table: risk._OCflowTrainWeighted forms the per-sample costs from it)
         return _OCflowTrain._forward_tail(ctx, L, dev, net, prob, tspan, nt, stepper, alph, n_total, group, n, sums, s_all, z_out)
 
     @staticmethod
@@ -498,6 +511,29 @@ _JOINT_ARGTYPES = {"nocf_rollout_bwd_small_w_f32": _JOINT_HEAD + [C.c_void_p] * 
                    "nocf_rollout_bwd_mid_w_f32": _JOINT_HEAD + [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                                                 C.c_void_p, C.c_size_t, C.c_void_p],
                    "nocf_rollout_bwd_act_w_f32": _JOINT_HEAD + [C.c_void_p] * 13 + [C.c_void_p, C.c_size_t, C.c_void_p]}
+
+
+_WEIGHTED_HEAD = [C.POINTER(_lib.NocfPhi), C.POINTER(_lib.NocfProb), C.c_int64, C.c_int32, C.c_int32, C.c_double,
+                  _lib.fp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+_WEIGHTED_ARGTYPES = {"nocf_rollout_bwd_small_rw_f32": _WEIGHTED_HEAD + [C.c_void_p] * 3,
+                      "nocf_rollout_bwd_mid_rw_f32": _WEIGHTED_HEAD + [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                                       C.c_void_p, C.c_size_t, C.c_void_p],
+                      "nocf_rollout_bwd_act_rw_f32": _WEIGHTED_HEAD + [C.c_void_p] * 12 + [C.c_void_p, C.c_size_t, C.c_void_p]}
+
+
+def _weighted_entries(L):
+    """(nocf_rollout_bwd_small_rw_f32, nocf_rollout_bwd_mid_rw_f32, nocf_rollout_bwd_act_rw_f32) of library L with their prototypes set --
+    the existing adjoint entries with `const float* wrow` in place of `double inv_n` --, or None when L lacks one of them"""
+    out = []
+    for name, argtypes in _WEIGHTED_ARGTYPES.items():
+        if not hasattr(L, name):
+            return None
+        f = getattr(L, name)
+        if f.argtypes is None:
+            f.restype = C.c_int
+            f.argtypes = argtypes
+        out.append(f)
+    return tuple(out)
 
 
 def _joint_entries(L):

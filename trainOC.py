@@ -35,7 +35,12 @@ one process.  Member e trains under per-step Brownian state disturbances sigma_e
 (neuraloc_amd.ensemble_noisy_ocflow_train), one launch per rollout and per adjoint for all members, on either family.
 The seed is noise_seed << 32 | iteration for ALL members (the --noise_rng counter convention, 0 <= noise_seed < 2**32): every member meets
 the same noise realisations scaled by its own level, so the members' costs are a paired comparison across sigma.  A level of 0 is the
-undisturbed member; validation stays undisturbed.  --members with --noise stays refused: this flag is the way in."""
+undisturbed member; validation stays undisturbed.  --members with --noise stays refused: this flag is the way in.
+--risk cvar|entropic --risk_level A [--risk_paths R] [--risk_mix M] (addition, with --noise SIGMA --noise_rng counter): risk-sensitive
+training (neuraloc_amd.risk_ocflow_train).  Every training batch is repeated R times (repeat_interleave: R noise paths
+per start) and the objective is the risk of each start's R costs -- CVaR at level A, or the entropic risk with theta = A -- blended with their
+mean by M; its exact gradient comes from one weighted adjoint launch.  The loss column carries the risk's value; validation stays undisturbed
+and averaged.  Single precision, one rank; not with --members or --adv."""
 import argparse
 import datetime
 import os
@@ -95,9 +100,14 @@ _FLAGS = [
     ("members_sigma", str, None, "(addition, with --members) S0,S1,...: E noise levels >= 0, member e trains under Brownian state disturbances "
                                  "sigma_e dB drawn inside the kernels (neuraloc_amd.ensemble_noisy_ocflow_train), all members under the seed "
                                  "noise_seed << 32 | iteration; validation stays undisturbed"),
+    ("risk", str, None, "(addition, with --noise SIGMA --noise_rng counter) cvar or entropic: train on a risk measure of each start's costs over "
+                        "--risk_paths noise paths (neuraloc_amd.risk_ocflow_train) instead of their mean"),
+    ("risk_level", float, None, "(addition, with --risk) cvar: the level 0 <= A < 1 (the mean of the worst (1 - A) share); entropic: theta > 0"),
+    ("risk_paths", int, 8, "(addition, with --risk) R >= 1 noise paths per start: every batch is repeated R times"),
+    ("risk_mix", float, 1.0, "(addition, with --risk) 0 <= M <= 1: the objective is (1 - M) mean + M risk"),
 ]
 _CHOICES = {"data": PROBLEM_NAMES, "optim": ["adam"], "prec": ["single", "double"], "approach": ["ocflow"], "noise_rng": ["torch", "counter"],
-            "adv_mode": ["free", "pgd"], "adv_objective": ["Jc", "control"], "members_family": list(na.ensemble.FAMILIES)}
+            "adv_mode": ["free", "pgd"], "risk": ["cvar", "entropic"], "adv_objective": ["Jc", "control"], "members_family": list(na.ensemble.FAMILIES)}
 
 
 def parse_args(argv=None):
@@ -109,6 +119,36 @@ def parse_args(argv=None):
     if a.new_alph is not None:
         a.new_alph = [float(v) for v in a.new_alph.split(",")]
     return a
+
+
+def risk_refusals(args, world):
+    """--risk: everything the risk-sensitive run does not take, refused before anything runs or is written"""
+    if args.risk is None:
+        if args.risk_level is not None:
+            raise SystemExit("--risk_level needs --risk cvar|entropic")
+        return
+    if args.prec == "double":
+        raise SystemExit("--risk runs in single precision only (the weighted adjoint takes no float64)")
+    if not args.noise > 0:
+        raise SystemExit("--risk needs --noise SIGMA > 0 (with --noise_rng counter): the risk is taken over each start's noise paths")
+    if args.noise_rng != "counter":
+        raise SystemExit("--risk needs --noise_rng counter, not --noise_rng torch: the paths' disturbances are drawn inside the kernels")
+    if args.members is not None or args.members_alph is not None or args.members_family != "lane" or args.members_sigma is not None:
+        raise SystemExit("--risk excludes --members: the weighted adjoint takes one network")
+    if args.adv > 0:
+        raise SystemExit("--risk excludes --adv: dJ/dW together with weights is not supported")
+    if world > 1:
+        raise SystemExit("--risk runs on one rank (one GPU): sharded batches are not supported")
+    if args.risk_level is None:
+        raise SystemExit("--risk needs --risk_level A")
+    if args.risk == "cvar" and not 0.0 <= args.risk_level < 1.0:
+        raise SystemExit("--risk cvar needs 0 <= --risk_level < 1")
+    if args.risk == "entropic" and not (0.0 < args.risk_level < float("inf")):
+        raise SystemExit("--risk entropic needs a finite --risk_level (theta) > 0")
+    if args.risk_paths < 1:
+        raise SystemExit("--risk_paths R must be >= 1")
+    if not 0.0 <= args.risk_mix <= 1.0:
+        raise SystemExit("--risk_mix M must lie in [0, 1]")
 
 
 def members_refusals(args, world):
@@ -279,6 +319,7 @@ def main(argv=None):
         raise SystemExit("--adv_objective control needs --adv_mode pgd: the free adversary climbs the training loss itself")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
+    risk_refusals(args, world)
     if args.members is not None or args.members_alph is not None or args.members_family != "lane" or args.members_sigma is not None:
         sigmas = members_sigma_levels(args)
         return train_members(args, members_refusals(args, world), sigmas)
@@ -341,7 +382,11 @@ def main(argv=None):
     end = time.time()
     for itr in range(1, args.niters + 1):
         optim.zero_grad()
-        if noise_counter:
+        if args.risk is not None:                         # R noise paths per start, rows [i R, (i + 1) R): the risk of each start's costs
+            Jc, cs, _ = na.risk_ocflow_train(x0.repeat_interleave(args.risk_paths, 0), net, prob, tspan, args.nt, args.risk, args.risk_level,
+                                             paths=args.risk_paths, mix=args.risk_mix, sigma=args.noise,
+                                             seed=(args.noise_seed << 32) | itr, stepper="rk4", alph=net.alph)
+        elif noise_counter:
             Jc, cs = na.noisy_ocflow_train(x0, net, prob, tspan, args.nt, args.noise, (args.noise_seed << 32) | itr, "rk4", net.alph,
                                            row_offset=lo, group=True if dist else None)
         elif noise_gen is not None:
