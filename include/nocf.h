@@ -652,6 +652,32 @@ int nocf_rollout_bwd_act_rw_f32(const NocfPhi* phi, const NocfProb* prob, int64_
                                 void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The WEIGHTED ENSEMBLE adjoints: nocf_rollout_bwd_small_ensemble_f32 / nocf_rollout_bwd_mid_ensemble_f32 with one weight per row of every
+ * member in place of the scalar inv_n -- a risk measure per member (a sweep over the CVaR level or over theta) differentiated in the one
+ * launch the members' means cost.  The kernels are the ensemble adjoints' further instantiation (ensemble AND weighted, both compile-time
+ * choices): the member's pointers and multipliers as in the ensemble adjoint, wrow[e][row] where inv_n stands at that row's cotangent seeds
+ * as in the weighted adjoint.
+ *   wrow   device [E, n] float32, contiguous, not modified: member e's weights are the n floats at wrow + e n -- the lane ensemble's row
+ *          order (row g of the E n batch reads wrow[g]) and the one-CU ensemble's member-major order alike.  Any finite values, negative and
+ *          zero included; nothing checks them on the device.  Tail rows of a member's last tile (one-CU) keep weight 0; a tail wave (lane)
+ *          replicates the last row and writes nothing
+ *   every output is the ensemble entry's with wrow[e][i] for inv_n: member e's partial vectors sum to sum_i wrow[e][i] grad J_{e,i} and
+ *          lam0[e][i] = wrow[e][i] dJ_{e,i}/dx.  Member e's results carry the bits of nocf_rollout_bwd_small_rw_f32 /
+ *          nocf_rollout_bwd_mid_rw_f32 with wrow + e n on that member alone; wrow filled with (float)inv_n gives the ensemble entry's bits
+ *   every other argument, buffer layout (lane: rows [e n, (e + 1) n) of gpart / lam0; one-CU: member-major, gpart_rows == the query's), the
+ *          workspace and every refusal: the ensemble entry's;  wrow == NULL: NOCF_E_NULL.  Every refusal returns before anything is enqueued
+ * nocf_last_rollout_kernel() reports "rollout_lane_bwd_kernel<ens,weighted>" / "rollout_mono_bwd_kernel<ens,weighted>".  nocf_version()
+ * is unchanged: callers probe for the symbols.  float32 only.
+ */
+int nocf_rollout_bwd_small_ensemble_rw_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper,
+                                           double t1, const float* alph, const float* wrow, const float* s_all, const float* z_final,
+                                           const float* hs, float* gpart, float* lam0, void* stream);
+int nocf_rollout_bwd_mid_ensemble_rw_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper,
+                                         double t1, const float* alph, const float* wrow, const float* s_all, const float* z_final,
+                                         const float* hs, const float* act_rec, float* gpart, int64_t gpart_rows, float* lam0,
+                                         void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * One step of projected gradient ascent on per-row disturbance paths, in place: for every row i, over its [nt, d] path of W,
  *     W_i += step (mask o g_i) / ||mask o g_i||_2          (the row is left untouched when that norm is 0 or not finite)
  *     W_i *= eps / ||W_i||_2   when ||W_i||_2 > eps         (projection onto the ball over the whole path)

@@ -17,6 +17,7 @@ from .minmax import minmax_ocflow_train, ascend_disturbances, adversarial_step, 
 from .ensemble import PhiEnsemble, ensemble_rollout, ensemble_ocflow_train
 from .ensemble_noise import ensemble_noisy_rollout, ensemble_noisy_ocflow_train, ensemble_noise_study
 from .risk import risk_weights, weighted_ocflow_train, risk_ocflow_train
+from .ensemble_risk import ensemble_risk_weights, ensemble_weighted_ocflow_train, ensemble_risk_ocflow_train
 
 __all__ = ["Phi", "ResNN", "antiderivTanh", "derivTanh", "OCflow", "ocG", "Cross2D", "SwarmTraj",
            "Quadcopter", "initProb", "resample", "OCflow_sharded", "shard_rows", "reduce_cost_sums", "check_errors",
@@ -27,4 +28,5 @@ __all__ = ["Phi", "ResNN", "antiderivTanh", "derivTanh", "OCflow", "ocG", "Cross
            "minmax_ocflow_train", "ascend_disturbances", "adversarial_step", "pgd_ocflow_train",
            "PhiEnsemble", "ensemble_rollout", "ensemble_ocflow_train",
            "ensemble_noisy_rollout", "ensemble_noisy_ocflow_train", "ensemble_noise_study",
-           "risk_weights", "weighted_ocflow_train", "risk_ocflow_train"]
+           "risk_weights", "weighted_ocflow_train", "risk_ocflow_train",
+           "ensemble_risk_weights", "ensemble_weighted_ocflow_train", "ensemble_risk_ocflow_train"]

@@ -1950,13 +1950,14 @@ int nocf_rollout_record_noisy_ensemble_f32(const NocfPhi* phi, const NocfProb* p
                                  nullptr, nullptr, s_all, stream, &nz);
 }
 
-int nocf_rollout_bwd_small_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper, double t1,
-                                        const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
-                                        float* gpart, float* lam0, void* stream) {
+// weighted: the ENS && RW instantiation (nocf_rollout_bwd_small_ensemble_rw_f32) -- wrow [E, n] in place of inv_n, which is then not read
+static int bwd_small_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper, double t1,
+                                   const float* alph, double inv_n, const float* wrow, bool weighted, const float* s_all, const float* z_final,
+                                   const float* hs, float* gpart, float* lam0, void* stream) {
     DevProb pb;
     const int rc = ensemble_check(phi, prob, n, members, nt, stepper, true, &pb);
     if (rc) return rc;
-    if (!alph || !s_all || !z_final || !hs || !gpart) return NOCF_E_NULL;
+    if (!alph || !s_all || !z_final || !hs || !gpart || (weighted && !wrow)) return NOCF_E_NULL;
     const long rows = (long)members * n;
     LaneBwdArgs la;
     memset(&la, 0, sizeof(la));
@@ -1964,13 +1965,14 @@ int nocf_rollout_bwd_small_ensemble_f32(const NocfPhi* phi, const NocfProb* prob
     la.d = phi->d; la.m = phi->m; la.r = phi->r; la.nAg = pb.nAgents;
     la.sAll = s_all; la.zT = z_final; la.hs = hs; la.n = rows; la.nt = nt; la.nstage = (stepper == NOCF_RK4) ? 4 : 1;
     la.t1 = (float)t1; la.inv_n = (float)inv_n;
-    la.gpart = gpart; la.P_total = nocf_small_grad_floats(phi->d, phi->m); la.lam0 = lam0; la.lamW = nullptr; la.wrow = nullptr;
+    la.gpart = gpart; la.P_total = nocf_small_grad_floats(phi->d, phi->m); la.lam0 = lam0; la.lamW = nullptr; la.wrow = weighted ? wrow : nullptr;
     const EnsArgs ea{(unsigned)n, 0l, alph};
     hipStream_t st = (hipStream_t)stream;
     const int grid = (int)((rows + 3) / 4);
     const int MPsel = phi->m <= 16 ? 16 : 32;
     const int DPsel = phi->d + 1 <= 8 ? 8 : (phi->d + 1 <= 16 ? 16 : 32);
-#define NOCF_LANEB_ENS_LAUNCH(MPV, DPV) hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV, 0, true>), dim3(grid), dim3(256), 0, st, la, pb, ea)
+#define NOCF_LANEB_ENS_LAUNCH(MPV, DPV) do { if (weighted) hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV, 0, true, true>), dim3(grid), dim3(256), 0, st, la, pb, ea); \
+                                              else hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV, 0, true>), dim3(grid), dim3(256), 0, st, la, pb, ea); } while (0)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (g_prof_on) {
         if (hipEventCreate(&ev0) || hipEventCreate(&ev1)) return (int)hipErrorUnknown;
@@ -1980,9 +1982,21 @@ int nocf_rollout_bwd_small_ensemble_f32(const NocfPhi* phi, const NocfProb* prob
     else             { if (DPsel == 8) { NOCF_LANEB_ENS_LAUNCH(32, 8); } else if (DPsel == 16) { NOCF_LANEB_ENS_LAUNCH(32, 16); } else { NOCF_LANEB_ENS_LAUNCH(32, 32); } }
 #undef NOCF_LANEB_ENS_LAUNCH
     if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
-    g_last_kernel = "rollout_lane_bwd_kernel<ens>";
+    g_last_kernel = weighted ? "rollout_lane_bwd_kernel<ens,weighted>" : "rollout_lane_bwd_kernel<ens>";
     g_last_errp = nullptr;
     return (int)hipGetLastError();
+}
+
+int nocf_rollout_bwd_small_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper, double t1,
+                                        const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
+                                        float* gpart, float* lam0, void* stream) {
+    return bwd_small_ensemble_impl(phi, prob, n, members, nt, stepper, t1, alph, inv_n, nullptr, false, s_all, z_final, hs, gpart, lam0, stream);
+}
+
+int nocf_rollout_bwd_small_ensemble_rw_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper,
+                                           double t1, const float* alph, const float* wrow, const float* s_all, const float* z_final,
+                                           const float* hs, float* gpart, float* lam0, void* stream) {
+    return bwd_small_ensemble_impl(phi, prob, n, members, nt, stepper, t1, alph, 0.0, wrow, true, s_all, z_final, hs, gpart, lam0, stream);
 }
 
 int nocf_contract_f32(const float* A, const float* B, int64_t K, int32_t m, int32_t n, float* C, int32_t accumulate,
@@ -3135,11 +3149,13 @@ int nocf_rollout_record_noisy_mid_ensemble_f32(const NocfPhi* phi, const NocfPro
 #endif
 }
 
-int nocf_rollout_bwd_mid_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper, double t1,
-                                      const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
-                                      const float* act_rec, float* gpart, int64_t gpart_rows, float* lam0,
-                                      void* workspace, size_t workspace_bytes, void* stream) {
+// weighted: the ENS && RW instantiation (nocf_rollout_bwd_mid_ensemble_rw_f32) -- wrow [E, n] in place of inv_n, which is then not read
+static int bwd_mid_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper, double t1,
+                                 const float* alph, double inv_n, const float* wrow, bool weighted, const float* s_all, const float* z_final,
+                                 const float* hs, const float* act_rec, float* gpart, int64_t gpart_rows, float* lam0,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
 #ifdef NOCF_JIT_ONLY
+    (void)wrow; (void)weighted;
     (void)phi; (void)prob; (void)n; (void)members; (void)nt; (void)stepper; (void)t1; (void)alph; (void)inv_n; (void)s_all; (void)z_final; (void)hs;
     (void)act_rec; (void)gpart; (void)gpart_rows; (void)lam0; (void)workspace; (void)workspace_bytes; (void)stream;
     return NOCF_E_SHAPE;
@@ -3149,7 +3165,7 @@ int nocf_rollout_bwd_mid_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, 
     MonoPlan mpl;
     int rc = mid_ensemble_check(phi, prob, n, members, nt, stepper, true, workspace, workspace_bytes, &pb, &pl, &mpl);
     if (rc) return rc;
-    if (!alph || !s_all || !z_final || !hs || !gpart) return NOCF_E_NULL;
+    if (!alph || !s_all || !z_final || !hs || !gpart || (weighted && !wrow)) return NOCF_E_NULL;
     const int64_t rows = nocf_mid_grad_rows(phi->d, phi->m, phi->nTh, phi->r, pb.nAgents, n);
     if (rows == 0) return NOCF_E_SHAPE;
     if (gpart_rows != rows) return NOCF_E_WORKSPACE;       // (gpart [E, rows, P]: the member blocks sit rows partial vectors apart)
@@ -3162,7 +3178,7 @@ int nocf_rollout_bwd_mid_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, 
     ba.sAll = s_all; ba.zT = z_final; ba.hs = hs; ba.n = n; ba.nt = nt; ba.nstage = (stepper == NOCF_RK4) ? 4 : 1;
     ba.t1 = (float)t1;
     ba.inv_n = (float)inv_n;
-    ba.lam0 = lam0; ba.lamW = nullptr;
+    ba.lam0 = lam0; ba.lamW = nullptr; ba.wrow = weighted ? wrow : nullptr;
     ba.gpart = gpart; ba.gstride = nocf_small_grad_floats(phi->d, phi->m);
     ba.act = (act_rec && (phi->m % 16) == 0) ? act_rec : nullptr; ba.actRows = (long)nt * ba.nstage * n;
     MonoEnsArgs en;
@@ -3171,7 +3187,8 @@ int nocf_rollout_bwd_mid_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, 
     en.sas = (long)nt * ba.nstage * n * (phi->d + 1); en.acts = (long)mono_ens_act_stride(phi, n, nt, stepper);
     const size_t ldsBytes = (size_t)mpl.pp.ldsFloats * 4;
     const void* fk = nullptr;
-#define NOCF_MBW_ENS_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) fk = reinterpret_cast<const void*>(rollout_mono_bwd_kernel<M_, D_, 0, true>);
+#define NOCF_MBW_ENS_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) fk = weighted ? reinterpret_cast<const void*>(rollout_mono_bwd_kernel<M_, D_, 0, true, true>) \
+                                                                                     : reinterpret_cast<const void*>(rollout_mono_bwd_kernel<M_, D_, 0, true>);
     NOCF_MBW_ENS_PICK(8, 1) NOCF_MBW_ENS_PICK(6, 1) NOCF_MBW_ENS_PICK(4, 1) NOCF_MBW_ENS_PICK(8, 2) NOCF_MBW_ENS_PICK(6, 2) NOCF_MBW_ENS_PICK(4, 2)
 #undef NOCF_MBW_ENS_PICK
     if (!fk) return NOCF_E_SHAPE;
@@ -3189,10 +3206,26 @@ int nocf_rollout_bwd_mid_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, 
     e = hipLaunchKernel(fk, dim3((unsigned)((long)members * rows)), dim3(256), args, ldsBytes, st);
     if (e) return (int)e;
     if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
-    g_last_kernel = "rollout_mono_bwd_kernel<ens>";
+    g_last_kernel = weighted ? "rollout_mono_bwd_kernel<ens,weighted>" : "rollout_mono_bwd_kernel<ens>";
     g_last_errp = nullptr;
     return (int)hipGetLastError();
 #endif
+}
+
+int nocf_rollout_bwd_mid_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper, double t1,
+                                      const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
+                                      const float* act_rec, float* gpart, int64_t gpart_rows, float* lam0,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+    return bwd_mid_ensemble_impl(phi, prob, n, members, nt, stepper, t1, alph, inv_n, nullptr, false, s_all, z_final, hs, act_rec, gpart,
+                                 gpart_rows, lam0, workspace, workspace_bytes, stream);
+}
+
+int nocf_rollout_bwd_mid_ensemble_rw_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper,
+                                         double t1, const float* alph, const float* wrow, const float* s_all, const float* z_final,
+                                         const float* hs, const float* act_rec, float* gpart, int64_t gpart_rows, float* lam0,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+    return bwd_mid_ensemble_impl(phi, prob, n, members, nt, stepper, t1, alph, 0.0, wrow, true, s_all, z_final, hs, act_rec, gpart,
+                                 gpart_rows, lam0, workspace, workspace_bytes, stream);
 }
 
 // ---- the state-only adjoint (include/nocf.h): lane, then one-CU, then per-tile -- nocf_rollout_record_disturbed_f32's order.  A family says

@@ -39,9 +39,12 @@ __device__ __forceinline__ float sgnf(float v) { return (v > 0.f) ? 1.f : (v < 0
 // RW (STATES = 0, no ensemble; nocf_rollout_bwd_small_rw_f32): the per-sample weight la.wrow[sample] stands where la.inv_n stands at the four
 // cotangent seeds (LAM, gbar, phib, kL): gpart[sample] = wrow[sample] grad J_sample, lam0[sample] = wrow[sample] dJ_sample/dx.  The sample of
 // a wave is uniform, so the weight is read once into a scalar register; every RW test is a compile-time choice at its place of use.
+//
+// ENS && RW (STATES = 0; nocf_rollout_bwd_small_ensemble_rw_f32): both of the above and nothing more.  la.wrow is [E, ea.n] contiguous, which is
+// the row order of the E * ea.n batch, so row g reads la.wrow[g] through the same scalar read; la.inv_n is not read.
 template <int MP, int DP, int STATES = 0, bool ENS = false, bool RW = false>
 __global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, DevProb pb, EnsArgs ea) {
-    static_assert(!RW || (STATES == 0 && !ENS), "the weighted variant is the parameter-and-lam0 adjoint of one network");
+    static_assert(!RW || STATES == 0, "the weighted variants are parameter-and-lam0 adjoints");
     const int lane = threadIdx.x & 63;
     const long sample = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const bool live = sample < la.n;

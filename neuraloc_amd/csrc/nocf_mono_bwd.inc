@@ -148,12 +148,15 @@ __device__ __forceinline__ void mono_lowrank(const MonoPlan& mp, const f32x4& AZ
 //
 // RW (STATES = 0, no ensemble; nocf_rollout_bwd_mid_rw_f32): the per-sample table lINV, which every cotangent seed already reads, is filled
 // with BwdArgs::wrow[row] instead of the one value inv_n (0 for the tail rows, as before): one load per sample and tile, nothing else differs.
+//
+// ENS && RW (STATES = 0; nocf_rollout_bwd_mid_ensemble_rw_f32): BwdArgs::wrow is [E, en.n]; member e's workgroups move it to their member's
+// row where they move zT and lam0, and fill lINV from it as the RW instantiation does.  ba.inv_n is not read.
 template <int KBM, int KBD, int STATES = 0, bool ENS = false, bool RW = false>
 __global__ void __launch_bounds__(256) rollout_mono_bwd_kernel(const MonoPlan* __restrict__ mpp, DevProb pb, const float* __restrict__ ws, BwdArgs ba,
                                                                MonoEnsArgs en) {
     static_assert(KBD == 1 || KBD == 2, "d + 1 <= 32: the (sample, entry) threads take KBD entries each; dM is KBD x KBD tiles on the four waves");
     static_assert(!ENS || STATES == 0, "ensembles take the full adjoint");
-    static_assert(!RW || (STATES == 0 && !ENS), "the weighted variant is the parameter-and-lam0 adjoint of one network");
+    static_assert(!RW || STATES == 0, "the weighted variants are parameter-and-lam0 adjoints");
     constexpr int MT = (KBM + 3) / 4;
     constexpr int T = 16;
     constexpr MonoBwdLds LL = mono_bwd_lds(KBM, KBD);
@@ -195,6 +198,7 @@ __global__ void __launch_bounds__(256) rollout_mono_bwd_kernel(const MonoPlan* _
         const long eo = (long)(blockIdx.x / en.tiles) * en.n;
         ba.zT += eo * (d + 4);
         if (ba.lam0) ba.lam0 += eo * d;
+        if constexpr (RW) ba.wrow += eo;
     }
 
     // ---- resident weights (as the forward kernel's)

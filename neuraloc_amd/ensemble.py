@@ -53,6 +53,31 @@ _ARGTYPES_MID = {
 }
 
 
+# the weighted ensemble adjoints (ensemble_risk.py): the two adjoint entries above with `const float* wrow` [E, n] in place of `double inv_n`
+_ARGTYPES_RW = {
+    "lane": ("nocf_rollout_bwd_small_ensemble_rw_f32",
+             [C.POINTER(_lib.NocfPhi), C.POINTER(_lib.NocfProb), C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+              C.c_double, C.c_void_p, C.c_void_p] + [C.c_void_p] * 5 + [C.c_void_p]),
+    "mid": ("nocf_rollout_bwd_mid_ensemble_rw_f32",
+            [C.POINTER(_lib.NocfPhi), C.POINTER(_lib.NocfProb), C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+             C.c_double, C.c_void_p, C.c_void_p] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p] + _TAIL),
+}
+
+
+def weighted_entry(L, family):
+    """the weighted ensemble adjoint of a family in library L, prototype set; RuntimeError when L does not export BOTH (a library is rebuilt
+    as a whole)"""
+    missing = [name for name, _ in _ARGTYPES_RW.values() if not hasattr(L, name)]
+    if missing:
+        raise RuntimeError("ensemble: the HIP library does not export " + " / ".join(missing) + "; rebuild it")
+    name, argtypes = _ARGTYPES_RW[family]
+    f = getattr(L, name)
+    if f.argtypes is None:
+        f.restype = C.c_int
+        f.argtypes = argtypes
+    return f
+
+
 def _entries_mid(L):
     """(nocf_rollout_mid_ensemble_f32, nocf_rollout_record_mid_ensemble_f32, nocf_rollout_bwd_mid_ensemble_f32) of library L with their
     prototypes set (and nocf_mid_ensemble_workspace_bytes'), or None when L lacks one of the four"""
@@ -502,6 +527,7 @@ class _EnsembleTrain(torch.autograd.Function):
         ctx.x_needs_grad = bool(x.requires_grad)
         b = _launch(x, ens, prob, tspan, nt, stepper, alph, record=True, noise=noise)
         ctx.ens, ctx.prob, ctx.tspan, ctx.nt, ctx.stepper, ctx.table = ens, prob, tspan, nt, stepper, b["table"]
+        ctx.persample = b["persample"]                      # (the weighted calls form their sums and risks from it: ensemble_risk.py)
         ctx.save_for_backward(b["s_all"], b["z_out"])
         # the adjoint re-reads the weights from the module: they must still be the ones this forward ran with
         ctx.param_versions = [p._version for _, p in ens._params()]
@@ -518,7 +544,8 @@ class _EnsembleTrain(torch.autograd.Function):
         return _EnsembleTrain._adjoint(ctx, gJ)
 
     @staticmethod
-    def _adjoint(ctx, gJ):
+    def _adjoint(ctx, gJ, wrow=None):
+        """wrow: [E, n] float32 weights (ensemble_risk.py) -- the launch is the weighted entry's, wrow standing where 1 / n stands"""
         s_all, z_out = ctx.saved_tensors
         ens, prob, nt = ctx.ens, ctx.prob, ctx.nt
         if [p._version for _, p in ens._params()] != ctx.param_versions:
@@ -529,6 +556,9 @@ class _EnsembleTrain(torch.autograd.Function):
         D1 = d + 1
         n = z_out.shape[0] // E
         L, (_f_eval, _f_rec, f_bwd) = _shipped()
+        what = "nocf_rollout_bwd_small_ensemble_f32"
+        if wrow is not None:
+            f_bwd, what = weighted_entry(L, "lane"), _ARGTYPES_RW["lane"][0]
         phi_st, keep1 = ens._c_struct()
         prob_st, keep2 = prob._c_struct(dev)
         hs = _step_sizes(ctx.tspan, nt).to(dev)
@@ -537,9 +567,9 @@ class _EnsembleTrain(torch.autograd.Function):
         lam0 = torch.empty(E * n, d, device=dev) if ctx.x_needs_grad else None
         with torch.cuda.device(dev):
             rc = f_bwd(C.byref(phi_st), C.byref(prob_st), n, E, int(nt), _STEPPERS[ctx.stepper], float(ctx.tspan[1]),
-                       _lib.ptr(ctx.table), 1.0 / float(n), _lib.ptr(s_all), _lib.ptr(z_out), _lib.ptr(hs),
+                       _lib.ptr(ctx.table), 1.0 / float(n) if wrow is None else _lib.ptr(wrow), _lib.ptr(s_all), _lib.ptr(z_out), _lib.ptr(hs),
                        _lib.ptr(gpart), _lib.ptr(lam0), _lib.stream_ptr(dev))
-        _lib.check(rc, "nocf_rollout_bwd_small_ensemble_f32")
+        _lib.check(rc, what)
         # per member the sum and the products of the single-network adjoint (train._unpack_partials on the member's contiguous [n, P] slice:
         # the same calls on the same shapes, so the same bits); only the exact elementwise scaling by gJ runs on the stacked tensors
         A = ens.A.detach()
@@ -566,6 +596,7 @@ class _EnsembleTrainMid(torch.autograd.Function):
         b = _launch_mid(x, ens, prob, tspan, nt, stepper, alph, record=True, noise=noise)
         ctx.ens, ctx.prob, ctx.tspan, ctx.nt, ctx.stepper, ctx.table = ens, prob, tspan, nt, stepper, b["table"]
         ctx.act = b["act"]
+        ctx.persample = b["persample"]
         ctx.save_for_backward(b["s_all"], b["z_out"])
         ctx.param_versions = [p._version for _, p in ens._params()]
         sums, a = b["sums"], b["table"]
@@ -581,7 +612,8 @@ class _EnsembleTrainMid(torch.autograd.Function):
         return _EnsembleTrainMid._adjoint(ctx, gJ)
 
     @staticmethod
-    def _adjoint(ctx, gJ):
+    def _adjoint(ctx, gJ, wrow=None):
+        """wrow: as for _EnsembleTrain._adjoint"""
         s_all, z_out = ctx.saved_tensors
         ens, prob, nt = ctx.ens, ctx.prob, ctx.nt
         if [p._version for _, p in ens._params()] != ctx.param_versions:
@@ -592,6 +624,9 @@ class _EnsembleTrainMid(torch.autograd.Function):
         D1 = d + 1
         n = z_out.shape[1]
         L, (_f_eval, _f_rec, f_bwd) = _shipped_mid()
+        what = "nocf_rollout_bwd_mid_ensemble_f32"
+        if wrow is not None:
+            f_bwd, what = weighted_entry(L, "mid"), _ARGTYPES_RW["mid"][0]
         phi_st, keep1 = ens._c_struct()
         prob_st, keep2 = prob._c_struct(dev)
         ws = ens.mid_workspace(L, dev)
@@ -604,9 +639,9 @@ class _EnsembleTrainMid(torch.autograd.Function):
         lam0 = torch.empty(E, n, d, device=dev) if ctx.x_needs_grad else None
         with torch.cuda.device(dev):
             rc = f_bwd(C.byref(phi_st), C.byref(prob_st), n, E, int(nt), _STEPPERS[ctx.stepper], float(ctx.tspan[1]),
-                       _lib.ptr(ctx.table), 1.0 / float(n), _lib.ptr(s_all), _lib.ptr(z_out), _lib.ptr(hs), _lib.ptr(ctx.act),
-                       _lib.ptr(gpart), rows, _lib.ptr(lam0), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-        _lib.check(rc, "nocf_rollout_bwd_mid_ensemble_f32")
+                       _lib.ptr(ctx.table), 1.0 / float(n) if wrow is None else _lib.ptr(wrow), _lib.ptr(s_all), _lib.ptr(z_out), _lib.ptr(hs),
+                       _lib.ptr(ctx.act), _lib.ptr(gpart), rows, _lib.ptr(lam0), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+        _lib.check(rc, what)
         ctx.act = None
         # per member the sum and the products of the single-network adjoint: train._unpack_partials on the member's contiguous [rows, P] block
         A = ens.A.detach()

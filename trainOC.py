@@ -40,7 +40,13 @@ undisturbed member; validation stays undisturbed.  --members with --noise stays 
 training (neuraloc_amd.risk_ocflow_train).  Every training batch is repeated R times (repeat_interleave: R noise paths
 per start) and the objective is the risk of each start's R costs -- CVaR at level A, or the entropic risk with theta = A -- blended with their
 mean by M; its exact gradient comes from one weighted adjoint launch.  The loss column carries the risk's value; validation stays undisturbed
-and averaged.  Single precision, one rank; not with --members or --adv."""
+and averaged.  Single precision, one rank; not with --members or --adv.
+--members_risk cvar|entropic|mean --members_risk_level A | A0,A1,... [--members_risk_paths R] [--members_risk_mix M] (addition, with --members E
+--members_sigma ...): a sweep over the risk level in one process (neuraloc_amd.ensemble_risk_ocflow_train).  Every
+training batch is repeated R times (default 8) for every member, member e's objective is the risk of each start's R costs at ITS level -- one
+level per member, or one for all -- and all members' exact gradients come from ONE weighted ensemble adjoint launch.  The seed is
+noise_seed << 32 | iteration for all members; the loss column carries each member's risk value; validation stays undisturbed and averaged;
+one checkpoint per member as with --members.  --risk with --members stays refused: this flag is the way in."""
 import argparse
 import datetime
 import os
@@ -100,6 +106,12 @@ _FLAGS = [
     ("members_sigma", str, None, "(addition, with --members) S0,S1,...: E noise levels >= 0, member e trains under Brownian state disturbances "
                                  "sigma_e dB drawn inside the kernels (neuraloc_amd.ensemble_noisy_ocflow_train), all members under the seed "
                                  "noise_seed << 32 | iteration; validation stays undisturbed"),
+    ("members_risk", str, None, "(addition, with --members E --members_sigma ...) cvar, entropic or mean: every member trains on that risk measure "
+                                "of each start's costs over --members_risk_paths noise paths (neuraloc_amd.ensemble_risk_ocflow_train)"),
+    ("members_risk_level", str, None, "(addition, with --members_risk) A or A0,A1,...: one level for all members or one per member (cvar: "
+                                      "0 <= A < 1; entropic: theta > 0)"),
+    ("members_risk_paths", int, 8, "(addition, with --members_risk) R >= 1 noise paths per start: every batch is repeated R times per member"),
+    ("members_risk_mix", float, 1.0, "(addition, with --members_risk) 0 <= M <= 1: every member's objective is (1 - M) mean + M risk"),
     ("risk", str, None, "(addition, with --noise SIGMA --noise_rng counter) cvar or entropic: train on a risk measure of each start's costs over "
                         "--risk_paths noise paths (neuraloc_amd.risk_ocflow_train) instead of their mean"),
     ("risk_level", float, None, "(addition, with --risk) cvar: the level 0 <= A < 1 (the mean of the worst (1 - A) share); entropic: theta > 0"),
@@ -107,7 +119,7 @@ _FLAGS = [
     ("risk_mix", float, 1.0, "(addition, with --risk) 0 <= M <= 1: the objective is (1 - M) mean + M risk"),
 ]
 _CHOICES = {"data": PROBLEM_NAMES, "optim": ["adam"], "prec": ["single", "double"], "approach": ["ocflow"], "noise_rng": ["torch", "counter"],
-            "adv_mode": ["free", "pgd"], "risk": ["cvar", "entropic"], "adv_objective": ["Jc", "control"], "members_family": list(na.ensemble.FAMILIES)}
+            "adv_mode": ["free", "pgd"], "risk": ["cvar", "entropic"], "members_risk": list(na.risk.RISKS), "adv_objective": ["Jc", "control"], "members_family": list(na.ensemble.FAMILIES)}
 
 
 def parse_args(argv=None):
@@ -119,6 +131,15 @@ def parse_args(argv=None):
     if a.new_alph is not None:
         a.new_alph = [float(v) for v in a.new_alph.split(",")]
     return a
+
+
+def _level_in_range(risk, level):
+    """the range of a risk's level: cvar 0 <= A < 1, entropic a finite theta > 0 (the mean reads none)"""
+    if risk == "cvar":
+        return 0.0 <= level < 1.0
+    if risk == "entropic":
+        return 0.0 < level < float("inf")
+    return True
 
 
 def risk_refusals(args, world):
@@ -141,9 +162,9 @@ def risk_refusals(args, world):
         raise SystemExit("--risk runs on one rank (one GPU): sharded batches are not supported")
     if args.risk_level is None:
         raise SystemExit("--risk needs --risk_level A")
-    if args.risk == "cvar" and not 0.0 <= args.risk_level < 1.0:
+    if args.risk == "cvar" and not _level_in_range("cvar", args.risk_level):
         raise SystemExit("--risk cvar needs 0 <= --risk_level < 1")
-    if args.risk == "entropic" and not (0.0 < args.risk_level < float("inf")):
+    if args.risk == "entropic" and not _level_in_range("entropic", args.risk_level):
         raise SystemExit("--risk entropic needs a finite --risk_level (theta) > 0")
     if args.risk_paths < 1:
         raise SystemExit("--risk_paths R must be >= 1")
@@ -210,9 +231,45 @@ def members_sigma_levels(args):
     return levels
 
 
-def train_members(args, rows, sigmas=None):
+def members_risk_spec(args, sigmas):
+    """--members_risk: the members' risk measure and levels, refused before anything runs or is written.
+    -> (risk, E levels, paths, mix), or None without the flag"""
+    if args.members_risk is None:
+        if args.members_risk_level is not None:
+            raise SystemExit("--members_risk_level needs --members_risk cvar|entropic|mean")
+        return None
+    if args.members is None or args.members < 1 or sigmas is None:
+        raise SystemExit("--members_risk needs --members E --members_sigma S0,S1,...: the risk is taken over each start's noise paths")
+    if args.members_risk_level is None:
+        if args.members_risk != "mean":
+            raise SystemExit("--members_risk needs --members_risk_level A or A0,A1,...")
+        levels = [0.0]
+    else:
+        try:
+            levels = [float(v) for v in args.members_risk_level.split(",")]
+        except ValueError:
+            raise SystemExit("--members_risk_level A or A0,A1,...: a number or a comma-separated list of numbers, got {!r}".format(
+                args.members_risk_level))
+    if len(levels) == 1:
+        levels = levels * args.members
+    if len(levels) != args.members:
+        raise SystemExit("--members_risk_level needs one level for all members or one per member: --members {:} but {:} values".format(
+            args.members, len(levels)))
+    if args.members_risk == "cvar" and not all(_level_in_range("cvar", v) for v in levels):
+        raise SystemExit("--members_risk cvar needs 0 <= --members_risk_level < 1 for every member")
+    if args.members_risk == "entropic" and not all(_level_in_range("entropic", v) for v in levels):
+        raise SystemExit("--members_risk entropic needs a finite --members_risk_level (theta) > 0 for every member")
+    if args.members_risk_paths < 1:
+        raise SystemExit("--members_risk_paths R must be >= 1")
+    if not 0.0 <= args.members_risk_mix <= 1.0:
+        raise SystemExit("--members_risk_mix M must lie in [0, 1]")
+    return args.members_risk, levels, args.members_risk_paths, args.members_risk_mix
+
+
+def train_members(args, rows, sigmas=None, mrisk=None):
     """the training loop of main() for E networks at once (neuraloc_amd.ensemble): same schedule, one log line and one checkpoint per member.
-    sigmas (--members_sigma): member e's training rollouts run under Brownian disturbances of level sigmas[e]"""
+    sigmas (--members_sigma): member e's training rollouts run under Brownian disturbances of level sigmas[e].  mrisk (--members_risk, with
+    sigmas): (risk, E levels, paths, mix) -- member e trains on that risk of each start's `paths` costs at its level"""
     E = args.members
     dev = torch.device("cuda", args.gpu)
     assert torch.cuda.is_available(), "trainOC.py needs an MI355X: there is no CPU path"
@@ -251,7 +308,11 @@ def train_members(args, rows, sigmas=None):
     end = time.time()
     for itr in range(1, args.niters + 1):
         optim.zero_grad()
-        if sigmas is not None:                            # one seed for all members: the same noise realisations at E levels
+        if mrisk is not None:                             # R noise paths per start and member, rows [i R, (i + 1) R) of every member's batch
+            Jc, cs, _ = na.ensemble_risk_ocflow_train(x0.repeat_interleave(mrisk[2], 0), ens, prob, tspan, args.nt, mrisk[0], mrisk[1],
+                                                      paths=mrisk[2], mix=mrisk[3], sigma=[[s_] for s_ in sigmas],
+                                                      seed=(args.noise_seed << 32) | itr, stepper="rk4", family=args.members_family)
+        elif sigmas is not None:                          # one seed for all members: the same noise realisations at E levels
             Jc, cs = na.ensemble_noisy_ocflow_train(x0, ens, prob, tspan, args.nt, [[s_] for s_ in sigmas], (args.noise_seed << 32) | itr,
                                                     "rk4", family=args.members_family)
         else:
@@ -320,9 +381,11 @@ def main(argv=None):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     risk_refusals(args, world)
-    if args.members is not None or args.members_alph is not None or args.members_family != "lane" or args.members_sigma is not None:
+    if args.members is not None or args.members_alph is not None or args.members_family != "lane" or args.members_sigma is not None \
+            or args.members_risk is not None or args.members_risk_level is not None:
         sigmas = members_sigma_levels(args)
-        return train_members(args, members_refusals(args, world), sigmas)
+        mrisk = members_risk_spec(args, sigmas)
+        return train_members(args, members_refusals(args, world), sigmas, mrisk)
     if world > 1:
         import torch.distributed as dist
         local = int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count())
