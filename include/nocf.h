@@ -693,6 +693,76 @@ int nocf_disturbance_ascent_f32(float* W, const float* g, const float* mask, int
                                 double step, double eps, void* stream);
 
 /*
+ * ADVERSARIAL ENSEMBLES: the ensemble launches above under a TENSOR disturbance per member, the ensemble adjoints with
+ * dJ/dW written out, and the ascent step over all members -- an iteration of min-max training, or of a worst-case search, for E networks in
+ * the three launches it costs one.  Every member e meets z_{k+1} = step(z_k) + W[e][k].
+ *
+ * Forwards: nocf_rollout_ensemble_f32 / nocf_rollout_record_ensemble_f32 (lane kernels) and nocf_rollout_mid_ensemble_f32 /
+ * nocf_rollout_record_mid_ensemble_f32 (one-CU kernels) with, behind x_member_stride,
+ *   W                device [E, nt, n, d] float32, MEMBER-major (both families): member e's slice is exactly the [nt, n, d] tensor of
+ *                    nocf_rollout_disturbed_f32; not modified
+ *   w_member_stride  nt * n * d, or 0: ONE [nt, n, d] tensor that every member meets (as x_member_stride = 0 shares the starts)
+ * and every other argument, buffer layout (lane: time-major over E*n rows; one-CU: member-major) and refusal is the undisturbed sibling's.
+ * Member e's results carry the bits of nocf_rollout_disturbed_f32 / nocf_rollout_record_disturbed_f32 with W + e w_member_stride on that
+ * member alone, on the same kernel family.  W == NULL: NOCF_E_NULL; a stride that is neither 0 nor nt n d: NOCF_E_SHAPE.
+ * nocf_last_rollout_kernel(): "rollout_lane_kernel<ens,disturbed>" / "rollout_mono_kernel<ens,disturbed>".
+ *
+ * Adjoints: nocf_rollout_bwd_small_ensemble_f32 / nocf_rollout_bwd_mid_ensemble_f32 with one more output behind lam0,
+ *   lamW   device [E, nt, n, d] float32, MEMBER-major (both families), contiguous: lamW[e][k] = the state cotangent of member e behind step k
+ *          = dJ_e/dW[e][k]; lamW[e][nt-1] is the terminal cotangent.  Only rows < n of each member and d floats per row are written
+ * _w (JOINT): every output of the ensemble adjoint exactly as it forms them AND lamW; lamW == NULL: the call IS the ensemble adjoint (same
+ *          kernel, same bits).  Member e's results carry the bits of nocf_rollout_bwd_small_w_f32 / nocf_rollout_bwd_mid_w_f32 on that member
+ * _states (STATE-ONLY): no gpart / gpart_rows argument; lam0 [E*n, d] (lane) / [E, n, d] (one-CU) and lamW, at least one of them (both NULL:
+ *          NOCF_E_NULL); alph rows with [3..5] = 0 give the control objective.  Member e's results carry the bits of
+ *          nocf_rollout_bwd_states_f32 on that member, on the same family
+ * Every other argument, the workspace and every refusal: the ensemble adjoint's.  A weighted (wrow) adversarial ensemble does not exist.
+ * nocf_last_rollout_kernel(): "rollout_lane_bwd_kernel<ens,joint>" / "<ens,states>", "rollout_mono_bwd_kernel<ens,joint>" / "<ens,states>".
+ *
+ * nocf_disturbance_ascent_ensemble_f32: nocf_disturbance_ascent_f32 over the E * n rows of W / g [E, nt, n, d] in one launch; the member of a
+ * row picks its step length and radius from the DEVICE tables steps [E] and epss [E] (float32, values >= 0 and finite: nothing checks them on
+ * the device).  Member e's slice carries the bits of nocf_disturbance_ascent_f32 on it with ((double)steps[e], (double)epss[e]).
+ * NULL W / g / steps / epss: NOCF_E_NULL; n, members, nt, d < 1 or members * n >= 2^31: NOCF_E_SHAPE.
+ *
+ * Every refusal returns before anything is enqueued.  nocf_version() is unchanged: callers probe for the symbols.  float32 only.
+ */
+int nocf_rollout_disturbed_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members, int64_t x_member_stride,
+                                        const float* W, int64_t w_member_stride,
+                                        double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                        float* z_out, float* persample, float* cost_sums, float* cost_means, float* zFull, float* ctrlFull,
+                                        void* workspace, size_t workspace_bytes, void* stream);
+int nocf_rollout_record_disturbed_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members,
+                                               int64_t x_member_stride, const float* W, int64_t w_member_stride,
+                                               double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                               float* z_out, float* persample, float* cost_sums, float* s_all,
+                                               void* workspace, size_t workspace_bytes, void* stream);
+int nocf_rollout_disturbed_mid_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members,
+                                            int64_t x_member_stride, const float* W, int64_t w_member_stride,
+                                            double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                            float* z_out, float* persample, float* cost_sums, float* cost_means, float* zFull, float* ctrlFull,
+                                            void* workspace, size_t workspace_bytes, void* stream);
+int nocf_rollout_record_disturbed_mid_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members,
+                                                   int64_t x_member_stride, const float* W, int64_t w_member_stride,
+                                                   double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                                   float* z_out, float* persample, float* cost_sums, float* s_all, float* act_rec, int32_t* recorded,
+                                                   void* workspace, size_t workspace_bytes, void* stream);
+int nocf_rollout_bwd_small_ensemble_w_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper,
+                                          double t1, const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
+                                          float* gpart, float* lam0, float* lamW, void* stream);
+int nocf_rollout_bwd_mid_ensemble_w_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper,
+                                        double t1, const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
+                                        const float* act_rec, float* gpart, int64_t gpart_rows, float* lam0, float* lamW,
+                                        void* workspace, size_t workspace_bytes, void* stream);
+int nocf_rollout_bwd_small_ensemble_states_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper,
+                                               double t1, const float* alph, double inv_n, const float* s_all, const float* z_final,
+                                               const float* hs, float* lam0, float* lamW, void* stream);
+int nocf_rollout_bwd_mid_ensemble_states_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper,
+                                             double t1, const float* alph, double inv_n, const float* s_all, const float* z_final,
+                                             const float* hs, const float* act_rec, float* lam0, float* lamW,
+                                             void* workspace, size_t workspace_bytes, void* stream);
+int nocf_disturbance_ascent_ensemble_f32(float* W, const float* g, const float* mask, int64_t n, int32_t members, int32_t nt, int32_t d,
+                                         const float* steps, const float* epss, void* stream);
+
+/*
  * C[m, n] (+)= sum_k A[k, 0..m) (x) B[k, 0..n) for small outputs (m, n <= 512, at most 64 tiles of 64 x 64) and very many rows: the contraction of the rows that
  * nocf_rollout_bwd_f32 streams into the weight gradients of a SMALL network (what torch autograd does with one mm per
  * parameter in the backward of trainOC.py:173).  Two launches, deterministic.  Wider networks contract with library GEMMs.

@@ -18,6 +18,9 @@ from .ensemble import PhiEnsemble, ensemble_rollout, ensemble_ocflow_train
 from .ensemble_noise import ensemble_noisy_rollout, ensemble_noisy_ocflow_train, ensemble_noise_study
 from .risk import risk_weights, weighted_ocflow_train, risk_ocflow_train
 from .ensemble_risk import ensemble_risk_weights, ensemble_weighted_ocflow_train, ensemble_risk_ocflow_train
+from .ensemble_minmax import (ensemble_disturbed_rollout, ensemble_disturbed_ocflow_train, ensemble_minmax_ocflow_train,
+                              ensemble_disturbance_gradient, ensemble_ascend_disturbances, ensemble_worst_case_disturbances,
+                              ensemble_adversarial_step)
 
 __all__ = ["Phi", "ResNN", "antiderivTanh", "derivTanh", "OCflow", "ocG", "Cross2D", "SwarmTraj",
            "Quadcopter", "initProb", "resample", "OCflow_sharded", "shard_rows", "reduce_cost_sums", "check_errors",
@@ -29,4 +32,7 @@ __all__ = ["Phi", "ResNN", "antiderivTanh", "derivTanh", "OCflow", "ocG", "Cross
            "PhiEnsemble", "ensemble_rollout", "ensemble_ocflow_train",
            "ensemble_noisy_rollout", "ensemble_noisy_ocflow_train", "ensemble_noise_study",
            "risk_weights", "weighted_ocflow_train", "risk_ocflow_train",
-           "ensemble_risk_weights", "ensemble_weighted_ocflow_train", "ensemble_risk_ocflow_train"]
+           "ensemble_risk_weights", "ensemble_weighted_ocflow_train", "ensemble_risk_ocflow_train",
+           "ensemble_disturbed_rollout", "ensemble_disturbed_ocflow_train", "ensemble_minmax_ocflow_train",
+           "ensemble_disturbance_gradient", "ensemble_ascend_disturbances", "ensemble_worst_case_disturbances",
+           "ensemble_adversarial_step"]

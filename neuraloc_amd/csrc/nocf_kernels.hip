@@ -1849,11 +1849,14 @@ static int ensemble_check(const NocfPhi* phi, const NocfProb* prob, int64_t n, i
 // the noise of a noisy ensemble (nocf_rollout_noisy_ensemble_f32, nocf_rollout_noisy_mid_ensemble_f32): device tables scale [E, d] and seeds [E],
 // and the key of every member's row 0
 struct EnsNoiseSpec { const float* scale; const uint64_t* seeds; int64_t row0; };
+// the tensor disturbance of a disturbed ensemble (nocf_rollout_disturbed_ensemble_f32, nocf_rollout_disturbed_mid_ensemble_f32): device W
+// [E, nt, n, d] with stride nt n d, or one [nt, n, d] for all members with stride 0
+struct EnsDistSpec { const float* W; int64_t stride; };
 
 static int rollout_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members, int64_t x_member_stride,
                                  double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
                                  float* z_out, float* persample, float* cost_sums, float* cost_means, float* zFull, float* ctrlFull,
-                                 float* s_all, void* stream, const EnsNoiseSpec* noise = nullptr) {
+                                 float* s_all, void* stream, const EnsNoiseSpec* noise = nullptr, const EnsDistSpec* dist = nullptr) {
     DevProb pb;
     const int rc = ensemble_check(phi, prob, n, members, nt, stepper, false, &pb);
     if (rc) return rc;
@@ -1861,6 +1864,8 @@ static int rollout_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, const
     if ((zFull != nullptr) != (ctrlFull != nullptr)) return NOCF_E_NULL;
     if ((cost_sums && !persample) || (cost_means && !cost_sums)) return NOCF_E_NULL;
     if (x_member_stride != 0 && x_member_stride != n * phi->d) return NOCF_E_SHAPE;
+    if (dist && !dist->W) return NOCF_E_NULL;
+    if (dist && dist->stride != 0 && dist->stride != (int64_t)nt * n * phi->d) return NOCF_E_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     const long rows = (long)members * n;
     RollArgs ra;
@@ -1870,12 +1875,14 @@ static int rollout_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, const
     ra.cdim = nocf_ctrl_dim(prob, phi->d);
     ra.sAll = s_all;
     if (noise) ra.nzRow0 = (long)noise->row0;             // (the scale and the seed are per member: EnsNoiseArgs)
+    if (dist) ra.dist = dist->W;                          // (the member's slice begins EnsNoiseArgs::ws floats times the member behind it)
     LaneArgs la;
     memset(&la, 0, sizeof(la));
     la.P = DevPhi{phi->K0, phi->b0, phi->K, phi->b, phi->w, phi->A, phi->cw, phi->cb_dev};
     la.d = phi->d; la.m = phi->m; la.r = phi->r; la.nAg = pb.nAgents;
     const EnsArgs ea{(unsigned)n, (long)x_member_stride, alph};
-    const EnsNoiseArgs nz{noise ? noise->scale : nullptr, noise ? reinterpret_cast<const unsigned long long*>(noise->seeds) : nullptr};
+    const EnsNoiseArgs nz{noise ? noise->scale : nullptr, noise ? reinterpret_cast<const unsigned long long*>(noise->seeds) : nullptr,
+                          dist ? (long)dist->stride : 0l};
     const int grid = (int)((rows + 3) / 4);
     const int MPsel = phi->m <= 16 ? 16 : 32;
     const int DPsel = phi->d + 1 <= 8 ? 8 : (phi->d + 1 <= 16 ? 16 : 32);
@@ -1884,7 +1891,9 @@ static int rollout_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, const
         if (hipEventCreate(&ev0) || hipEventCreate(&ev1)) return (int)hipErrorUnknown;
         (void)hipEventRecord(ev0, st);
     }
-#define NOCF_LANE_ENS_LAUNCH(MPV, DPV) do { if (noise && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 2, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz); \
+#define NOCF_LANE_ENS_LAUNCH(MPV, DPV) do { if (dist && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 1, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz); \
+                                             else if (dist) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 1, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz); \
+                                             else if (noise && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 2, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz); \
                                              else if (noise) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 2, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz); \
                                              else if (s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 0, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz); \
                                              else hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 0, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz); } while (0)
@@ -1893,7 +1902,7 @@ static int rollout_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, const
 #undef NOCF_LANE_ENS_LAUNCH
     hipError_t e = hipGetLastError();
     if (e) return (int)e;
-    g_last_kernel = noise ? "rollout_lane_kernel<ens,noisy>" : "rollout_lane_kernel<ens>";
+    g_last_kernel = dist ? "rollout_lane_kernel<ens,disturbed>" : noise ? "rollout_lane_kernel<ens,noisy>" : "rollout_lane_kernel<ens>";
     g_last_errp = nullptr;
     if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
     if (cost_sums) {
@@ -1950,14 +1959,42 @@ int nocf_rollout_record_noisy_ensemble_f32(const NocfPhi* phi, const NocfProb* p
                                  nullptr, nullptr, s_all, stream, &nz);
 }
 
+// the same two under a tensor disturbance W [E, nt, n, d] (or one [nt, n, d] for all members, w_member_stride = 0), DESIGN 3.17
+int nocf_rollout_disturbed_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members, int64_t x_member_stride,
+                                        const float* W, int64_t w_member_stride,
+                                        double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                        float* z_out, float* persample, float* cost_sums, float* cost_means, float* zFull, float* ctrlFull,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+    (void)workspace; (void)workspace_bytes;
+    if (!W) return NOCF_E_NULL;
+    const EnsDistSpec ds{W, w_member_stride};
+    return rollout_ensemble_impl(phi, prob, x, n, members, x_member_stride, t0, t1, nt, stepper, alph, z_out, persample, cost_sums, cost_means,
+                                 zFull, ctrlFull, nullptr, stream, nullptr, &ds);
+}
+
+int nocf_rollout_record_disturbed_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members,
+                                               int64_t x_member_stride, const float* W, int64_t w_member_stride,
+                                               double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                               float* z_out, float* persample, float* cost_sums, float* s_all,
+                                               void* workspace, size_t workspace_bytes, void* stream) {
+    (void)workspace; (void)workspace_bytes;
+    if (!W || !s_all || !z_out) return NOCF_E_NULL;
+    const EnsDistSpec ds{W, w_member_stride};
+    return rollout_ensemble_impl(phi, prob, x, n, members, x_member_stride, t0, t1, nt, stepper, alph, z_out, persample, cost_sums, nullptr,
+                                 nullptr, nullptr, s_all, stream, nullptr, &ds);
+}
+
 // weighted: the ENS && RW instantiation (nocf_rollout_bwd_small_ensemble_rw_f32) -- wrow [E, n] in place of inv_n, which is then not read
+// mode 2 (nocf_rollout_bwd_small_ensemble_w_f32): the ENS joint instantiation -- gpart and lamW [E, nt, n, d]; mode 1
+// (nocf_rollout_bwd_small_ensemble_states_f32): the ENS state-only one -- no gpart, lam0 and / or lamW
 static int bwd_small_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper, double t1,
                                    const float* alph, double inv_n, const float* wrow, bool weighted, const float* s_all, const float* z_final,
-                                   const float* hs, float* gpart, float* lam0, void* stream) {
+                                   const float* hs, float* gpart, float* lam0, void* stream, float* lamW = nullptr, int mode = 0) {
     DevProb pb;
     const int rc = ensemble_check(phi, prob, n, members, nt, stepper, true, &pb);
     if (rc) return rc;
-    if (!alph || !s_all || !z_final || !hs || !gpart || (weighted && !wrow)) return NOCF_E_NULL;
+    if (!alph || !s_all || !z_final || !hs || (mode != 1 && !gpart) || (weighted && !wrow)) return NOCF_E_NULL;
+    if ((mode == 2 && !lamW) || (mode == 1 && !lam0 && !lamW)) return NOCF_E_NULL;
     const long rows = (long)members * n;
     LaneBwdArgs la;
     memset(&la, 0, sizeof(la));
@@ -1965,13 +2002,15 @@ static int bwd_small_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, int
     la.d = phi->d; la.m = phi->m; la.r = phi->r; la.nAg = pb.nAgents;
     la.sAll = s_all; la.zT = z_final; la.hs = hs; la.n = rows; la.nt = nt; la.nstage = (stepper == NOCF_RK4) ? 4 : 1;
     la.t1 = (float)t1; la.inv_n = (float)inv_n;
-    la.gpart = gpart; la.P_total = nocf_small_grad_floats(phi->d, phi->m); la.lam0 = lam0; la.lamW = nullptr; la.wrow = weighted ? wrow : nullptr;
+    la.gpart = gpart; la.P_total = nocf_small_grad_floats(phi->d, phi->m); la.lam0 = lam0; la.lamW = mode != 0 ? lamW : nullptr; la.wrow = weighted ? wrow : nullptr;
     const EnsArgs ea{(unsigned)n, 0l, alph};
     hipStream_t st = (hipStream_t)stream;
     const int grid = (int)((rows + 3) / 4);
     const int MPsel = phi->m <= 16 ? 16 : 32;
     const int DPsel = phi->d + 1 <= 8 ? 8 : (phi->d + 1 <= 16 ? 16 : 32);
-#define NOCF_LANEB_ENS_LAUNCH(MPV, DPV) do { if (weighted) hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV, 0, true, true>), dim3(grid), dim3(256), 0, st, la, pb, ea); \
+#define NOCF_LANEB_ENS_LAUNCH(MPV, DPV) do { if (mode == 2) hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV, 2, true>), dim3(grid), dim3(256), 0, st, la, pb, ea); \
+                                              else if (mode == 1) hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV, 1, true>), dim3(grid), dim3(256), 0, st, la, pb, ea); \
+                                              else if (weighted) hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV, 0, true, true>), dim3(grid), dim3(256), 0, st, la, pb, ea); \
                                               else hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV, 0, true>), dim3(grid), dim3(256), 0, st, la, pb, ea); } while (0)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (g_prof_on) {
@@ -1982,7 +2021,8 @@ static int bwd_small_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, int
     else             { if (DPsel == 8) { NOCF_LANEB_ENS_LAUNCH(32, 8); } else if (DPsel == 16) { NOCF_LANEB_ENS_LAUNCH(32, 16); } else { NOCF_LANEB_ENS_LAUNCH(32, 32); } }
 #undef NOCF_LANEB_ENS_LAUNCH
     if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
-    g_last_kernel = weighted ? "rollout_lane_bwd_kernel<ens,weighted>" : "rollout_lane_bwd_kernel<ens>";
+    g_last_kernel = mode == 2 ? "rollout_lane_bwd_kernel<ens,joint>" : mode == 1 ? "rollout_lane_bwd_kernel<ens,states>" :
+                    (weighted ? "rollout_lane_bwd_kernel<ens,weighted>" : "rollout_lane_bwd_kernel<ens>");
     g_last_errp = nullptr;
     return (int)hipGetLastError();
 }
@@ -1997,6 +2037,20 @@ int nocf_rollout_bwd_small_ensemble_rw_f32(const NocfPhi* phi, const NocfProb* p
                                            double t1, const float* alph, const float* wrow, const float* s_all, const float* z_final,
                                            const float* hs, float* gpart, float* lam0, void* stream) {
     return bwd_small_ensemble_impl(phi, prob, n, members, nt, stepper, t1, alph, 0.0, wrow, true, s_all, z_final, hs, gpart, lam0, stream);
+}
+
+int nocf_rollout_bwd_small_ensemble_w_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper,
+                                          double t1, const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
+                                          float* gpart, float* lam0, float* lamW, void* stream) {
+    return bwd_small_ensemble_impl(phi, prob, n, members, nt, stepper, t1, alph, inv_n, nullptr, false, s_all, z_final, hs, gpart, lam0, stream,
+                                   lamW, lamW ? 2 : 0);
+}
+
+int nocf_rollout_bwd_small_ensemble_states_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper,
+                                               double t1, const float* alph, double inv_n, const float* s_all, const float* z_final,
+                                               const float* hs, float* lam0, float* lamW, void* stream) {
+    return bwd_small_ensemble_impl(phi, prob, n, members, nt, stepper, t1, alph, inv_n, nullptr, false, s_all, z_final, hs, nullptr, lam0, stream,
+                                   lamW, 1);
 }
 
 int nocf_contract_f32(const float* A, const float* B, int64_t K, int32_t m, int32_t n, float* C, int32_t accumulate,
@@ -2993,7 +3047,7 @@ static int rollout_mid_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, c
                                      double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
                                      float* z_out, float* persample, float* cost_sums, float* cost_means, float* zFull, float* ctrlFull,
                                      float* s_all, float* act, int32_t* act_recorded, void* workspace, size_t workspace_bytes, void* stream,
-                                     const EnsNoiseSpec* noise = nullptr) {
+                                     const EnsNoiseSpec* noise = nullptr, const EnsDistSpec* dist = nullptr) {
     if (act_recorded) *act_recorded = 0;
     DevProb pb;
     DevPlan pl;
@@ -3004,6 +3058,8 @@ static int rollout_mid_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, c
     if ((zFull != nullptr) != (ctrlFull != nullptr)) return NOCF_E_NULL;
     if ((cost_sums && !persample) || (cost_means && !cost_sums)) return NOCF_E_NULL;
     if (x_member_stride != 0 && x_member_stride != n * phi->d) return NOCF_E_SHAPE;
+    if (dist && !dist->W) return NOCF_E_NULL;
+    if (dist && dist->stride != 0 && dist->stride != (int64_t)nt * n * phi->d) return NOCF_E_SHAPE;
     if (s_all && env_int("NOCF_MONO_REC", 1) == 0) return NOCF_E_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     float* ws = (float*)workspace;
@@ -3020,7 +3076,9 @@ static int rollout_mid_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, c
     const bool mono_rec = act && s_all && (phi->m % 16) == 0 && phi->m > 32;
     if (mono_rec) { ra.act = act; ra.actRows = (long)nt * nstage * n; }
     if (noise) ra.nzRow0 = (long)noise->row0;             // (the scale and the seed are per member: EnsNoiseArgs)
-    EnsNoiseArgs nz{noise ? noise->scale : nullptr, noise ? reinterpret_cast<const unsigned long long*>(noise->seeds) : nullptr};
+    if (dist) ra.dist = dist->W;                          // (the member's slice begins EnsNoiseArgs::ws floats times the member behind it)
+    EnsNoiseArgs nz{noise ? noise->scale : nullptr, noise ? reinterpret_cast<const unsigned long long*>(noise->seeds) : nullptr,
+                    dist ? (long)dist->stride : 0l};
     MonoEnsArgs en;
     memset(&en, 0, sizeof(en));
     en.n = (unsigned)n; en.tiles = (unsigned)((n + 15) / 16); en.xs = (long)x_member_stride; en.wss = (long)(mono_ens_ws_stride(mpl) / 4);
@@ -3029,7 +3087,9 @@ static int rollout_mid_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, c
     en.acts = (long)mono_ens_act_stride(phi, n, nt, stepper);
     const size_t ldsBytes = (size_t)mpl.pp.ldsFloats * 4;
     const void* fk = nullptr;
-#define NOCF_MONO_ENS_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) fk = noise ? (s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, 2, true>) \
+#define NOCF_MONO_ENS_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) fk = dist ? (s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, 1, true>) \
+                                                                                                : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 1, true>)) \
+                                                                                 : noise ? (s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, 2, true>) \
                                                                                                  : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 2, true>)) \
                                                                                  : s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, 0, true>) \
                                                                                          : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 0, true>);
@@ -3049,7 +3109,7 @@ static int rollout_mid_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, c
     e = hipLaunchKernel(fk, dim3((unsigned)((long)members * en.tiles)), dim3(256), args, ldsBytes, st);
     if (e) return (int)e;
     if (mono_rec && act_recorded) *act_recorded = 1;
-    g_last_kernel = noise ? "rollout_mono_kernel<ens,noisy>" : "rollout_mono_kernel<ens>";
+    g_last_kernel = dist ? "rollout_mono_kernel<ens,disturbed>" : noise ? "rollout_mono_kernel<ens,noisy>" : "rollout_mono_kernel<ens>";
     g_last_errp = nullptr;
     e = hipGetLastError();
     if (e) return (int)e;
@@ -3149,13 +3209,54 @@ int nocf_rollout_record_noisy_mid_ensemble_f32(const NocfPhi* phi, const NocfPro
 #endif
 }
 
+// the same two under a tensor disturbance W [E, nt, n, d] (or one [nt, n, d] for all members, w_member_stride = 0), DESIGN 3.17
+int nocf_rollout_disturbed_mid_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members,
+                                            int64_t x_member_stride, const float* W, int64_t w_member_stride,
+                                            double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                            float* z_out, float* persample, float* cost_sums, float* cost_means, float* zFull, float* ctrlFull,
+                                            void* workspace, size_t workspace_bytes, void* stream) {
+#ifdef NOCF_JIT_ONLY
+    (void)phi; (void)prob; (void)x; (void)n; (void)members; (void)x_member_stride; (void)W; (void)w_member_stride;
+    (void)t0; (void)t1; (void)nt; (void)stepper; (void)alph;
+    (void)z_out; (void)persample; (void)cost_sums; (void)cost_means; (void)zFull; (void)ctrlFull; (void)workspace; (void)workspace_bytes; (void)stream;
+    return NOCF_E_SHAPE;
+#else
+    if (!W) return NOCF_E_NULL;
+    const EnsDistSpec ds{W, w_member_stride};
+    return rollout_mid_ensemble_impl(phi, prob, x, n, members, x_member_stride, t0, t1, nt, stepper, alph, z_out, persample, cost_sums, cost_means,
+                                     zFull, ctrlFull, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream, nullptr, &ds);
+#endif
+}
+
+int nocf_rollout_record_disturbed_mid_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n, int32_t members,
+                                                   int64_t x_member_stride, const float* W, int64_t w_member_stride,
+                                                   double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                                   float* z_out, float* persample, float* cost_sums, float* s_all, float* act_rec, int32_t* recorded,
+                                                   void* workspace, size_t workspace_bytes, void* stream) {
+#ifdef NOCF_JIT_ONLY
+    (void)phi; (void)prob; (void)x; (void)n; (void)members; (void)x_member_stride; (void)W; (void)w_member_stride;
+    (void)t0; (void)t1; (void)nt; (void)stepper; (void)alph;
+    (void)z_out; (void)persample; (void)cost_sums; (void)s_all; (void)act_rec; (void)workspace; (void)workspace_bytes; (void)stream;
+    if (recorded) *recorded = 0;
+    return NOCF_E_SHAPE;
+#else
+    if (recorded) *recorded = 0;
+    if (!W || !s_all || !z_out) return NOCF_E_NULL;
+    const EnsDistSpec ds{W, w_member_stride};
+    return rollout_mid_ensemble_impl(phi, prob, x, n, members, x_member_stride, t0, t1, nt, stepper, alph, z_out, persample, cost_sums, nullptr,
+                                     nullptr, nullptr, s_all, act_rec, recorded, workspace, workspace_bytes, stream, nullptr, &ds);
+#endif
+}
+
 // weighted: the ENS && RW instantiation (nocf_rollout_bwd_mid_ensemble_rw_f32) -- wrow [E, n] in place of inv_n, which is then not read
+// mode 2 (nocf_rollout_bwd_mid_ensemble_w_f32): the ENS joint instantiation -- gpart and lamW [E, nt, n, d]; mode 1
+// (nocf_rollout_bwd_mid_ensemble_states_f32): the ENS state-only one -- no gpart, lam0 and / or lamW
 static int bwd_mid_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper, double t1,
                                  const float* alph, double inv_n, const float* wrow, bool weighted, const float* s_all, const float* z_final,
                                  const float* hs, const float* act_rec, float* gpart, int64_t gpart_rows, float* lam0,
-                                 void* workspace, size_t workspace_bytes, void* stream) {
+                                 void* workspace, size_t workspace_bytes, void* stream, float* lamW = nullptr, int mode = 0) {
 #ifdef NOCF_JIT_ONLY
-    (void)wrow; (void)weighted;
+    (void)wrow; (void)weighted; (void)lamW; (void)mode;
     (void)phi; (void)prob; (void)n; (void)members; (void)nt; (void)stepper; (void)t1; (void)alph; (void)inv_n; (void)s_all; (void)z_final; (void)hs;
     (void)act_rec; (void)gpart; (void)gpart_rows; (void)lam0; (void)workspace; (void)workspace_bytes; (void)stream;
     return NOCF_E_SHAPE;
@@ -3165,10 +3266,11 @@ static int bwd_mid_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, int64
     MonoPlan mpl;
     int rc = mid_ensemble_check(phi, prob, n, members, nt, stepper, true, workspace, workspace_bytes, &pb, &pl, &mpl);
     if (rc) return rc;
-    if (!alph || !s_all || !z_final || !hs || !gpart || (weighted && !wrow)) return NOCF_E_NULL;
+    if (!alph || !s_all || !z_final || !hs || (mode != 1 && !gpart) || (weighted && !wrow)) return NOCF_E_NULL;
+    if ((mode == 2 && !lamW) || (mode == 1 && !lam0 && !lamW)) return NOCF_E_NULL;
     const int64_t rows = nocf_mid_grad_rows(phi->d, phi->m, phi->nTh, phi->r, pb.nAgents, n);
     if (rows == 0) return NOCF_E_SHAPE;
-    if (gpart_rows != rows) return NOCF_E_WORKSPACE;       // (gpart [E, rows, P]: the member blocks sit rows partial vectors apart)
+    if (mode != 1 && gpart_rows != rows) return NOCF_E_WORKSPACE;       // (gpart [E, rows, P]: the member blocks sit rows partial vectors apart)
     hipStream_t st = (hipStream_t)stream;
     float* ws = (float*)workspace;
     rc = mid_ensemble_pack(phi, mpl.pp, mpl, members, ws, st);
@@ -3178,7 +3280,7 @@ static int bwd_mid_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, int64
     ba.sAll = s_all; ba.zT = z_final; ba.hs = hs; ba.n = n; ba.nt = nt; ba.nstage = (stepper == NOCF_RK4) ? 4 : 1;
     ba.t1 = (float)t1;
     ba.inv_n = (float)inv_n;
-    ba.lam0 = lam0; ba.lamW = nullptr; ba.wrow = weighted ? wrow : nullptr;
+    ba.lam0 = lam0; ba.lamW = mode != 0 ? lamW : nullptr; ba.wrow = weighted ? wrow : nullptr;
     ba.gpart = gpart; ba.gstride = nocf_small_grad_floats(phi->d, phi->m);
     ba.act = (act_rec && (phi->m % 16) == 0) ? act_rec : nullptr; ba.actRows = (long)nt * ba.nstage * n;
     MonoEnsArgs en;
@@ -3187,7 +3289,9 @@ static int bwd_mid_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, int64
     en.sas = (long)nt * ba.nstage * n * (phi->d + 1); en.acts = (long)mono_ens_act_stride(phi, n, nt, stepper);
     const size_t ldsBytes = (size_t)mpl.pp.ldsFloats * 4;
     const void* fk = nullptr;
-#define NOCF_MBW_ENS_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) fk = weighted ? reinterpret_cast<const void*>(rollout_mono_bwd_kernel<M_, D_, 0, true, true>) \
+#define NOCF_MBW_ENS_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) fk = mode == 2 ? reinterpret_cast<const void*>(rollout_mono_bwd_kernel<M_, D_, 2, true>) \
+                                                                           : mode == 1 ? reinterpret_cast<const void*>(rollout_mono_bwd_kernel<M_, D_, 1, true>) \
+                                                                           : weighted ? reinterpret_cast<const void*>(rollout_mono_bwd_kernel<M_, D_, 0, true, true>) \
                                                                                      : reinterpret_cast<const void*>(rollout_mono_bwd_kernel<M_, D_, 0, true>);
     NOCF_MBW_ENS_PICK(8, 1) NOCF_MBW_ENS_PICK(6, 1) NOCF_MBW_ENS_PICK(4, 1) NOCF_MBW_ENS_PICK(8, 2) NOCF_MBW_ENS_PICK(6, 2) NOCF_MBW_ENS_PICK(4, 2)
 #undef NOCF_MBW_ENS_PICK
@@ -3206,7 +3310,8 @@ static int bwd_mid_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, int64
     e = hipLaunchKernel(fk, dim3((unsigned)((long)members * rows)), dim3(256), args, ldsBytes, st);
     if (e) return (int)e;
     if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
-    g_last_kernel = weighted ? "rollout_mono_bwd_kernel<ens,weighted>" : "rollout_mono_bwd_kernel<ens>";
+    g_last_kernel = mode == 2 ? "rollout_mono_bwd_kernel<ens,joint>" : mode == 1 ? "rollout_mono_bwd_kernel<ens,states>" :
+                    (weighted ? "rollout_mono_bwd_kernel<ens,weighted>" : "rollout_mono_bwd_kernel<ens>");
     g_last_errp = nullptr;
     return (int)hipGetLastError();
 #endif
@@ -3226,6 +3331,22 @@ int nocf_rollout_bwd_mid_ensemble_rw_f32(const NocfPhi* phi, const NocfProb* pro
                                          void* workspace, size_t workspace_bytes, void* stream) {
     return bwd_mid_ensemble_impl(phi, prob, n, members, nt, stepper, t1, alph, 0.0, wrow, true, s_all, z_final, hs, act_rec, gpart,
                                  gpart_rows, lam0, workspace, workspace_bytes, stream);
+}
+
+int nocf_rollout_bwd_mid_ensemble_w_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper,
+                                        double t1, const float* alph, double inv_n, const float* s_all, const float* z_final, const float* hs,
+                                        const float* act_rec, float* gpart, int64_t gpart_rows, float* lam0, float* lamW,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+    return bwd_mid_ensemble_impl(phi, prob, n, members, nt, stepper, t1, alph, inv_n, nullptr, false, s_all, z_final, hs, act_rec, gpart,
+                                 gpart_rows, lam0, workspace, workspace_bytes, stream, lamW, lamW ? 2 : 0);
+}
+
+int nocf_rollout_bwd_mid_ensemble_states_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper,
+                                             double t1, const float* alph, double inv_n, const float* s_all, const float* z_final,
+                                             const float* hs, const float* act_rec, float* lam0, float* lamW,
+                                             void* workspace, size_t workspace_bytes, void* stream) {
+    return bwd_mid_ensemble_impl(phi, prob, n, members, nt, stepper, t1, alph, inv_n, nullptr, false, s_all, z_final, hs, act_rec, nullptr, 0,
+                                 lam0, workspace, workspace_bytes, stream, lamW, 1);
 }
 
 // ---- the state-only adjoint (include/nocf.h): lane, then one-CU, then per-tile -- nocf_rollout_record_disturbed_f32's order.  A family says
@@ -3255,6 +3376,15 @@ int nocf_disturbance_ascent_f32(float* W, const float* g, const float* mask, int
     if (n < 1 || nt < 1 || d < 1 || !(step >= 0.0 && step <= 3.0e38) || !(eps >= 0.0 && eps <= 3.0e38)) return NOCF_E_SHAPE;
     hipLaunchKernelGGL(disturbance_ascent_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, W, g, mask, (long)n, (int)nt,
                        (int)d, (float)step, (float)eps);
+    return (int)hipGetLastError();
+}
+
+int nocf_disturbance_ascent_ensemble_f32(float* W, const float* g, const float* mask, int64_t n, int32_t members, int32_t nt, int32_t d,
+                                         const float* steps, const float* epss, void* stream) {
+    if (!W || !g || !steps || !epss) return NOCF_E_NULL;
+    if (n < 1 || members < 1 || nt < 1 || d < 1 || (int64_t)members * n > 0x7fffffffl) return NOCF_E_SHAPE;
+    hipLaunchKernelGGL(disturbance_ascent_ens_kernel, dim3((unsigned)(((int64_t)members * n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, W, g, mask,
+                       (long)n, (int)members, (int)nt, (int)d, steps, epss);
     return (int)hipGetLastError();
 }
 

@@ -40,7 +40,7 @@ struct EnsArgs { unsigned n; long xs; const float* alph; };
 // recording forward of disturbed training): the next step's first stage input is formed from the displaced z, so it is recorded displaced
 // DIST == 2: the same with the entry drawn here (nocf_noise.inc: RollArgs::nzScale / nzSeed / nzRow0) where DIST == 1 loads it -- into the same
 // register, at the top of the step, so every instruction behind it is shared.  Tail waves draw the noise of the row they replicate
-// ENS: an ensemble of E networks of one shape in one launch (DIST = 0 or 2, ONE = false).  A wave is a whole sample and nothing in a workgroup is
+// ENS: an ensemble of E networks of one shape in one launch (every DIST, ONE = false).  A wave is a whole sample and nothing in a workgroup is
 // shared, so the only change is WHICH network, multipliers and start a wave reads: the member e = row / ensN is wave-uniform and is kept, with
 // the member's eight tensor pointers and its row of the multiplier table, in scalar registers; every statement of the rollout behind these
 // reads is the single-network one, so member e's rows carry the bits of the single-network call on that member.  Every ENS test is
@@ -49,9 +49,13 @@ struct EnsArgs { unsigned n; long xs; const float* alph; };
 // pointers: lane j < d reads scale[e * d + j], the seed is seeds[e], and the key of a row is RollArgs::nzRow0 + the row INSIDE the member --
 // members given one seed meet the same noise.  Behind these reads the DIST == 2 statements, so member e carries the bits of the single-network
 // noisy call
+// ENS with DIST == 1 (nocf_rollout_disturbed_ensemble_f32, DESIGN.md section 3.17; REC or not): every member under its own tensor disturbance,
+// RollArgs::dist = W [E, nt, n, d] member-major -- member e's slice is the [nt, n, d] of the single-network disturbed call -- or, with
+// EnsNoiseArgs::ws == 0, one [nt, n, d] for all members.  The member's slice begins e * ws floats behind the base (wave-uniform, like the
+// member's other pointers) and is indexed by the step and the row INSIDE the member; the load stands where the DIST == 1 load stands, at the
+// top of the step, and every statement behind it is the DIST == 1 one
 template <int MP, int DP, bool REC, bool ONE = false, int DIST = 0, bool ENS = false>
 __global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb pb, RollArgs ra, EnsArgs ea, EnsNoiseArgs nz) {
-    static_assert(!ENS || DIST != 1, "a disturbed ensemble draws its noise (DIST == 2): there is no tensor-W ensemble");
     const int lane = threadIdx.x & 63;
     const long sample = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const bool live = sample < ra.n;
@@ -63,6 +67,7 @@ __global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb 
     float eA0 = 0.f, eAQ = 0.f, eAW = 0.f;              // ENS: the member's alph[0], alph_Q, alph_W
     const float* nzScale = ra.nzScale;                  // DIST == 2: the noise scale [d] and seed of this wave's rows (ENS: the member's)
     unsigned long long nzSeed = ra.nzSeed;
+    const float* wmem = ra.dist;                        // ENS with DIST == 1: the member's slice [nt, ea.n, d] of the disturbance
     if constexpr (ENS) {
         const unsigned e = (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)row / ea.n));
         P.K0 += (long)e * m * D1; P.b0 += (long)e * m; P.K += (long)e * m * m; P.b += (long)e * m; P.w += (long)e * m;
@@ -71,6 +76,7 @@ __global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb 
         const float* at = ea.alph + (long)e * 6;
         eA0 = at[0]; eAQ = at[1]; eAW = at[2];
         if constexpr (DIST == 2) { nzScale = nz.scale + (long)e * d; nzSeed = nz.seeds[e]; }
+        if constexpr (DIST == 1) wmem += (long)e * nz.ws;
     }
     // the multipliers and the decisions they take: the problem's (one network), the member's (ENS) -- wave-uniform either way
     auto wantWp = [&]() -> bool { if constexpr (ENS) return eAW != 0.f; else return want_W(pb); };
@@ -210,6 +216,7 @@ __global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb 
         const float hs = (float)hsd;
         float wk = 0.f;
         if constexpr (DIST == 2) wk = lane < d ? noise_value(nzs, nzSeed, ra.nzRow0 + (ENS ? xr : row), k, lane) : 0.f;
+        else if constexpr (DIST == 1 && ENS) wk = lane < d ? wmem[((long)k * ea.n + xr) * d + lane] : 0.f;
         else if constexpr (DIST == 1) wk = lane < d ? ra.dist[((long)k * ra.n + row) * d + lane] : 0.f;
         // training: the stage input s = [x, t] of every evaluation goes to sAll[(k*nstage + st)][sample][0..d] (one row per lane group)
         auto record = [&](int st, int nstage, float s) {

@@ -42,6 +42,12 @@ __device__ __forceinline__ float sgnf(float v) { return (v > 0.f) ? 1.f : (v < 0
 //
 // ENS && RW (STATES = 0; nocf_rollout_bwd_small_ensemble_rw_f32): both of the above and nothing more.  la.wrow is [E, ea.n] contiguous, which is
 // the row order of the E * ea.n batch, so row g reads la.wrow[g] through the same scalar read; la.inv_n is not read.
+//
+// ENS && STATES == 2 (nocf_rollout_bwd_small_ensemble_w_f32) and ENS && STATES == 1 (nocf_rollout_bwd_small_ensemble_states_f32), DESIGN.md
+// section 3.17: the ensemble adjoint with the lamW[k] store of the joint / state-only modes.  la.lamW is [E, nt, ea.n, d] MEMBER-major -- member
+// e's slice is the [nt, n, d] the single-network call writes, so W.grad of a disturbed ensemble needs no transposition.  A wave offsets the
+// pointer once to its member's slice and its row of step 0 (wave-uniform); the store stands where the single-network store stands.  Tail waves
+// write nothing.  RW with STATES != 0 stays refused (the static_assert below): a weighted adversarial ensemble is not built.
 template <int MP, int DP, int STATES = 0, bool ENS = false, bool RW = false>
 __global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, DevProb pb, EnsArgs ea) {
     static_assert(!RW || STATES == 0, "the weighted variants are parameter-and-lam0 adjoints");
@@ -52,12 +58,14 @@ __global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, D
     const int d = la.d, D1 = d + 1, m = la.m, N = la.nAg;
     DevPhi P = la.P;
     float eA0 = 0.f, eAQ = 0.f, eAW = 0.f, eA3 = 0.f, eA4 = 0.f, eA5 = 0.f;      // ENS: the member's row of the multiplier table
+    float* lamWe = la.lamW;                                         // ENS && STATES != 0: this wave's row of step 0 in the member's slice of lamW
     if constexpr (ENS) {
         const unsigned e = (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)row / ea.n));
         P.K0 += (long)e * m * D1; P.b0 += (long)e * m; P.K += (long)e * m * m; P.b += (long)e * m; P.w += (long)e * m;
         P.A += (long)e * la.r * D1; P.cw += (long)e * D1; P.cbp += e;
         const float* at = ea.alph + (long)e * 6;
         eA0 = at[0]; eAQ = at[1]; eAW = at[2]; eA3 = at[3]; eA4 = at[4]; eA5 = at[5];
+        if constexpr (STATES != 0) { if (lamWe) lamWe += (((long)e * la.nt) * ea.n + (row - (long)e * ea.n)) * d; }
     }
     // (below, `ENS ? member's : the call's` is a compile-time choice at the place of use: the other instantiations keep their statements)
     float wI = 0.f;                                                 // RW: this wave's sample weight (a tail wave reads the last row's and writes nothing)
@@ -113,7 +121,8 @@ __global__ void __launch_bounds__(256) rollout_lane_bwd_kernel(LaneBwdArgs la, D
         float wst = 1.f, cpl = 0.f;
         if (la.nstage != 1) { wst = (st == 0 || st == 3) ? c16 : c26; cpl = (st == 3) ? 0.f : (st == 2 ? 1.f : 0.5f); }
         if (!fin && st == la.nstage - 1) {
-            if constexpr (STATES != 0) { if (la.lamW && live && lane < d) la.lamW[((long)k * la.n + sample) * d + lane] = LAM; }
+            if constexpr (STATES != 0 && ENS) { if (lamWe && live && lane < d) lamWe[(long)k * ea.n * d + lane] = LAM; }
+            else if constexpr (STATES != 0) { if (la.lamW && live && lane < d) la.lamW[((long)k * la.n + sample) * d + lane] = LAM; }
             XS = 0.f; XP = 0.f;
         }
         float s;
@@ -316,6 +325,49 @@ __global__ void __launch_bounds__(256) disturbance_ascent_kernel(float* __restri
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= n) return;                                            // (wave-uniform: sum64 needs every lane of the wave)
+    const int L = nt * d;
+    float s = 0.f;
+    for (int e = lane; e < L; e += 64) {
+        const int k = e / d, i = e - k * d;
+        float v = g[((long)k * n + row) * d + i];
+        if (mask) v *= mask[i];
+        s = fmaf(v, v, s);
+    }
+    const float gn = sqrtf(sum64(s));
+    if (!(gn > 0.f) || !(gn <= 3.0e38f)) return;
+    const float sc = step / gn;
+    float q = 0.f;
+    for (int e = lane; e < L; e += 64) {
+        const int k = e / d, i = e - k * d;
+        const long o = ((long)k * n + row) * d + i;
+        float w = W[o];
+        const float mk = mask ? mask[i] : 1.f;
+        if (mk != 0.f) { w = fmaf(sc, mk * g[o], w); W[o] = w; }
+        q = fmaf(w, w, q);
+    }
+    const float wn = sqrtf(sum64(q));
+    if (!(wn > eps)) return;
+    const float f = eps / wn;
+    for (int e = lane; e < L; e += 64) {
+        const int k = e / d, i = e - k * d;
+        const long o = ((long)k * n + row) * d + i;
+        W[o] *= f;
+    }
+}
+
+// The same step for an ensemble (nocf_disturbance_ascent_ensemble_f32, DESIGN.md section 3.17): W / g are [E, nt, n, d] member-major, one
+// wavefront per row of the E * n batch.  The member of a row (wave-uniform) picks its step length and radius from the device tables steps [E]
+// and epss [E] and its slice of W / g; behind that the statements are disturbance_ascent_kernel's on the member's [nt, n, d] slice, so member
+// e's slice carries the bits of the single-network step on a copy of it with (steps[e], epss[e]).
+__global__ void __launch_bounds__(256) disturbance_ascent_ens_kernel(float* __restrict__ W, const float* __restrict__ g, const float* __restrict__ mask,
+                                                                     long n, int members, int nt, int d, const float* __restrict__ steps,
+                                                                     const float* __restrict__ epss) {
+    const int lane = threadIdx.x & 63;
+    const long grow = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (grow >= n * members) return;                                 // (wave-uniform: sum64 needs every lane of the wave)
+    const long e_ = grow / n, row = grow - e_ * n;
+    W += e_ * nt * n * d; g += e_ * nt * n * d;
+    const float step = steps[e_], eps = epss[e_];
     const int L = nt * d;
     float s = 0.f;
     for (int e = lane; e < L; e += 64) {

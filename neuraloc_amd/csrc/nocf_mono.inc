@@ -199,15 +199,18 @@ __device__ __forceinline__ void mono_sincos(float x, float& sn, float& cs) {
 // disturbed training): the state rows SB hold the displaced state when the next step's first stage input and activations are recorded
 // DIST == 2: the entries are drawn (nocf_noise.inc: RollArgs::nzScale / nzSeed / nzRow0) where DIST == 1 ADDS them, behind the last stage, into the
 // same variable: nothing is held across the step's evaluations (drawn at the top of the step like the loads, the (4, 2) instantiation lost a wave)
-// ENS (DIST = 0 or 2): an ensemble, see MonoEnsArgs.  ra.n is a member's row count; member e = blockIdx.x / en.tiles is workgroup-uniform, the
+// ENS (every DIST): an ensemble, see MonoEnsArgs.  ra.n is a member's row count; member e = blockIdx.x / en.tiles is workgroup-uniform, the
 // member's last tile replicates the member's row n - 1.  Every ENS test is a compile-time choice at its place of use.
 // ENS with DIST == 2 (nocf_rollout_noisy_mid_ensemble_f32, DESIGN 3.14): member e under its own noise level and seed, EnsNoiseArgs (nocf_noise.inc)
 // as a further last argument that no other instantiation reads.  row0 is the tile's first row INSIDE the member, so ra.nzRow0 + row0 + s_ is
 // already the key of a row; the kernel's copy of `ra` takes the member's scale row and seed, and both places that draw read them from there
+// ENS with DIST == 1 (nocf_rollout_disturbed_mid_ensemble_f32, DESIGN 3.17; REC or not): member e under its own tensor disturbance, ra.dist = W
+// [E, nt, n, d] member-major (EnsNoiseArgs::ws = nt n d) or one [nt, n, d] for all members (ws = 0).  The kernel's copy of ra.dist moves to the
+// member's slice once, with the member's other pointers (workgroup-uniform); ra.n and row0 are the member's, so the DIST == 1 load and add
+// below are the single-network statements on that slice
 template <int KBM, int KBD, bool REC, int DIST = 0, bool ENS = false>
 __global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __restrict__ mpp, DevProb pb, float* ws, RollArgs ra, MonoEnsArgs en,
                                                            EnsNoiseArgs nz) {
-    static_assert(!ENS || DIST != 1, "a disturbed ensemble draws its noise (DIST == 2): there is no tensor-W ensemble");
     constexpr int MT = (KBM + 3) / 4;              // hidden M-tiles per wave: tiles w, w+4, ...
     constexpr int T = 16;
     constexpr MonoFwdLds LL = mono_fwd_lds(KBM, KBD);
@@ -222,6 +225,7 @@ __global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __res
         ra.x += e * en.xs;
         if (ra.zFull) { ra.zFull += e * en.zfs; ra.ctrlFull += e * en.cfs; }
         if (REC) { if (ra.sAll) ra.sAll += e * en.sas; if (ra.act) ra.act += e * en.acts; }
+        if constexpr (DIST == 1) ra.dist += e * nz.ws;
     }
     MonoPlan mp = *mpp;                    // local copy; the LDS layout is a compile-time constant, the shape words sit in scalar registers
     mp.lSF = LL.lSF; mp.lUF = LL.lUF; mp.lVF = LL.lVF; mp.lK4 = LL.lK4; mp.lAT = LL.lAT; mp.lVO = LL.lVO; mp.lCW = LL.lCW; mp.lZP = LL.lZP;

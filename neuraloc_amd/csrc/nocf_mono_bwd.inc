@@ -151,11 +151,16 @@ __device__ __forceinline__ void mono_lowrank(const MonoPlan& mp, const f32x4& AZ
 //
 // ENS && RW (STATES = 0; nocf_rollout_bwd_mid_ensemble_rw_f32): BwdArgs::wrow is [E, en.n]; member e's workgroups move it to their member's
 // row where they move zT and lam0, and fill lINV from it as the RW instantiation does.  ba.inv_n is not read.
+//
+// ENS && STATES == 2 (nocf_rollout_bwd_mid_ensemble_w_f32) and ENS && STATES == 1 (nocf_rollout_bwd_mid_ensemble_states_f32), DESIGN 3.17: the
+// ensemble adjoint with the lamW[k] store of the joint / state-only modes.  BwdArgs::lamW is [E, nt, en.n, d] member-major; member e's
+// workgroups move it to their member's slice where they move zT and lam0 (workgroup-uniform), and ba.n / row0 are the member's, so the store is
+// the single-network statement on that slice: tail rows of a member's last tile write nothing.  STATES == 1 writes no partial vector (gpart is
+// not read).  RW with STATES != 0 stays refused.
 template <int KBM, int KBD, int STATES = 0, bool ENS = false, bool RW = false>
 __global__ void __launch_bounds__(256) rollout_mono_bwd_kernel(const MonoPlan* __restrict__ mpp, DevProb pb, const float* __restrict__ ws, BwdArgs ba,
                                                                MonoEnsArgs en) {
     static_assert(KBD == 1 || KBD == 2, "d + 1 <= 32: the (sample, entry) threads take KBD entries each; dM is KBD x KBD tiles on the four waves");
-    static_assert(!ENS || STATES == 0, "ensembles take the full adjoint");
     static_assert(!RW || STATES == 0, "the weighted variants are parameter-and-lam0 adjoints");
     constexpr int MT = (KBM + 3) / 4;
     constexpr int T = 16;
@@ -199,6 +204,7 @@ __global__ void __launch_bounds__(256) rollout_mono_bwd_kernel(const MonoPlan* _
         ba.zT += eo * (d + 4);
         if (ba.lam0) ba.lam0 += eo * d;
         if constexpr (RW) ba.wrow += eo;
+        if constexpr (STATES != 0) { if (ba.lamW) ba.lamW += eo * ba.nt * d; }      // lamW [E, nt, n, d]: the member's slice
     }
 
     // ---- resident weights (as the forward kernel's)

@@ -44,7 +44,10 @@ __device__ __forceinline__ float noise_value(float scale, unsigned long long see
 // level and seed -- scale [E, d] (member e's fp32 sigma_i sqrt(h)) and seeds [E], device tables.  The LAST argument of the lane and the one-CU
 // rollout kernels, behind EnsArgs / MonoEnsArgs and for their reason (the offsets of the arguments in front of it stay where they are), and
 // read by the ENS instantiations with DIST == 2 alone.  The key of a row is RollArgs::nzRow0 + the row INSIDE its member
-struct EnsNoiseArgs { const float* scale; const unsigned long long* seeds; };
+// ws (the struct's last word, so nothing in front of it moves): read by the ENS instantiations with DIST == 1 alone
+// (nocf_rollout_disturbed_ensemble_f32 / nocf_rollout_disturbed_mid_ensemble_f32, DESIGN.md section 3.17) -- the member stride of the tensor
+// disturbance RollArgs::dist in floats, nt n d for W [E, nt, n, d] or 0 for one [nt, n, d] that every member meets
+struct EnsNoiseArgs { const float* scale; const unsigned long long* seeds; long ws; };
 
 // W[k][row][i] = noise_value(scale[i], seed, row0 + row, k, i): one thread per element, rows < n and d floats per row only
 __global__ void __launch_bounds__(256) noise_fill_kernel(float* __restrict__ W, long n, int nt, int d, const float* __restrict__ scale,

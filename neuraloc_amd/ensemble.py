@@ -354,11 +354,15 @@ def _refuse(fn, x, ens, prob, nt, stepper, train, noMean=False, W=None, family="
     return E, int(n), int(d), own
 
 
-def _launch(x, ens, prob, tspan, nt, stepper, alph=None, intermediates=False, record=False, bufs=None, noise=None):
+def _launch(x, ens, prob, tspan, nt, stepper, alph=None, intermediates=False, record=False, bufs=None, noise=None, dist=None):
     """one ensemble launch (nocf_rollout_ensemble_f32, or nocf_rollout_record_ensemble_f32 with record) -> dict of its buffers: persample
     [E*n, 7], z_out [E*n, d+4], sums [E, 8], means [E, 8] (evaluation), zFull / ctrlFull (time-major over E*n rows, intermediates), s_all
     [nt*nstage, E*n, d+1] (record).  bufs: buffers to write into instead of fresh ones (same keys).  noise: an ensemble_noise._Noise -- the
-    launch is the noisy sibling's (nocf_rollout_noisy_ensemble_f32 / nocf_rollout_record_noisy_ensemble_f32), same buffers"""
+    launch is the noisy sibling's (nocf_rollout_noisy_ensemble_f32 / nocf_rollout_record_noisy_ensemble_f32), same buffers.  dist: an
+    ensemble_minmax._Disturbance -- the launch is the disturbed sibling's (nocf_rollout_disturbed_ensemble_f32 /
+    nocf_rollout_record_disturbed_ensemble_f32) under its tensor W, same buffers; it speaks noise's protocol (entries, args)"""
+    if dist is not None:
+        noise = dist
     E = ens.members
     own = x.dim() == 3
     n, d = x.shape[-2], x.shape[-1]
@@ -414,12 +418,15 @@ def _act_stride(L, ens, n, nt, stepper):
     return (int(L.nocf_activation_record_floats(ens.d, ens.m, ens.nTh, int(n), int(nt), _STEPPERS[stepper])) + 3) // 4 * 4
 
 
-def _launch_mid(x, ens, prob, tspan, nt, stepper, alph=None, intermediates=False, record=False, bufs=None, noise=None):
+def _launch_mid(x, ens, prob, tspan, nt, stepper, alph=None, intermediates=False, record=False, bufs=None, noise=None, dist=None):
     """one launch of the one-CU family (nocf_rollout_mid_ensemble_f32, or nocf_rollout_record_mid_ensemble_f32 with record) -> dict of its
     buffers, all MEMBER-MAJOR: persample [E, n, 7], z_out [E, n, d+4], sums [E, 8], means [E, 8] (evaluation), zFull [E, nt+1, n, d+4] /
     ctrlFull [E, nt+1, n, a] (intermediates), s_all [E, nt*nstage, n, d+1] and act [E, stride] or None (record; "recorded": the kernel wrote
     it).  bufs: buffers to write into instead of fresh ones (same keys).  noise: as for _launch (nocf_rollout_noisy_mid_ensemble_f32 /
-    nocf_rollout_record_noisy_mid_ensemble_f32)"""
+    nocf_rollout_record_noisy_mid_ensemble_f32).  dist: as for _launch (nocf_rollout_disturbed_mid_ensemble_f32 /
+    nocf_rollout_record_disturbed_mid_ensemble_f32)"""
+    if dist is not None:
+        noise = dist
     E = ens.members
     own = x.dim() == 3
     n, d = x.shape[-2], x.shape[-1]
@@ -522,10 +529,11 @@ class _EnsembleTrain(torch.autograd.Function):
         return _EnsembleTrain._forward(ctx, x, ens, prob, tspan, nt, stepper, alph)
 
     @staticmethod
-    def _forward(ctx, x, ens, prob, tspan, nt, stepper, alph, noise=None):
-        """(noise: the recording forward draws its disturbances, ensemble_noise.py; everything saved is what the undisturbed forward saves)"""
+    def _forward(ctx, x, ens, prob, tspan, nt, stepper, alph, noise=None, dist=None):
+        """(noise: the recording forward draws its disturbances, ensemble_noise.py; dist: it runs under a tensor disturbance,
+        ensemble_minmax.py; everything saved is what the undisturbed forward saves)"""
         ctx.x_needs_grad = bool(x.requires_grad)
-        b = _launch(x, ens, prob, tspan, nt, stepper, alph, record=True, noise=noise)
+        b = _launch(x, ens, prob, tspan, nt, stepper, alph, record=True, noise=noise, dist=dist)
         ctx.ens, ctx.prob, ctx.tspan, ctx.nt, ctx.stepper, ctx.table = ens, prob, tspan, nt, stepper, b["table"]
         ctx.persample = b["persample"]                      # (the weighted calls form their sums and risks from it: ensemble_risk.py)
         ctx.save_for_backward(b["s_all"], b["z_out"])
@@ -544,8 +552,10 @@ class _EnsembleTrain(torch.autograd.Function):
         return _EnsembleTrain._adjoint(ctx, gJ)
 
     @staticmethod
-    def _adjoint(ctx, gJ, wrow=None):
-        """wrow: [E, n] float32 weights (ensemble_risk.py) -- the launch is the weighted entry's, wrow standing where 1 / n stands"""
+    def _adjoint(ctx, gJ, wrow=None, joint=None):
+        """wrow: [E, n] float32 weights (ensemble_risk.py) -- the launch is the weighted entry's, wrow standing where 1 / n stands.
+        joint: (entry, its name, lamW [E, nt, n, d]) (ensemble_minmax.py) -- the launch is the joint entry's, which takes lamW behind lam0 and
+        fills it with every member's dJ/dW; what is returned does not change"""
         s_all, z_out = ctx.saved_tensors
         ens, prob, nt = ctx.ens, ctx.prob, ctx.nt
         if [p._version for _, p in ens._params()] != ctx.param_versions:
@@ -559,6 +569,9 @@ class _EnsembleTrain(torch.autograd.Function):
         what = "nocf_rollout_bwd_small_ensemble_f32"
         if wrow is not None:
             f_bwd, what = weighted_entry(L, "lane"), _ARGTYPES_RW["lane"][0]
+        lamW = ()
+        if joint is not None:
+            f_bwd, what, lamW = joint[0], joint[1], (_lib.ptr(joint[2]),)
         phi_st, keep1 = ens._c_struct()
         prob_st, keep2 = prob._c_struct(dev)
         hs = _step_sizes(ctx.tspan, nt).to(dev)
@@ -568,7 +581,7 @@ class _EnsembleTrain(torch.autograd.Function):
         with torch.cuda.device(dev):
             rc = f_bwd(C.byref(phi_st), C.byref(prob_st), n, E, int(nt), _STEPPERS[ctx.stepper], float(ctx.tspan[1]),
                        _lib.ptr(ctx.table), 1.0 / float(n) if wrow is None else _lib.ptr(wrow), _lib.ptr(s_all), _lib.ptr(z_out), _lib.ptr(hs),
-                       _lib.ptr(gpart), _lib.ptr(lam0), _lib.stream_ptr(dev))
+                       _lib.ptr(gpart), _lib.ptr(lam0), *lamW, _lib.stream_ptr(dev))
         _lib.check(rc, what)
         # per member the sum and the products of the single-network adjoint (train._unpack_partials on the member's contiguous [n, P] slice:
         # the same calls on the same shapes, so the same bits); only the exact elementwise scaling by gJ runs on the stacked tensors
@@ -591,9 +604,9 @@ class _EnsembleTrainMid(torch.autograd.Function):
         return _EnsembleTrainMid._forward(ctx, x, ens, prob, tspan, nt, stepper, alph)
 
     @staticmethod
-    def _forward(ctx, x, ens, prob, tspan, nt, stepper, alph, noise=None):
+    def _forward(ctx, x, ens, prob, tspan, nt, stepper, alph, noise=None, dist=None):
         ctx.x_needs_grad = bool(x.requires_grad)
-        b = _launch_mid(x, ens, prob, tspan, nt, stepper, alph, record=True, noise=noise)
+        b = _launch_mid(x, ens, prob, tspan, nt, stepper, alph, record=True, noise=noise, dist=dist)
         ctx.ens, ctx.prob, ctx.tspan, ctx.nt, ctx.stepper, ctx.table = ens, prob, tspan, nt, stepper, b["table"]
         ctx.act = b["act"]
         ctx.persample = b["persample"]
@@ -612,8 +625,8 @@ class _EnsembleTrainMid(torch.autograd.Function):
         return _EnsembleTrainMid._adjoint(ctx, gJ)
 
     @staticmethod
-    def _adjoint(ctx, gJ, wrow=None):
-        """wrow: as for _EnsembleTrain._adjoint"""
+    def _adjoint(ctx, gJ, wrow=None, joint=None):
+        """wrow, joint: as for _EnsembleTrain._adjoint"""
         s_all, z_out = ctx.saved_tensors
         ens, prob, nt = ctx.ens, ctx.prob, ctx.nt
         if [p._version for _, p in ens._params()] != ctx.param_versions:
@@ -627,6 +640,9 @@ class _EnsembleTrainMid(torch.autograd.Function):
         what = "nocf_rollout_bwd_mid_ensemble_f32"
         if wrow is not None:
             f_bwd, what = weighted_entry(L, "mid"), _ARGTYPES_RW["mid"][0]
+        lamW = ()
+        if joint is not None:
+            f_bwd, what, lamW = joint[0], joint[1], (_lib.ptr(joint[2]),)
         phi_st, keep1 = ens._c_struct()
         prob_st, keep2 = prob._c_struct(dev)
         ws = ens.mid_workspace(L, dev)
@@ -640,7 +656,7 @@ class _EnsembleTrainMid(torch.autograd.Function):
         with torch.cuda.device(dev):
             rc = f_bwd(C.byref(phi_st), C.byref(prob_st), n, E, int(nt), _STEPPERS[ctx.stepper], float(ctx.tspan[1]),
                        _lib.ptr(ctx.table), 1.0 / float(n) if wrow is None else _lib.ptr(wrow), _lib.ptr(s_all), _lib.ptr(z_out), _lib.ptr(hs),
-                       _lib.ptr(ctx.act), _lib.ptr(gpart), rows, _lib.ptr(lam0), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+                       _lib.ptr(ctx.act), _lib.ptr(gpart), rows, _lib.ptr(lam0), *lamW, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
         _lib.check(rc, what)
         ctx.act = None
         # per member the sum and the products of the single-network adjoint: train._unpack_partials on the member's contiguous [rows, P] block

@@ -46,7 +46,14 @@ and averaged.  Single precision, one rank; not with --members or --adv.
 training batch is repeated R times (default 8) for every member, member e's objective is the risk of each start's R costs at ITS level -- one
 level per member, or one for all -- and all members' exact gradients come from ONE weighted ensemble adjoint launch.  The seed is
 noise_seed << 32 | iteration for all members; the loss column carries each member's risk value; validation stays undisturbed and averaged;
-one checkpoint per member as with --members.  --risk with --members stays refused: this flag is the way in."""
+one checkpoint per member as with --members.  --risk with --members stays refused: this flag is the way in.
+--members_adv EPS0,EPS1,... [--adv_steps K] (addition, with --members): E adversary budgets >= 0, one per member -- a sweep over the budget in
+one process (neuraloc_amd.ensemble_adversarial_step).  Free-mode min-max training: one W [E, nt, n, d] persists across
+the iterations on a batch -- zero at the start and whenever the batch is resampled -- and per Adam step member e's slice takes one projected
+ascent step of length 2.5 EPS_e / K inside its ball ||W_i||_2 <= EPS_e, from the same joint ensemble adjoint launch that gives all members'
+parameter gradients: three launches per iteration for all members, on either family.  A budget of 0 is the undisturbed member; validation stays
+undisturbed; one log line and one checkpoint per member as with --members.  Not with --members_sigma, --members_risk, --noise or --adv:
+--members with --adv stays refused, this flag is the way in."""
 import argparse
 import datetime
 import os
@@ -112,6 +119,8 @@ _FLAGS = [
                                       "0 <= A < 1; entropic: theta > 0)"),
     ("members_risk_paths", int, 8, "(addition, with --members_risk) R >= 1 noise paths per start: every batch is repeated R times per member"),
     ("members_risk_mix", float, 1.0, "(addition, with --members_risk) 0 <= M <= 1: every member's objective is (1 - M) mean + M risk"),
+    ("members_adv", str, None, "(addition, with --members) EPS0,EPS1,...: E adversary budgets >= 0, member e trains against the worst "
+                               "disturbance path of norm <= EPS_e per start (neuraloc_amd.ensemble_adversarial_step, free mode; --adv_steps K)"),
     ("risk", str, None, "(addition, with --noise SIGMA --noise_rng counter) cvar or entropic: train on a risk measure of each start's costs over "
                         "--risk_paths noise paths (neuraloc_amd.risk_ocflow_train) instead of their mean"),
     ("risk_level", float, None, "(addition, with --risk) cvar: the level 0 <= A < 1 (the mean of the worst (1 - A) share); entropic: theta > 0"),
@@ -266,10 +275,35 @@ def members_risk_spec(args, sigmas):
     return args.members_risk, levels, args.members_risk_paths, args.members_risk_mix
 
 
-def train_members(args, rows, sigmas=None, mrisk=None):
+def members_adv_budgets(args, sigmas, mrisk):
+    """--members_adv: the members' adversary budgets, refused before anything runs or is written.  -> E floats, or None without the flag"""
+    if args.members_adv is None:
+        return None
+    if args.members is None or args.members < 1:
+        raise SystemExit("--members_adv needs --members E: one adversary budget per member")
+    try:
+        budgets = [float(v) for v in args.members_adv.split(",")]
+    except ValueError:
+        raise SystemExit("--members_adv EPS0,EPS1,...: a comma-separated list of numbers, got {!r}".format(args.members_adv))
+    if len(budgets) != args.members:
+        raise SystemExit("--members_adv needs one budget per member: --members {:} but {:} values".format(args.members, len(budgets)))
+    if not all(v >= 0.0 and v != float("inf") for v in budgets):
+        raise SystemExit("--members_adv: every budget must be a finite number >= 0")
+    if sigmas is not None or mrisk is not None:
+        raise SystemExit("--members_adv excludes --members_sigma and --members_risk: one disturbance per rollout, and dJ/dW together with "
+                         "weights is not supported")
+    if args.noise > 0 or args.adv > 0:
+        raise SystemExit("--members_adv excludes --noise and --adv: the members' budgets are the disturbance of the run")
+    if args.adv_steps < 1:
+        raise SystemExit("--adv_steps K must be >= 1")
+    return budgets
+
+
+def train_members(args, rows, sigmas=None, mrisk=None, budgets=None):
     """the training loop of main() for E networks at once (neuraloc_amd.ensemble): same schedule, one log line and one checkpoint per member.
     sigmas (--members_sigma): member e's training rollouts run under Brownian disturbances of level sigmas[e].  mrisk (--members_risk, with
-    sigmas): (risk, E levels, paths, mix) -- member e trains on that risk of each start's `paths` costs at its level"""
+    sigmas): (risk, E levels, paths, mix) -- member e trains on that risk of each start's `paths` costs at its level.  budgets (--members_adv):
+    member e trains against the worst disturbance of norm <= budgets[e] per start, free mode"""
     E = args.members
     dev = torch.device("cuda", args.gpu)
     assert torch.cuda.is_available(), "trainOC.py needs an MI355X: there is no CPU path"
@@ -304,6 +338,8 @@ def train_members(args, rows, sigmas=None, mrisk=None):
         "valLoss", "valL", "valG", "valHJt", "valHJf", "valHJg", "valQ", "valW"))
     n_change = int(args.new_alph[0]) if args.new_alph is not None else -1
     best_loss, total = [float("inf")] * E, 0.0
+    # --members_adv: one W for all members, kept across the iterations on a batch (zeroed with every new batch)
+    adv_W = torch.zeros(E, args.nt, x0.shape[0], d, device=dev, requires_grad=True) if budgets is not None else None
     prob.train()
     end = time.time()
     for itr in range(1, args.niters + 1):
@@ -312,12 +348,16 @@ def train_members(args, rows, sigmas=None, mrisk=None):
             Jc, cs, _ = na.ensemble_risk_ocflow_train(x0.repeat_interleave(mrisk[2], 0), ens, prob, tspan, args.nt, mrisk[0], mrisk[1],
                                                       paths=mrisk[2], mix=mrisk[3], sigma=[[s_] for s_ in sigmas],
                                                       seed=(args.noise_seed << 32) | itr, stepper="rk4", family=args.members_family)
+        elif adv_W is not None:                           # forward, joint adjoint (both gradients) and the members' ascent steps: three launches
+            Jc, cs = na.ensemble_adversarial_step(x0, ens, prob, tspan, args.nt, adv_W, budgets, [2.5 * b_ / args.adv_steps for b_ in budgets],
+                                                  stepper="rk4", family=args.members_family)
         elif sigmas is not None:                          # one seed for all members: the same noise realisations at E levels
             Jc, cs = na.ensemble_noisy_ocflow_train(x0, ens, prob, tspan, args.nt, [[s_] for s_ in sigmas], (args.noise_seed << 32) | itr,
                                                     "rk4", family=args.members_family)
         else:
             Jc, cs = na.ensemble_ocflow_train(x0, ens, prob, tspan, args.nt, "rk4", family=args.members_family)
-        Jc.sum().backward()                               # (upstream gradient 1 for every member: E independent gradients)
+        if adv_W is None:                                 # (upstream gradient 1 for every member: E independent gradients)
+            Jc.sum().backward()
         torch.cuda.synchronize()
         optim.step()
         dt = time.time() - end
@@ -348,6 +388,9 @@ def train_members(args, rows, sigmas=None, mrisk=None):
                 g["lr"] *= args.lr_decay
         if itr % args.sample_freq == 0:
             x0 = resample(x0, xInit, args.var0, cvt)
+            if adv_W is not None:
+                with torch.no_grad():
+                    adv_W.zero_()
         if itr == n_change:
             rows = [[r_[0]] + list(args.new_alph[2:4]) + list(r_[3:]) for r_ in rows]       # like main(): the Q / W weights change, the others stay
             ens.alph = [list(r_) for r_ in rows]
@@ -382,10 +425,11 @@ def main(argv=None):
     rank = int(os.environ.get("RANK", "0"))
     risk_refusals(args, world)
     if args.members is not None or args.members_alph is not None or args.members_family != "lane" or args.members_sigma is not None \
-            or args.members_risk is not None or args.members_risk_level is not None:
+            or args.members_risk is not None or args.members_risk_level is not None or args.members_adv is not None:
         sigmas = members_sigma_levels(args)
         mrisk = members_risk_spec(args, sigmas)
-        return train_members(args, members_refusals(args, world), sigmas, mrisk)
+        budgets = members_adv_budgets(args, sigmas, mrisk)
+        return train_members(args, members_refusals(args, world), sigmas, mrisk, budgets)
     if world > 1:
         import torch.distributed as dist
         local = int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count())
