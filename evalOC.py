@@ -13,6 +13,8 @@ line, appended to `<save>/deploy_times`) plus a batch, and with --do_shock runs 
 Differences, on purpose: --make_vid only states that videos are out of scope; --gpu/--batch are additions, and so is
 --noise SIGMA [--noise_paths R --noise_seed S]: the distribution of the costs over R rollouts of xInit under per-step Brownian
 disturbances (neuraloc_amd.disturb; single precision), one line per quantity and `<save>/figs/eval_<name>_noise.npz`;
+--noise_rho RHO (with --noise): those disturbances correlated in time, an Ornstein-Uhlenbeck path of lag-one correlation 0 < RHO < 1
+(neuraloc_amd.noise_study(..., rho=RHO), DESIGN.md section 3.18; the default 0 is the white noise);
 --worst EPS [--worst_steps K]: the disturbance path of energy ||W||_2 <= EPS that hurts the control objective L + alph0 G of xInit most
 (neuraloc_amd.worst_case_disturbances, K projected ascent steps; single precision), one line per quantity, nominal against worst case,
 and `<save>/figs/eval_<name>_worst.npz`."""
@@ -45,13 +47,29 @@ p.add_argument("--noise_seed", type=int, default=0, metavar="S", help="(addition
 p.add_argument("--noise_rng", type=str, default="torch", choices=["torch", "counter"],
                help="(addition) torch: the disturbances are drawn with torch.randn; counter: inside the kernels from (seed, row, step, "
                     "component) (neuraloc_amd.noisy_rollout): no tensor, and the figures do not depend on the chunking")
+p.add_argument("--noise_rho", type=float, default=0.0, metavar="RHO",
+               help="(addition, with --noise) 0 <= RHO < 1: time-correlated (Ornstein-Uhlenbeck) disturbances of lag-one correlation RHO, on either "
+                    "--noise_rng (neuraloc_amd.noise_study with rho=RHO); 0: the white noise of --noise")
 p.add_argument("--worst", type=float, default=None, metavar="EPS",
                help="(addition) search the per-step state disturbances of path norm <= EPS that hurt xInit's L + G most (neuraloc_amd.worst_case_disturbances)")
 p.add_argument("--worst_steps", type=int, default=20, metavar="K", help="(addition) projected ascent steps for --worst")
 
 
+def noise_rho_refusals(args):
+    """--noise_rho: what the time-correlated noise does not take, refused before anything runs or is written"""
+    if args.noise_rho == 0:
+        return
+    if not 0.0 <= args.noise_rho < 1.0:                    # (a NaN fails both comparisons)
+        raise SystemExit("--noise_rho RHO must be a number with 0 <= RHO < 1")
+    if args.noise is None:
+        raise SystemExit("--noise_rho needs --noise SIGMA: it shapes that noise in time")
+    if args.prec == "double":
+        raise SystemExit("--noise_rho runs in single precision only (the double-precision rollout takes no disturbance)")
+
+
 def main(argv=None):
     args = p.parse_args(argv)
+    noise_rho_refusals(args)
     args.alph = [float(item) for item in args.alph.split(",")]
     prec = torch.float64 if args.prec == "double" else torch.float32          # evalOC.py:28-31
     if args.noise is not None and prec != torch.float32:                     # refused before anything runs or is written
@@ -124,11 +142,12 @@ def main(argv=None):
                 print("%s at t=0.1: nShock=%d, final state error %.4e" %
                       (tag, res["nShock"], float((res["traj"][0, :, -1] - prob.xtarget.reshape(-1)).norm())))
         if args.noise is not None:
+            rho_kw = {"rho": args.noise_rho} if args.noise_rho != 0 else {}         # (0: the white path and its entry points)
             if args.noise_rng == "counter":
-                st = na.noise_study(xInit, net, prob, nt, args.noise, args.noise_paths, alph=alph, rng="counter", seed=args.noise_seed)
+                st = na.noise_study(xInit, net, prob, nt, args.noise, args.noise_paths, alph=alph, rng="counter", seed=args.noise_seed, **rho_kw)
             else:
                 gen = torch.Generator(device=xInit.device).manual_seed(args.noise_seed)
-                st = na.noise_study(xInit, net, prob, nt, args.noise, args.noise_paths, alph=alph, generator=gen)
+                st = na.noise_study(xInit, net, prob, nt, args.noise, args.noise_paths, alph=alph, generator=gen, **rho_kw)
             print("noise sigma=%g, %d paths, seed %d: %-4s %11s %11s %11s %11s %11s" %
                   (args.noise, args.noise_paths, args.noise_seed, "", "mean", "std", "5%", "50%", "95%"))
             keys = ("mean", "std", "q05", "q50", "q95")

@@ -257,6 +257,41 @@ int nocf_rollout_record_noisy_f32(const NocfPhi* phi, const NocfProb* prob, cons
                                   float* z_out, float* persample, float* cost_sums, float* s_all, float* act_rec, int32_t* recorded,
                                   void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * Time-correlated (AR(1) / Ornstein-Uhlenbeck) disturbances from the same generator.  With w(scale, seed, row, k, i) the white entry above,
+ * component i of GLOBAL row `row` meets the path
+ *     w_0 = w(scale0[i], seed, row, 0, i)
+ *     w_k = fl32( fl32(rho[i] * w_{k-1}) + w(scale1[i], seed, row, k, i) )        k >= 1
+ * -- two roundings, never an fma, fenced like the white product, so float32 arithmetic on the host restates it bit for bit.  Three device
+ * tables [d], float32: rho[i] in [0, 1); scale0[i] = sigma_i sqrt(h); scale1[i] = sigma_i sqrt(h) sqrt(1 - rho_i^2) (formed in double, then
+ * rounded; both 0 for a component that is not disturbed).  Then every w_k has the white entry's variance (a stationary start) and
+ * corr(w_k, w_{k+j}) = rho_i^j; rho == 0 gives the white values (0 * w + v = v).  Row keys, row0 and the prefix property are the white
+ * generator's: a row meets the same path alone, in any batch, on any device and in any chunk.  The carried w_{k-1} never leaves the kernel.
+ * The values of rho are not checked here (the Python layer refuses rho outside [0, 1)); any finite table gives a defined path.
+ *
+ * nocf_noise_fill_corr_f32: nocf_noise_fill_f32 for the path, W[k][row][i] = w_k of (row0 + row, i).
+ * nocf_rollout_noisy_corr_f32 / nocf_rollout_record_noisy_corr_f32: nocf_rollout_noisy_f32 / nocf_rollout_record_noisy_f32 with
+ * (scale0, scale1, rho) where `scale` stands; every output equals, bit for bit, that of nocf_rollout_disturbed_f32 /
+ * nocf_rollout_record_disturbed_f32 on the W that nocf_noise_fill_corr_f32 writes, and the recording forward goes to the same adjoints (W does
+ * not depend on the parameters).  Same contract, dispatch (lane, one-CU, per-tile; never the split-role kernel) and refusals as the white
+ * entries; a NULL table: NOCF_E_NULL.  On the per-tile kernel the carried values take T (d + 4) floats of LDS behind the plan's; a shape whose
+ * plan leaves no room for them: NOCF_E_LDS.  Every refusal returns before anything is enqueued.  nocf_last_rollout_kernel() reports
+ * "rollout_lane_kernel<noise-corr>", "rollout_mono_kernel<noise-corr>", "rollout_kernel<generic, noise-corr>" or
+ * "rollout_kernel<shape-specialised, noise-corr>".  Single networks only; nocf_version() is unchanged: callers probe for the symbols.
+ */
+int nocf_noise_fill_corr_f32(float* W, int64_t n, int32_t nt, int32_t d, const float* scale0, const float* scale1, const float* rho,
+                             uint64_t seed, int64_t row0, void* stream);
+int nocf_rollout_noisy_corr_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, const float* scale0, const float* scale1,
+                                const float* rho, uint64_t seed, int64_t row0,
+                                int64_t n, double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                float* z_out, float* persample, float* cost_sums, float* cost_means, float* zFull, float* ctrlFull,
+                                void* workspace, size_t workspace_bytes, void* stream);
+int nocf_rollout_record_noisy_corr_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, const float* scale0, const float* scale1,
+                                       const float* rho, uint64_t seed, int64_t row0,
+                                       int64_t n, double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                       float* z_out, float* persample, float* cost_sums, float* s_all, float* act_rec, int32_t* recorded,
+                                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* host only: the four Philox words of (seed, row, k, i) as the kernels form them (no device is touched).  out == NULL: NOCF_E_NULL;
  * row, k or i < 0: NOCF_E_SHAPE. */
 int nocf_debug_noise_words(uint64_t seed, int64_t row, int32_t k, int32_t i, uint32_t out[4]);

@@ -12,7 +12,7 @@ from .baseline_quad import quad_baseline_loss, quad_baseline_report, quad_initia
 from .disturb import disturbed_rollout, brownian_disturbances, noise_study
 from .train import disturbed_ocflow_train
 from .adversary import disturbance_gradient, worst_case_disturbances
-from .noise import counter_disturbances, noisy_rollout, noisy_ocflow_train
+from .noise import counter_disturbances, noisy_rollout, noisy_ocflow_train, noise_corr_scales
 from .minmax import minmax_ocflow_train, ascend_disturbances, adversarial_step, pgd_ocflow_train
 from .ensemble import PhiEnsemble, ensemble_rollout, ensemble_ocflow_train
 from .ensemble_noise import ensemble_noisy_rollout, ensemble_noisy_ocflow_train, ensemble_noise_study

@@ -171,4 +171,8 @@ struct RollArgs {
     // the same disturbances drawn inside the kernels (include/nocf.h, nocf_rollout_noisy_f32; nocf_noise.inc): entry (k, row, i) is
     // noise_value(nzScale[i], nzSeed, nzRow0 + row, k, i).  Read only by the DIST == 2 instantiations; dist is null there.
     const float* nzScale; unsigned long long nzSeed; long nzRow0;
+    // time-correlated noise (include/nocf.h, nocf_rollout_noisy_corr_f32; nocf_noise.inc): device tables [d], the scale s1 of steps k >= 1 and
+    // rho; nzScale is then s0, the scale of step 0.  Read only by the DIST == 3 instantiations; the struct's last words, so nothing in front
+    // of them moves.
+    const float* nzScale1; const float* nzRho;
 };

@@ -986,7 +986,19 @@ __device__ __forceinline__ void rollout_body(const DevPlan& pl, const DevPlan* _
     // disturbance of item j of step k's write-back sweep: point agents sweep the T*d state components (the tile's rows of W[k] are one
     // contiguous run), quadcopters the T*(d+4) components of z
     // DIST == 2: the entry is drawn here (nocf_noise.inc) instead of loaded -- in the sweep for the same reason, the generator's registers die with it
+    // DIST == 3 (time-correlated noise, nocf_noise.inc): item j of the sweep is the same thread's and the same (t, i) in every step, and its
+    // w_{k-1} waits in LDS slot j BEHIND the plan's carve (the launch asks for T (d + 4) floats more) -- not in registers, for the reason
+    // given above.  Only the owner ever touches a slot, so it needs no barrier; step 0 writes it before anything reads it
     auto dist_at = [&](int k, int j) -> float {
+        if constexpr (DIST == 3) {
+            const int dd = quad ? d + 4 : d;
+            const int t = j / dd, i = j - t * dd;
+            if (!(j < T * dd && i < d && row0 + t < ra.n)) return 0.f;
+            float* slot = lds + pl.ldsFloats + j;
+            const float w = noise_corr_value(ra.nzScale[i], ra.nzScale1[i], ra.nzRho[i], k == 0 ? 0.f : *slot, ra.nzSeed, ra.nzRow0 + row0 + t, k, i);
+            *slot = w;
+            return w;
+        }
         if constexpr (DIST == 2) {
             const int dd = quad ? d + 4 : d;
             const int t = j / dd, i = j - t * dd;
@@ -2197,7 +2209,8 @@ static unsigned* lane_ticket(hipStream_t st) {
     return b + it->second;
 }
 
-struct NoiseSpec { const float* scale; unsigned long long seed; long long row0; };       // nocf_rollout_noisy_f32: mode 2 of rollout_impl
+// nocf_rollout_noisy_f32: mode 2 of rollout_impl; with scale1 and rho (nocf_rollout_noisy_corr_f32) mode 3, and `scale` is then s0
+struct NoiseSpec { const float* scale; unsigned long long seed; long long row0; const float* scale1 = nullptr; const float* rho = nullptr; };
 
 static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n,
                         double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
@@ -2206,9 +2219,9 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
                         float* act = nullptr, int32_t* act_recorded = nullptr, float* tapeU1 = nullptr, float* tapeSc = nullptr,
                         const SegTab* seg = nullptr, float* cost_means = nullptr, const float* distW = nullptr, const NoiseSpec* noise = nullptr) {
     if (act_recorded) *act_recorded = 0;
-    // disturbance mode of this call: 0 none, 1 W from memory (distW), 2 drawn inside the kernels (noise).  `dist` below: either of the two,
-    // they share every rule and the dispatch
-    const int dmode = noise ? 2 : (distW ? 1 : 0);
+    // disturbance mode of this call: 0 none, 1 W from memory (distW), 2 drawn inside the kernels (noise), 3 drawn and correlated in time
+    // (noise with rho).  `dist` below: any of the three, they share every rule and the dispatch
+    const int dmode = noise ? (noise->rho ? 3 : 2) : (distW ? 1 : 0);
     const bool dist = dmode != 0;
     int rc = check_phi(phi);
     if (rc) return rc;
@@ -2232,6 +2245,9 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
     if (rc) return rc;
     pl.cb = phi->cb;
     if (workspace_bytes < plan_ws_bytes(pl)) return NOCF_E_WORKSPACE;
+    // mode 3 on the per-tile kernel: the carried w_{k-1} of the tile's T (d + 4) components sits in LDS behind the plan's carve
+    const size_t corrLds = dmode == 3 ? (size_t)pl.T * (phi->d + 4) * 4 : 0;
+    if ((size_t)pl.ldsFloats * 4 + corrLds > 160 * 1024) return NOCF_E_LDS;
     hipStream_t st = (hipStream_t)stream;
     float* ws = (float*)workspace;
     RollArgs ra;
@@ -2248,6 +2264,7 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
     ra.tapeU1 = nullptr; ra.tapeSc = nullptr;
     ra.dist = distW;                              // (disturbed rollouts: lane, then one-CU, then per-tile; never the split-role kernel)
     ra.nzScale = noise ? noise->scale : nullptr; ra.nzSeed = noise ? noise->seed : 0ull; ra.nzRow0 = noise ? (long)noise->row0 : 0l;
+    ra.nzScale1 = noise ? noise->scale1 : nullptr; ra.nzRho = noise ? noise->rho : nullptr;
     hipError_t e;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     const unsigned* errp = nullptr;
@@ -2278,7 +2295,9 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
             (void)hipEventRecord(ev0, st);
         }
         const size_t laneLds = ticket ? (size_t)(256 * 7 * 8 + 16) : 0;      // (the last-workgroup reduction's scratch: only with a ticket)
-#define NOCF_LANE_LAUNCH(MPV, DPV) do { if (dmode == 2 && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 2>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}); \
+#define NOCF_LANE_LAUNCH(MPV, DPV) do { if (dmode == 3 && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 3>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}); \
+                                         else if (dmode == 3) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 3>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}); \
+                                         else if (dmode == 2 && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 2>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}); \
                                          else if (dmode == 2) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 2>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}); \
                                          else if (dist && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 1>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}); \
                                          else if (dist) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 1>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}); \
@@ -2290,7 +2309,7 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
 #undef NOCF_LANE_LAUNCH
         e = hipGetLastError();
         if (e) return (int)e;
-        g_last_kernel = dmode == 2 ? "rollout_lane_kernel<noise>" : dist ? "rollout_lane_kernel<dist>" : "rollout_lane_kernel";
+        g_last_kernel = dmode == 3 ? "rollout_lane_kernel<noise-corr>" : dmode == 2 ? "rollout_lane_kernel<noise>" : dist ? "rollout_lane_kernel<dist>" : "rollout_lane_kernel";
         if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
         if (cost_sums && !ticket) {
             hipLaunchKernelGGL(cost_sum_kernel, dim3(1), dim3(256), 0, st, persample, (long)n, cost_sums, errp, mean_args);
@@ -2345,7 +2364,7 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
         hipLaunchKernelGGL(mono_pack_kernel, dim3(64), dim3(256), 0, st, mpl, P, ws);
         const size_t ldsBytes = (size_t)mpl.pp.ldsFloats * 4;
         const void* fk = nullptr;
-#define NOCF_MONO_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) fk = dmode == 2 ? (s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, 2>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 2>)) : dist ? (s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, 1>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 1>)) : s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false>);
+#define NOCF_MONO_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) fk = dmode == 3 ? (s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, 3>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 3>)) : dmode == 2 ? (s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, 2>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 2>)) : dist ? (s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, 1>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 1>)) : s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false>);
         MONO_SHAPES(NOCF_MONO_PICK)
 #undef NOCF_MONO_PICK
         e = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes); if (e) return (int)e;
@@ -2365,7 +2384,7 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
         e = hipLaunchKernel(fk, dim3((int)((n + 15) / 16)), dim3(256), args, ldsBytes, st); if (e) return (int)e;
         ra.act = nullptr; ra.actRows = 0;
         if (mono_rec && act_recorded) *act_recorded = 1;
-        g_last_kernel = dmode == 2 ? "rollout_mono_kernel<noise>" : dist ? "rollout_mono_kernel<dist>" : "rollout_mono_kernel";
+        g_last_kernel = dmode == 3 ? "rollout_mono_kernel<noise-corr>" : dmode == 2 ? "rollout_mono_kernel<noise>" : dist ? "rollout_mono_kernel<dist>" : "rollout_mono_kernel";
         e = hipGetLastError();
         if (e) return (int)e;
         if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
@@ -2386,7 +2405,7 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
     }
     if (seg) return NOCF_E_SHAPE;                     // (segments: no one-CU instantiation for this shape -- the caller launches them one by one)
     {
-        const size_t ldsBytes = (size_t)pl.ldsFloats * 4;
+        const size_t ldsBytes = (size_t)pl.ldsFloats * 4 + corrLds;
         const int grid = (int)((n + pl.T - 1) / pl.T);
         const int block = pl.nwaves * 64;
         if (g_prof_on) {
@@ -2399,7 +2418,8 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
             // compile-time one bit for bit, so the environment knobs and odd shapes always get the generic kernel
             const void* fk = nullptr;
 #define NOCF_TRY_FIXED(D, M, NTH, R, NAG) \
-            if (!fk && plan_is<FixedPlan<D, M, NTH, R, NAG, 0>>(pl)) fk = dmode == 2 ? reinterpret_cast<const void*>(rollout_kernel<1, FixedPlan<D, M, NTH, R, NAG, 0>, 2>) \
+            if (!fk && plan_is<FixedPlan<D, M, NTH, R, NAG, 0>>(pl)) fk = dmode == 3 ? reinterpret_cast<const void*>(rollout_kernel<1, FixedPlan<D, M, NTH, R, NAG, 0>, 3>) \
+                                                                   : dmode == 2 ? reinterpret_cast<const void*>(rollout_kernel<1, FixedPlan<D, M, NTH, R, NAG, 0>, 2>) \
                                                                    : dist ? reinterpret_cast<const void*>(rollout_kernel<1, FixedPlan<D, M, NTH, R, NAG, 0>, 1>) \
                                                                               : reinterpret_cast<const void*>(rollout_kernel<1, FixedPlan<D, M, NTH, R, NAG, 0>>);
             FIXED_SHAPES(NOCF_TRY_FIXED)
@@ -2416,15 +2436,23 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
                 void* args[] = {(void*)&plp, (void*)&pb, (void*)&ws, (void*)&ra};
                 e = hipLaunchKernel(fk, dim3(grid), dim3(block), args, ldsBytes, st); if (e) return (int)e;
                 launched = true;
-                g_last_kernel = dmode == 2 ? "rollout_kernel<shape-specialised, noise>" : dist ? "rollout_kernel<shape-specialised, dist>" : "rollout_kernel<shape-specialised>";
+                g_last_kernel = dmode == 3 ? "rollout_kernel<shape-specialised, noise-corr>" : dmode == 2 ? "rollout_kernel<shape-specialised, noise>" : dist ? "rollout_kernel<shape-specialised, dist>" : "rollout_kernel<shape-specialised>";
                 if (env_int("NOCF_DEBUG", 0)) fprintf(stderr, "[nocf] shape-specialised rollout kernel\n");
             }
         }
-        if (!launched) g_last_kernel = dmode == 2 ? "rollout_kernel<generic, noise>" : dist ? "rollout_kernel<generic, dist>" : "rollout_kernel<generic>";
+        if (!launched) g_last_kernel = dmode == 3 ? "rollout_kernel<generic, noise-corr>" : dmode == 2 ? "rollout_kernel<generic, noise>" : dist ? "rollout_kernel<generic, dist>" : "rollout_kernel<generic>";
         if (!launched && env_int("NOCF_DEBUG", 0))
             fprintf(stderr, "[nocf] generic rollout kernel: T %d, %d waves, SK1/SK6/SKm %d/%d/%d, cap %d, LDS %zu B/workgroup\n",
                     pl.T, pl.nwaves, pl.SK1, pl.SK6, pl.SKm, skCap, ldsBytes);
-        if (!launched && dmode == 2) switch (pl.T / 4) {
+        if (!launched && dmode == 3) switch (pl.T / 4) {
+            case 1: e = set_lds(rollout_kernel<1, DynPlan, 3>, ldsBytes); if (e) return (int)e;
+                    hipLaunchKernelGGL((rollout_kernel<1, DynPlan, 3>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
+            case 2: e = set_lds(rollout_kernel<2, DynPlan, 3>, ldsBytes); if (e) return (int)e;
+                    hipLaunchKernelGGL((rollout_kernel<2, DynPlan, 3>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
+            default: e = set_lds(rollout_kernel<4, DynPlan, 3>, ldsBytes); if (e) return (int)e;
+                    hipLaunchKernelGGL((rollout_kernel<4, DynPlan, 3>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
+        }
+        else if (!launched && dmode == 2) switch (pl.T / 4) {
             case 1: e = set_lds(rollout_kernel<1, DynPlan, 2>, ldsBytes); if (e) return (int)e;
                     hipLaunchKernelGGL((rollout_kernel<1, DynPlan, 2>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
             case 2: e = set_lds(rollout_kernel<2, DynPlan, 2>, ldsBytes); if (e) return (int)e;
@@ -2499,6 +2527,19 @@ int nocf_rollout_noisy_f32(const NocfPhi* phi, const NocfProb* prob, const float
                         workspace, workspace_bytes, stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, cost_means, nullptr, &nz);
 }
 
+int nocf_rollout_noisy_corr_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, const float* scale0, const float* scale1, const float* rho,
+                                uint64_t seed, int64_t row0, int64_t n,
+                                double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                float* z_out, float* persample, float* cost_sums, float* cost_means, float* zFull, float* ctrlFull,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    if (!scale0 || !scale1 || !rho) return NOCF_E_NULL;
+    if (row0 < 0) return NOCF_E_SHAPE;
+    if (cost_means && !cost_sums) return NOCF_E_NULL;
+    const NoiseSpec nz{scale0, (unsigned long long)seed, (long long)row0, scale1, rho};
+    return rollout_impl(phi, prob, x, n, t0, t1, nt, stepper, alph, z_out, persample, cost_sums, zFull, ctrlFull,
+                        workspace, workspace_bytes, stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, cost_means, nullptr, &nz);
+}
+
 int nocf_rollout_segments_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n,
                               int32_t nseg, int64_t rows_per_seg, const double* t0s, double t1, const int32_t* nts, const int32_t* slot0s,
                               int32_t stepper, const float* alph, float* z_out, float* persample, float* cost_sums, float* zFull, float* ctrlFull,
@@ -2551,6 +2592,19 @@ int nocf_rollout_record_noisy_f32(const NocfPhi* phi, const NocfProb* prob, cons
                         workspace, workspace_bytes, stream, s_all, act_rec, recorded, nullptr, nullptr, nullptr, nullptr, nullptr, &nz);
 }
 
+int nocf_rollout_record_noisy_corr_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, const float* scale0, const float* scale1,
+                                       const float* rho, uint64_t seed, int64_t row0, int64_t n,
+                                       double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                                       float* z_out, float* persample, float* cost_sums, float* s_all, float* act_rec, int32_t* recorded,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+    if (recorded) *recorded = 0;
+    if (!scale0 || !scale1 || !rho || !s_all || !z_out) return NOCF_E_NULL;
+    if (row0 < 0) return NOCF_E_SHAPE;
+    const NoiseSpec nz{scale0, (unsigned long long)seed, (long long)row0, scale1, rho};
+    return rollout_impl(phi, prob, x, n, t0, t1, nt, stepper, alph, z_out, persample, cost_sums, nullptr, nullptr,
+                        workspace, workspace_bytes, stream, s_all, act_rec, recorded, nullptr, nullptr, nullptr, nullptr, nullptr, &nz);
+}
+
 // W[k][row][i] = the disturbance of (seed, row0 + row, k, i): what the <noise> kernels add, as a tensor (nocf_noise.inc)
 int nocf_noise_fill_f32(float* W, int64_t n, int32_t nt, int32_t d, const float* scale, uint64_t seed, int64_t row0, void* stream) {
     if (!W || !scale) return NOCF_E_NULL;
@@ -2558,6 +2612,18 @@ int nocf_noise_fill_f32(float* W, int64_t n, int32_t nt, int32_t d, const float*
     const int64_t total = n * (int64_t)nt * d;
     const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 65536);
     hipLaunchKernelGGL(noise_fill_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, W, (long)n, (int)nt, (int)d, scale,
+                       (unsigned long long)seed, (long)row0);
+    return (int)hipGetLastError();
+}
+
+// the same for the time-correlated path: what the <noise-corr> kernels add, as a tensor
+int nocf_noise_fill_corr_f32(float* W, int64_t n, int32_t nt, int32_t d, const float* scale0, const float* scale1, const float* rho,
+                             uint64_t seed, int64_t row0, void* stream) {
+    if (!W || !scale0 || !scale1 || !rho) return NOCF_E_NULL;
+    if (n < 1 || nt < 1 || d < 1 || row0 < 0) return NOCF_E_SHAPE;
+    const int64_t per = n * (int64_t)d;
+    const unsigned grid = (unsigned)std::min<int64_t>((per + 255) / 256, 65536);
+    hipLaunchKernelGGL(noise_fill_corr_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, W, (long)n, (int)nt, (int)d, scale0, scale1, rho,
                        (unsigned long long)seed, (long)row0);
     return (int)hipGetLastError();
 }

@@ -40,7 +40,9 @@ struct EnsArgs { unsigned n; long xs; const float* alph; };
 // recording forward of disturbed training): the next step's first stage input is formed from the displaced z, so it is recorded displaced
 // DIST == 2: the same with the entry drawn here (nocf_noise.inc: RollArgs::nzScale / nzSeed / nzRow0) where DIST == 1 loads it -- into the same
 // register, at the top of the step, so every instruction behind it is shared.  Tail waves draw the noise of the row they replicate
-// ENS: an ensemble of E networks of one shape in one launch (every DIST, ONE = false).  A wave is a whole sample and nothing in a workgroup is
+// DIST == 3: time-correlated noise (nocf_noise.inc, DESIGN.md section 3.18): DIST == 2 with the entry formed from the lane's carried w_{k-1},
+// one more register per lane for the whole rollout; single networks only (no ENS instantiation exists)
+// ENS: an ensemble of E networks of one shape in one launch (DIST 0 / 1 / 2, ONE = false).  A wave is a whole sample and nothing in a workgroup is
 // shared, so the only change is WHICH network, multipliers and start a wave reads: the member e = row / ensN is wave-uniform and is kept, with
 // the member's eight tensor pointers and its row of the multiplier table, in scalar registers; every statement of the rollout behind these
 // reads is the single-network one, so member e's rows carry the bits of the single-network call on that member.  Every ENS test is
@@ -106,7 +108,9 @@ __global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb 
     const float cw = lane < D1 ? P.cw[lane] : 0.f;
     const float xt = lane < d ? pb.xtarget[lane] : 0.f;
     float nzs = 0.f;                                    // this lane's component of sigma sqrt(h)
-    if constexpr (DIST == 2) nzs = lane < d ? nzScale[lane] : 0.f;
+    if constexpr (DIST == 2 || DIST == 3) nzs = lane < d ? nzScale[lane] : 0.f;
+    float nzs1 = 0.f, nzr = 0.f, wc = 0.f;              // DIST == 3: this lane's s1 and rho, and the carried w_{k-1} (one register per lane)
+    if constexpr (DIST == 3) { nzs1 = lane < d ? ra.nzScale1[lane] : 0.f; nzr = lane < d ? ra.nzRho[lane] : 0.f; }
 
     // ---- agent pairs handled by this lane (two trips cover up to 128 pairs; eligibility keeps N <= 15)
     const int npairs = (N * (N - 1)) / 2;
@@ -215,7 +219,8 @@ __global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb 
         const double hsd = t1k - tk;                      // stepRK4 re-derives h = t1 - t0 (src/OCflow.py:170)
         const float hs = (float)hsd;
         float wk = 0.f;
-        if constexpr (DIST == 2) wk = lane < d ? noise_value(nzs, nzSeed, ra.nzRow0 + (ENS ? xr : row), k, lane) : 0.f;
+        if constexpr (DIST == 3) { wc = lane < d ? noise_corr_value(nzs, nzs1, nzr, wc, nzSeed, ra.nzRow0 + row, k, lane) : 0.f; wk = wc; }
+        else if constexpr (DIST == 2) wk = lane < d ? noise_value(nzs, nzSeed, ra.nzRow0 + (ENS ? xr : row), k, lane) : 0.f;
         else if constexpr (DIST == 1 && ENS) wk = lane < d ? wmem[((long)k * ea.n + xr) * d + lane] : 0.f;
         else if constexpr (DIST == 1) wk = lane < d ? ra.dist[((long)k * ra.n + row) * d + lane] : 0.f;
         // training: the stage input s = [x, t] of every evaluation goes to sAll[(k*nstage + st)][sample][0..d] (one row per lane group)

@@ -199,7 +199,10 @@ __device__ __forceinline__ void mono_sincos(float x, float& sn, float& cs) {
 // disturbed training): the state rows SB hold the displaced state when the next step's first stage input and activations are recorded
 // DIST == 2: the entries are drawn (nocf_noise.inc: RollArgs::nzScale / nzSeed / nzRow0) where DIST == 1 ADDS them, behind the last stage, into the
 // same variable: nothing is held across the step's evaluations (drawn at the top of the step like the loads, the (4, 2) instantiation lost a wave)
-// ENS (every DIST): an ensemble, see MonoEnsArgs.  ra.n is a member's row count; member e = blockIdx.x / en.tiles is workgroup-uniform, the
+// DIST == 3: time-correlated noise (nocf_noise.inc, DESIGN 3.18): the entry is formed where DIST == 2 draws it, from the w_{k-1} this thread carries
+// for each of its components of the sweep (wcar: KBD + 1 registers at most, one for singlequad; RollArgs::nzScale1 / nzRho); rows past n and the
+// four cost components carry 0 and draw nothing, so a tail tile's replicated rows leave the real rows' paths alone.  Single networks only
+// ENS (DIST 0 / 1 / 2): an ensemble, see MonoEnsArgs.  ra.n is a member's row count; member e = blockIdx.x / en.tiles is workgroup-uniform, the
 // member's last tile replicates the member's row n - 1.  Every ENS test is a compile-time choice at its place of use.
 // ENS with DIST == 2 (nocf_rollout_noisy_mid_ensemble_f32, DESIGN 3.14): member e under its own noise level and seed, EnsNoiseArgs (nocf_noise.inc)
 // as a further last argument that no other instantiation reads.  row0 is the tile's first row INSIDE the member, so ra.nzRow0 + row0 + s_ is
@@ -342,6 +345,11 @@ __global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __res
     const bool quad1 = quad && pb.nAgents == 1 && d == 12 && KBD == 1;     // singlequad: wave-local physics below
     float qz0 = quad1 ? Z0[(tid >> 4) * ZLD + (tid & 15)] : 0.f, qzA = 0.f; // ... with component tid%16 of sample tid/16 of z in registers
     bool sf_ready = false;                                             // the RK update has already written the next stage state's fragments
+    float wcar[KBD + 1];                                               // DIST == 3: w_{k-1} of this thread's components of the write-back sweep
+    if constexpr (DIST == 3) {
+#pragma unroll
+        for (int q = 0; q < KBD + 1; ++q) wcar[q] = 0.f;
+    }
 
     for (int k = 0; k <= sg_nt; ++k) {
         const bool fin = (k == sg_nt);
@@ -634,7 +642,12 @@ __global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __res
                     float xs_;
                     if (last) {
                         xs_ = (nstage == 1 ? qz0 : qzA) + rk_wa * K;
-                        if constexpr (DIST == 2) xs_ += (j < d && row0 + s_ < ra.n) ? noise_value(ra.nzScale[j], ra.nzSeed, ra.nzRow0 + row0 + s_, k, j) : 0.f;
+                        if constexpr (DIST == 3) {
+                            if (j < d && row0 + s_ < ra.n)
+                                wcar[0] = noise_corr_value(ra.nzScale[j], ra.nzScale1[j], ra.nzRho[j], wcar[0], ra.nzSeed, ra.nzRow0 + row0 + s_, k, j);
+                            xs_ += wcar[0];                                    // (j >= 12 and rows past n: 0 for the whole rollout)
+                        }
+                        else if constexpr (DIST == 2) xs_ += (j < d && row0 + s_ < ra.n) ? noise_value(ra.nzScale[j], ra.nzSeed, ra.nzRow0 + row0 + s_, k, j) : 0.f;
                         else if constexpr (DIST == 1) xs_ += wpre[0];          // (j >= 12: 0)
                         qz0 = xs_;
                     }
@@ -690,7 +703,17 @@ __global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __res
                     if constexpr (DIST) {
                         if (last) {
                             float w = 0.f;
-                            if constexpr (DIST == 2) {
+                            if constexpr (DIST == 3) {
+                                // (trip `it` of the sweep is the same (t, i) in every step: its w_{k-1} is wcar[it], selected like wpre)
+                                if (i < d && row0 + t < ra.n) {
+                                    float wp = 0.f;
+#pragma unroll
+                                    for (int q = 0; q < NDW; ++q) wp = (it == q) ? wcar[q] : wp;
+                                    w = noise_corr_value(ra.nzScale[i], ra.nzScale1[i], ra.nzRho[i], wp, ra.nzSeed, ra.nzRow0 + row0 + t, k, i);
+#pragma unroll
+                                    for (int q = 0; q < NDW; ++q) wcar[q] = (it == q) ? w : wcar[q];
+                                }
+                            } else if constexpr (DIST == 2) {
                                 if (i < d && row0 + t < ra.n) w = noise_value(ra.nzScale[i], ra.nzSeed, ra.nzRow0 + row0 + t, k, i);
                             } else {
 #pragma unroll

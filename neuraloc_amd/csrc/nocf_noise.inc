@@ -1,7 +1,8 @@
 // nocf_noise.inc -- the counter-based Brownian disturbance (DESIGN.md section 3.10): entry (row, k, i) of the disturbance is a pure function
 // of (seed, GLOBAL row, step, component), so a row meets the same noise alone, in any batch, on any rank and in any chunk, and no tensor
 // W [nt][n][d] has to exist.  Included by nocf_kernels.hip in front of the three rollout kernels (the DIST == 2 instantiations read
-// RollArgs::nzScale / nzSeed / nzRow0, nocf_dev.h); noise_words is host code too (nocf_debug_noise_words).
+// RollArgs::nzScale / nzSeed / nzRow0, nocf_dev.h); noise_words is host code too (nocf_debug_noise_words).  DIST == 3 chains these entries
+// into a time-correlated path per (row, component): noise_corr_next / noise_corr_value below (section 3.18).
 //
 //   words   Philox4x32-10, counter (row lo, row hi, k, i), key (seed lo, seed hi)
 //   u1, u2  ((w >> 9) + 0.5) 2^-23 of words 0 and 1: exact in fp32, inside [2^-24, 1 - 2^-24]
@@ -40,6 +41,28 @@ __device__ __forceinline__ float noise_value(float scale, unsigned long long see
     return v;
 }
 
+// Time-correlated (AR(1) / Ornstein-Uhlenbeck) noise, DIST == 3 (DESIGN.md section 3.18): per component i, rho_i in [0, 1),
+//   w_0 = noise_value(s0_i, seed, row, 0, i)                                        s0_i = fp32(sigma_i sqrt(h))
+//   w_k = fl(fl(rho_i w_{k-1}) + noise_value(s1_i, seed, row, k, i))    k >= 1      s1_i = fp32(sigma_i sqrt(h) sqrt(1 - rho_i^2))
+// so every w_k has the white entry's variance and corr(w_k, w_{k+j}) = rho_i^j.  Two roundings, never an fma: the product and the sum each
+// leave through an empty asm (noise_value's fence), so neither can merge with the other or with the caller's +=, and numpy float32
+// arithmetic restates the path bit for bit.  The carried w_{k-1} stays with the thread that forms the component's entry (a register on the
+// lane and one-CU kernels, an LDS slot of its own on the per-tile kernel); s0 is RollArgs::nzScale, s1 and rho are RollArgs::nzScale1 / nzRho.
+__device__ __forceinline__ float noise_corr_next(float rho, float wprev, float v) {
+    float p = __fmul_rn(rho, wprev);
+    asm volatile("" : "+v"(p));
+    float w = __fadd_rn(p, v);
+    asm volatile("" : "+v"(w));
+    return w;
+}
+
+// entry k of the path of (row, i), given entry k - 1 (ignored at k == 0)
+__device__ __forceinline__ float noise_corr_value(float s0, float s1, float rho, float wprev, unsigned long long seed, long long row, int k, int i) {
+    const float v = noise_value(k == 0 ? s0 : s1, seed, row, k, i);
+    const float w = noise_corr_next(rho, wprev, v);
+    return k == 0 ? v : w;
+}
+
 // Noisy ENSEMBLES (nocf_rollout_noisy_ensemble_f32 / nocf_rollout_noisy_mid_ensemble_f32, DESIGN.md section 3.14): every member under its own
 // level and seed -- scale [E, d] (member e's fp32 sigma_i sqrt(h)) and seeds [E], device tables.  The LAST argument of the lane and the one-CU
 // rollout kernels, behind EnsArgs / MonoEnsArgs and for their reason (the offsets of the arguments in front of it stay where they are), and
@@ -58,5 +81,23 @@ __global__ void __launch_bounds__(256) noise_fill_kernel(float* __restrict__ W, 
         const long row = rem / d;
         const int i = (int)(rem - row * d);
         W[e] = noise_value(scale[i], seed, row0 + row, (int)k, i);
+    }
+}
+
+// W[k][row][i] = entry k of the correlated path of (row0 + row, i): one thread per (row, i) walks k, so for every k the stores of
+// neighbouring threads are neighbours in W
+__global__ void __launch_bounds__(256) noise_fill_corr_kernel(float* __restrict__ W, long n, int nt, int d, const float* __restrict__ scale0,
+                                                              const float* __restrict__ scale1, const float* __restrict__ rho,
+                                                              unsigned long long seed, long row0) {
+    const long per = n * d;
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < per; e += (long)gridDim.x * 256) {
+        const long row = e / d;
+        const int i = (int)(e - row * d);
+        const float s0 = scale0[i], s1 = scale1[i], r = rho[i];
+        float w = 0.f;
+        for (int k = 0; k < nt; ++k) {
+            w = noise_corr_value(s0, s1, r, w, seed, row0 + row, k, i);
+            W[(long)k * per + e] = w;
+        }
     }
 }

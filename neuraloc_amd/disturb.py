@@ -108,12 +108,18 @@ def disturbed_rollout(x, Phi, prob, nt, W, tspan=(0., 1.), alph=None, stepper="r
     return out
 
 
-def brownian_disturbances(nt, n, d, sigma, tspan=(0., 1.), generator=None, device=None, mask=None):
+def brownian_disturbances(nt, n, d, sigma, tspan=(0., 1.), generator=None, device=None, mask=None, rho=None):
     """sigma * sqrt(h) * randn, time-major [nt, n, d], float32: the increments of sigma dB over steps of h = (tspan[1] - tspan[0]) / nt.
     sigma: a float or a [d] tensor; mask [d]: coordinates with mask == 0 are not disturbed (the quadcopter's velocities only, say);
-    generator: a torch.Generator of `device` (default: that device's global one)."""
+    generator: a torch.Generator of `device` (default: that device's global one).
+    rho: a float or [d] in [0, 1): the white draws v_k become an AR(1) / Ornstein-Uhlenbeck path in k, w_0 = v_0 and
+    w_k = rho_i w_{k-1} + sqrt(1 - rho_i^2) v_k -- the recursion of noise.counter_disturbances(..., rho=) in plain torch on randn draws (the
+    same variance at every step, corr(w_k, w_{k+j}) = rho_i^j; no bit contract).  rho=0.0 gives the white tensor."""
     if int(nt) < 1 or int(n) < 1 or int(d) < 1:
         raise ValueError("nt, n and d must be >= 1")
+    if rho is not None:
+        from .noise import check_rho
+        rho = check_rho(rho, d, "brownian_disturbances")
     h = (float(tspan[1]) - float(tspan[0])) / int(nt)
     if not h > 0:
         raise ValueError("tspan must have positive length")
@@ -129,6 +135,11 @@ def brownian_disturbances(nt, n, d, sigma, tspan=(0., 1.), generator=None, devic
         if mk.numel() != int(d):
             raise ValueError("mask must have d entries")
         W = W * (mk.reshape(-1) != 0).to(torch.float32)
+    if rho is not None:
+        r = rho.to(W.device, torch.float32)
+        q = torch.sqrt(1.0 - rho * rho).to(W.device, torch.float32)
+        for k in range(1, int(nt)):
+            W[k] = r * W[k - 1] + q * W[k]
     return W.contiguous()
 
 
@@ -143,13 +154,15 @@ def path_statistics(v):
 
 
 def noise_study(x, Phi, prob, nt, sigma, paths, tspan=(0., 1.), alph=None, stepper="rk4", generator=None, mask=None, max_rows=1 << 16,
-                rng="torch", seed=None):
+                rng="torch", seed=None, rho=None):
     """The distribution of the costs over `paths` Brownian disturbances of every start: each start is repeated `paths` times as rows of one
     batch (start-major: row i * paths + p), in chunks of whole starts of at most max_rows rows (max_rows < paths is a ValueError), one launch
     per chunk.  The disturbances are drawn chunk by chunk from `generator` (brownian_disturbances(nt, rows, d, sigma, tspan=tspan,
     generator=generator, device=x.device, mask=mask)).
     rng="counter" (needs `seed`, a Python int in [0, 2**64); takes no generator): nothing is drawn -- every chunk is one noise.noisy_rollout
     with row_offset = the chunk's first row, so start i, path p meets the noise of global row i * paths + p whatever max_rows is.
+    rho (a float or [d] in [0, 1)): the disturbances are correlated in time -- rng="counter": noisy_rollout(..., rho=rho), the path of a
+    global row whatever max_rows is; rng="torch": brownian_disturbances(..., rho=rho).  A PhiEnsemble with rho is refused.
     :return: dict with, per quantity "L+G" (L + alph[0] G), "G", "Q", "W": a dict mean / std / q05 / q50 / q95 of [nex] tensors; and
              "persample" [nex, paths, 7], the table every figure is formed from"""
     alph = list(Phi.alph if alph is None else alph)
@@ -164,6 +177,11 @@ def noise_study(x, Phi, prob, nt, sigma, paths, tspan=(0., 1.), alph=None, stepp
         _check_seed(seed)
     elif seed is not None:
         raise ValueError("noise_study: seed belongs to rng='counter'; rng='torch' is seeded through generator")
+    if rho is not None:
+        from .noise import _refuse_ensemble, check_rho
+        _refuse_ensemble(Phi, "noise_study")
+        if isinstance(x, torch.Tensor) and x.dim() == 2:
+            check_rho(rho, x.shape[1], "noise_study")
     paths = int(paths)
     if paths < 1:
         raise ValueError("paths must be >= 1")
@@ -178,10 +196,12 @@ def noise_study(x, Phi, prob, nt, sigma, paths, tspan=(0., 1.), alph=None, stepp
     for s0 in range(0, n, per):
         xs = x[s0:s0 + per].repeat_interleave(paths, dim=0).contiguous()
         if rng == "counter":
+            kw = {} if rho is None else {"rho": rho}
             tabs.append(noisy_rollout(xs, Phi, prob, nt, sigma, seed, tspan=tspan, alph=alph, stepper=stepper, mask=mask,
-                                      row_offset=s0 * paths)["persample"])
+                                      row_offset=s0 * paths, **kw)["persample"])
             continue
-        Wc = brownian_disturbances(nt, xs.shape[0], d, sigma, tspan=tspan, generator=generator, device=x.device, mask=mask)
+        kw = {} if rho is None else {"rho": rho}
+        Wc = brownian_disturbances(nt, xs.shape[0], d, sigma, tspan=tspan, generator=generator, device=x.device, mask=mask, **kw)
         tabs.append(disturbed_rollout(xs, Phi, prob, nt, Wc, tspan=tspan, alph=alph, stepper=stepper)["persample"])
     tab = torch.cat(tabs).view(n, paths, 7)
     _lib.check_errors(sync=True)

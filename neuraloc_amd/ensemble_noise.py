@@ -116,8 +116,11 @@ class _Noise:
         return (C.c_void_p(t[0].data_ptr()), C.c_void_p(t[0].data_ptr() + t[1]), self.row_offset)
 
 
-def _prepare(fn, x, ens, prob, tspan, nt, sigma, seed, stepper, train, mask, row_offset, family):
+def _prepare(fn, x, ens, prob, tspan, nt, sigma, seed, stepper, train, mask, row_offset, family, rho=None):
     """every refusal of a noisy ensemble call -> (E, n, d, _Noise); nothing here touches a device"""
+    if rho is not None:
+        raise NotImplementedError(f"{fn}: rho is not supported for ensembles; the time-correlated noise takes one network "
+                                  "(noisy_rollout / noisy_ocflow_train with rho=; per-member rho is not built)")
     if isinstance(ens, ensemble.PhiEnsemble) and isinstance(x, torch.Tensor) and x.dim() in (2, 3):
         table = scale_table(sigma, ens.members, nt, x.shape[-1], tspan, mask) if int(nt) >= 1 else None
         seeds = seed_list(seed, ens.members)
@@ -131,7 +134,7 @@ def _prepare(fn, x, ens, prob, tspan, nt, sigma, seed, stepper, train, mask, row
 
 
 def ensemble_noisy_rollout(x, ens, prob, tspan, nt, sigma, seed, stepper="rk4", alph=None, intermediates=False, *, mask=None, row_offset=0,
-                           family="lane"):
+                           family="lane", rho=None):
     """ensemble_rollout with every member under per-step Brownian noise drawn inside the kernel, in one launch.
     :param sigma: a float or [d] (every member that level), or [E, 1] / [E, d] (a 2-D tensor or nested list: member e its row).  A member at 0
                   is rolled out undisturbed, bit for bit
@@ -139,9 +142,10 @@ def ensemble_noisy_rollout(x, ens, prob, tspan, nt, sigma, seed, stepper="rk4", 
                   row_offset + j); or a sequence of E ints, one per member
     :param mask:  [d]: coordinates with mask == 0 are not disturbed;  row_offset: the key of row 0 of every member, as in noisy_rollout
     :param x, ens, prob, tspan, nt, stepper, alph, intermediates, family: as for ensemble_rollout
+    :param rho:   refused (NotImplementedError) unless None: the time-correlated noise of noisy_rollout takes one network
     :return: what ensemble_rollout returns: (Jc [E], cs [E, 7]); with intermediates also the trajectories [E, nex, d+4, nt+1] and the controls
              [E, nex, a, nt+1].  Member e's values are bit for bit noisy_rollout's on ens.member(e) with sigma_e, seed_e, mask and row_offset."""
-    E, n, d, nz = _prepare("ensemble_noisy_rollout", x, ens, prob, tspan, nt, sigma, seed, stepper, False, mask, row_offset, family)
+    E, n, d, nz = _prepare("ensemble_noisy_rollout", x, ens, prob, tspan, nt, sigma, seed, stepper, False, mask, row_offset, family, rho)
     nt = int(nt)
     if family == "mid":
         b = ensemble._launch_mid(x, ens, prob, tspan, nt, stepper, alph, intermediates, noise=nz)
@@ -186,12 +190,13 @@ class _NoisyEnsembleTrainMid(torch.autograd.Function):
         return g[:7] + (None,) + g[7:]
 
 
-def ensemble_noisy_ocflow_train(x, ens, prob, tspan, nt, sigma, seed, stepper="rk4", alph=None, *, mask=None, row_offset=0, family="lane"):
+def ensemble_noisy_ocflow_train(x, ens, prob, tspan, nt, sigma, seed, stepper="rk4", alph=None, *, mask=None, row_offset=0, family="lane",
+                                rho=None):
     """(Jc [E], cs [E, 7]) under per-member Brownian noise, Jc differentiable in every stacked parameter of `ens` (and in x when every member
     has its own starts): one recording forward that draws the disturbances, then the ensemble adjoint launch of ensemble_ocflow_train
     unchanged.  Member e's Jc, gradients and x.grad[e] are bit for bit those of noisy_ocflow_train + backward() on ens.member(e) with sigma_e,
-    seed_e, mask and row_offset.  Arguments as for ensemble_noisy_rollout; shapes and problems as for ensemble_ocflow_train."""
-    _E, _n, _d, nz = _prepare("ensemble_noisy_ocflow_train", x, ens, prob, tspan, nt, sigma, seed, stepper, True, mask, row_offset, family)
+    seed_e, mask and row_offset.  Arguments as for ensemble_noisy_rollout; shapes and problems as for ensemble_ocflow_train (rho: refused unless None)."""
+    _E, _n, _d, nz = _prepare("ensemble_noisy_ocflow_train", x, ens, prob, tspan, nt, sigma, seed, stepper, True, mask, row_offset, family, rho)
     params = [p for _, p in ens._params()]
     fn = _NoisyEnsembleTrainMid if family == "mid" else _NoisyEnsembleTrain
     Jc, means = fn.apply(x, ens, prob, [float(tspan[0]), float(tspan[1])], int(nt), stepper, alph, nz, *params)
@@ -199,7 +204,7 @@ def ensemble_noisy_ocflow_train(x, ens, prob, tspan, nt, sigma, seed, stepper="r
 
 
 def ensemble_noise_study(x, ens, prob, nt, sigma, paths, seed, tspan=(0., 1.), alph=None, stepper="rk4", mask=None, max_rows=1 << 16,
-                         family="lane"):
+                         family="lane", rho=None):
     """noise_study(..., rng="counter") for every member of an ensemble, one launch per chunk: each start is repeated `paths` times as rows
     of a member's batch (start-major: row i * paths + p), in chunks of whole starts.  max_rows bounds the rows of ONE MEMBER per launch, as it
     bounds the rows of noise_study's launch: a launch holds at most E * max_rows rows in all (max_rows < paths is a ValueError).  Every chunk
@@ -209,6 +214,8 @@ def ensemble_noise_study(x, ens, prob, nt, sigma, paths, seed, tspan=(0., 1.), a
     :return: dict with, per quantity "L+G" (L + member e's alph[0] G), "G", "Q", "W": a dict mean / std / q05 / q50 / q95 of [E, nex] tensors;
              and "persample" [E, nex, paths, 7].  Member e's slices equal noise_study(x_e, ens.member(e), ..., sigma_e, rng="counter",
              seed=seed_e) on the same kernel family."""
+    if rho is not None:
+        _prepare("ensemble_noise_study", x, ens, prob, tspan, nt, sigma, seed, stepper, False, mask, 0, family, rho)
     paths = int(paths)
     if paths < 1:
         raise ValueError("paths must be >= 1")

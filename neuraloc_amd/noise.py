@@ -9,6 +9,12 @@ in any chunk (row_offset = the global index of the call's first row), and a pref
     noisy_rollout          disturbed_rollout on that tensor, bit for bit, without it (nocf_rollout_noisy_f32)
     noisy_ocflow_train     disturbed_ocflow_train likewise (nocf_rollout_record_noisy_f32); the adjoint is the same code
 
+rho= on all three: the disturbance of a (row, component) becomes an AR(1) / Ornstein-Uhlenbeck path in k,
+    w_0 = v_0(s0),  w_k = fl32(fl32(rho_i w_{k-1}) + v_k(s1)),   s0 = sigma_i sqrt(h),  s1 = s0 sqrt(1 - rho_i^2),
+with v_k(s) the white entry of scale s -- every w_k keeps the white variance and corr(w_k, w_{k+j}) = rho_i^j.  The carried value stays in
+the kernels (nocf_noise_fill_corr_f32, nocf_rollout_noisy_corr_f32, nocf_rollout_record_noisy_corr_f32); rho=None is the white path and
+its entry points, untouched, and rho=0.0 gives the white values through the new ones.
+
 Single precision only; no CPU or eager-torch fallback; every check raises before a device is touched."""
 import ctypes as C
 import math
@@ -30,8 +36,12 @@ _RECORD_ARGTYPES = [C.POINTER(_lib.NocfPhi), C.POINTER(_lib.NocfProb), C.c_void_
                     C.c_double, C.c_double, C.c_int32, C.c_int32, _lib.fp,
                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
                     C.c_void_p, C.c_size_t, C.c_void_p]
+# (the correlated entries: scale0, scale1, rho where `scale` stands)
 _PROTOTYPES = {"nocf_noise_fill_f32": _FILL_ARGTYPES, "nocf_rollout_noisy_f32": _NOISY_ARGTYPES,
-               "nocf_rollout_record_noisy_f32": _RECORD_ARGTYPES}
+               "nocf_rollout_record_noisy_f32": _RECORD_ARGTYPES,
+               "nocf_noise_fill_corr_f32": _FILL_ARGTYPES[:4] + [C.c_void_p] * 3 + _FILL_ARGTYPES[5:],
+               "nocf_rollout_noisy_corr_f32": _NOISY_ARGTYPES[:3] + [C.c_void_p] * 3 + _NOISY_ARGTYPES[4:],
+               "nocf_rollout_record_noisy_corr_f32": _RECORD_ARGTYPES[:3] + [C.c_void_p] * 3 + _RECORD_ARGTYPES[4:]}
 
 
 def _entry(L, name):
@@ -87,23 +97,74 @@ def noise_scale(sigma, nt, d, tspan=(0., 1.), mask=None):
     return scale.contiguous()
 
 
+def check_rho(rho, d, what="rho"):
+    """rho, a float or [d], as a float64 [d] tensor on the host; every refusal of a rho (outside [0, 1), non-finite, wrong shape, float64)"""
+    if isinstance(rho, bool):
+        raise ValueError(f"{what}: rho must be a float or a [d] tensor with 0 <= rho < 1, got {rho!r}")
+    if isinstance(rho, torch.Tensor):
+        if rho.dtype == torch.float64:
+            raise RuntimeError(f"{what}: rho is float64; the correlated noise is single precision only: pass a float or a float32 [d] tensor")
+        r = rho.detach().to("cpu", torch.float64)
+    else:
+        try:
+            r = torch.as_tensor(rho, dtype=torch.float64)
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError(f"{what}: rho must be a float or a [d] tensor with 0 <= rho < 1, got {rho!r}") from None
+    if r.dim() > 1 or (r.dim() == 1 and r.numel() != int(d)):
+        raise ValueError(f"{what}: rho must be a float or a [d] tensor with d = {int(d)}, got shape {tuple(r.shape)}")
+    r = r.expand(int(d)).contiguous()
+    # (the kernels multiply by fp32(rho): a rho that rounds to 1 there is no longer inside the interval)
+    if not bool(torch.isfinite(r).all()) or bool((r < 0).any()) or bool((r.to(torch.float32) >= 1).any()):
+        raise ValueError(f"{what}: rho must be finite with 0 <= rho < 1 (in float32), got {rho!r}")
+    return r
+
+
+def noise_corr_scales(sigma, rho, nt, d, tspan=(0., 1.), mask=None):
+    """(s0, s1, rho) [d] on the host, float32, of the correlated noise: s0 = noise_scale(sigma, ...) = fp32(sigma_i sqrt(h)),
+    s1 = fp32(sigma_i sqrt(h) sqrt(1 - rho_i^2)) -- both formed in double, both 0 where mask == 0 -- and fp32(rho_i).  rho = 0: s1 == s0"""
+    s0 = noise_scale(sigma, nt, d, tspan, mask)
+    r = check_rho(rho, d, "noise_corr_scales")
+    h = (float(tspan[1]) - float(tspan[0])) / int(nt)
+    sg = (sigma.detach().to("cpu", torch.float64) if isinstance(sigma, torch.Tensor) else torch.as_tensor(sigma, dtype=torch.float64))
+    s1 = (sg.expand(int(d)) * math.sqrt(h) * torch.sqrt(1.0 - r * r)).to(torch.float32)
+    if mask is not None:
+        s1 = s1 * (torch.as_tensor(mask).detach().to("cpu").reshape(-1) != 0).to(torch.float32)
+    return s0, s1.contiguous(), r.to(torch.float32).contiguous()
+
+
+def _refuse_ensemble(net, what):
+    from .ensemble import PhiEnsemble
+    if isinstance(net, PhiEnsemble):
+        raise NotImplementedError(f"{what}: rho with a PhiEnsemble is not supported; the correlated noise takes one network "
+                                  "(per-member rho is not built)")
+
+
 def _require_device(device, what):
     if device is None or torch.device(device).type != "cuda":
         raise RuntimeError(f"{what}: device is {device}: the generator runs only on an MI355X (ROCm 'cuda' device); there is no CPU fallback")
     return torch.device(device)
 
 
-def counter_disturbances(nt, n, d, sigma, seed, tspan=(0., 1.), mask=None, row_offset=0, device=None):
+def counter_disturbances(nt, n, d, sigma, seed, tspan=(0., 1.), mask=None, row_offset=0, device=None, rho=None):
     """The counterpart of brownian_disturbances: W [nt, n, d], float32, W[k, row, i] = the disturbance of (seed, row_offset + row, k, i) with
     scale sigma_i sqrt(h) -- the values noisy_rollout adds, as a tensor (nocf_noise_fill_f32).
     sigma: a float or [d]; mask [d]: coordinates with mask == 0 are not disturbed; seed: a Python int, 0 <= seed < 2**64;
-    row_offset: global index of row 0; device: an MI355X."""
+    row_offset: global index of row 0; device: an MI355X.
+    rho: a float or [d] in [0, 1): W[:, row, i] is the correlated path of the module's docstring (nocf_noise_fill_corr_f32)."""
     if int(nt) < 1 or int(n) < 1 or int(d) < 1:
         raise ValueError("nt, n and d must be >= 1")
     scale = noise_scale(sigma, nt, d, tspan, mask)
+    tabs = None if rho is None else noise_corr_scales(sigma, rho, nt, d, tspan, mask)
     seed, row_offset = _check_seed(seed), _check_row_offset(row_offset)
     dev = _require_device(device, "counter_disturbances")
     W = torch.empty(int(nt), int(n), int(d), dtype=torch.float32, device=dev)
+    if tabs is not None:
+        s0, s1, rh = (t.to(dev) for t in tabs)
+        with torch.cuda.device(dev):
+            _, f = _entry_for(_lib.lib(), "nocf_noise_fill_corr_f32", "counter_disturbances")
+            rc = f(_lib.ptr(W), int(n), int(nt), int(d), _lib.ptr(s0), _lib.ptr(s1), _lib.ptr(rh), seed, row_offset, _lib.stream_ptr(dev))
+        _lib.check(rc, "nocf_noise_fill_corr_f32")
+        return W
     scale = scale.to(dev)
     with torch.cuda.device(dev):
         _, f = _entry_for(_lib.lib(), "nocf_noise_fill_f32", "counter_disturbances")
@@ -133,15 +194,21 @@ def _check_call(what, x, net, nt, stepper, alph):
     return n, d
 
 
-def noisy_rollout(x, Phi, prob, nt, sigma, seed, tspan=(0., 1.), alph=None, stepper="rk4", intermediates=False, mask=None, row_offset=0):
+def noisy_rollout(x, Phi, prob, nt, sigma, seed, tspan=(0., 1.), alph=None, stepper="rk4", intermediates=False, mask=None, row_offset=0,
+                  rho=None):
     """disturbed_rollout(x, Phi, prob, nt, counter_disturbances(nt, nex, d, sigma, seed, tspan, mask, row_offset), ...) without the tensor: the
     kernels draw each disturbance where they would load it, and every output equals that call's bit for bit.
     :param sigma: a float or [d];  seed: a Python int, 0 <= seed < 2**64;  mask [d]: coordinates with mask == 0 are not disturbed
     :param row_offset: global index of x's first row: row j of this call meets the noise of global row row_offset + j
+    :param rho: a float or [d] in [0, 1): the correlated path (module docstring), counter_disturbances(..., rho=rho) without the tensor
+                (nocf_rollout_noisy_corr_f32); None: white noise
     :return: the dict of disturbed_rollout"""
+    if rho is not None:
+        _refuse_ensemble(Phi, "noisy_rollout")
     alph = list(Phi.alph if alph is None else alph)
     n, d = _check_call("noisy_rollout", x, Phi, nt, stepper, alph)
     scale = noise_scale(sigma, nt, d, tspan, mask)
+    corr = None if rho is None else noise_corr_scales(sigma, rho, nt, d, tspan, mask)[1:]
     seed, row_offset = _check_seed(seed), _check_row_offset(row_offset)
     x = _lib.require_device_f32(x, "x")
     Phi._guard_no_autograd(x, "noisy_rollout")
@@ -151,6 +218,11 @@ def noisy_rollout(x, Phi, prob, nt, sigma, seed, tspan=(0., 1.), alph=None, step
         prob_st, keep2 = prob._c_struct(x.device)
         dev = x.device
         scale = scale.to(dev)
+        name = "nocf_rollout_noisy_f32" if corr is None else "nocf_rollout_noisy_corr_f32"
+        tables = (_lib.ptr(scale),)
+        if corr is not None:
+            corr = tuple(t.to(dev) for t in corr)
+            tables += (_lib.ptr(corr[0]), _lib.ptr(corr[1]))
         persample = torch.empty(n, 7, dtype=torch.float32, device=dev)
         sums = torch.empty(8, dtype=torch.float32, device=dev)
         means = torch.empty(8, dtype=torch.float32, device=dev)
@@ -163,12 +235,12 @@ def noisy_rollout(x, Phi, prob, nt, sigma, seed, tspan=(0., 1.), alph=None, step
         alph_c = (C.c_float * 6)(*[float(a) for a in alph[:6]])
         with torch.cuda.device(dev):
             L = _lib.lib_for(Phi.d, Phi.m, Phi.nTh, phi_st.r, prob_st.n_agents, fwd=prob_st.kind != _lib.PROB_QUADCOPTER)
-            L, f = _entry_for(L, "nocf_rollout_noisy_f32", "noisy_rollout")
-            rc = f(C.byref(phi_st), C.byref(prob_st), _lib.ptr(x), _lib.ptr(scale), seed, row_offset, n,
+            L, f = _entry_for(L, name, "noisy_rollout")
+            rc = f(C.byref(phi_st), C.byref(prob_st), _lib.ptr(x), *tables, seed, row_offset, n,
                    float(tspan[0]), float(tspan[1]), int(nt), _STEPPERS[stepper], alph_c,
                    _lib.ptr(z_final), _lib.ptr(persample), _lib.ptr(sums), _lib.ptr(means), _lib.ptr(zFull), _lib.ptr(ctrlFull),
                    _lib.ptr(ws), ws.numel() * ws.element_size(), _lib.stream_ptr(dev))
-        _lib.check(rc, "nocf_rollout_noisy_f32")
+        _lib.check(rc, name)
         _lib.track_rollout_status(L, dev, "noisy_rollout")
         out = {"Jc": means[7], "cs": [means[i] for i in range(7)], "persample": persample, "z_final": z_final}
         if intermediates:
@@ -186,10 +258,13 @@ class _OCflowTrainNoisy(torch.autograd.Function):
         ctx.n_plain_args = 9
         ctx.x_needs_grad = bool(x.requires_grad)
         x = _lib.require_device_f32(x.detach(), "x")
-        scale, seed, row_offset = noise
+        scale, seed, row_offset = noise[:3]                # (with rho: two more entries, the tables s1 and rho; scale is then s0)
         n, d = x.shape
         dev = x.device
         scale = scale.to(dev)
+        corr = tuple(t.to(dev) for t in noise[3:])
+        name = "nocf_rollout_record_noisy_corr_f32" if corr else "nocf_rollout_record_noisy_f32"
+        tables = (_lib.ptr(scale),) + tuple(_lib.ptr(t) for t in corr)
         phi_st, keep1, ws = net._c_struct(n)
         prob_st, keep2 = prob._c_struct(dev)
         nstage = 4 if stepper == "rk4" else 1
@@ -202,7 +277,7 @@ class _OCflowTrainNoisy(torch.autograd.Function):
         ctx.tape = None
         with torch.cuda.device(dev):
             L = _lib.lib_for(net.d, net.m, net.nTh, phi_st.r, prob_st.n_agents, fwd=prob_st.kind != _lib.PROB_QUADCOPTER)
-            L, f = _entry_for(L, "nocf_rollout_record_noisy_f32", "noisy_ocflow_train")
+            L, f = _entry_for(L, name, "noisy_ocflow_train")
             ctx.mid_rows = int(L.nocf_mid_grad_rows(int(d), int(net.m), int(net.nTh), int(phi_st.r), int(prob_st.n_agents), int(n))) \
                 if hasattr(L, "nocf_rollout_bwd_mid_f32") else 0
             # (the activation record is the one-CU kernel's here, as in _OCflowTrainDisturbed: m = 512 records on the per-tile kernel)
@@ -215,11 +290,11 @@ class _OCflowTrainNoisy(torch.autograd.Function):
                 except torch.OutOfMemoryError:                 # the record is an optimisation: without it the adjoint recomputes
                     act = None
             recorded = C.c_int32(0)
-            rc = f(C.byref(phi_st), C.byref(prob_st), _lib.ptr(x), _lib.ptr(scale), seed, row_offset, n,
+            rc = f(C.byref(phi_st), C.byref(prob_st), _lib.ptr(x), *tables, seed, row_offset, n,
                    float(tspan[0]), float(tspan[1]), int(nt), _STEPPERS[stepper], alph_c,
                    _lib.ptr(z_out), _lib.ptr(persample), _lib.ptr(sums), _lib.ptr(s_all), _lib.ptr(act), C.byref(recorded),
                    _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-        _lib.check(rc, "nocf_rollout_record_noisy_f32")
+        _lib.check(rc, name)
         ctx.act = act if recorded.value else None
         ctx.persample = persample                          # (the [n, 7] table: risk._OCflowTrainWeighted forms the per-sample costs from it)
         return _OCflowTrain._forward_tail(ctx, L, dev, net, prob, tspan, nt, stepper, alph, n_total, group, n, sums, s_all, z_out)
@@ -230,12 +305,17 @@ class _OCflowTrainNoisy(torch.autograd.Function):
         return _OCflowTrain._adjoint(ctx, gJ)
 
 
-def noisy_ocflow_train(x, net, prob, tspan, nt, sigma, seed, stepper="rk4", alph=None, mask=None, row_offset=0, n_total=None, group=None):
+def noisy_ocflow_train(x, net, prob, tspan, nt, sigma, seed, stepper="rk4", alph=None, mask=None, row_offset=0, n_total=None, group=None,
+                       rho=None):
     """disturbed_ocflow_train under counter_disturbances(nt, nex, d, sigma, seed, tspan, mask, row_offset), without the tensor: (Jc, cs) with Jc
     differentiable w.r.t. every parameter of `net` and w.r.t. x when x requires a gradient.
     :param row_offset: global index of x's first row -- a rank passes the first row of its shard, and the noise a sample meets then does not
                        depend on how the batch is cut;  n_total, group: as for ocflow_train
+    :param rho: a float or [d] in [0, 1): training under the correlated path (module docstring; nocf_rollout_record_noisy_corr_f32).  The
+                path does not depend on the parameters, so the adjoint is the white one's, on the recorded displaced states
     Single precision only.  Every check below raises before a device is touched."""
+    if rho is not None:
+        _refuse_ensemble(net, "noisy_ocflow_train")
     alph = list(net.alph if alph is None else alph)
     for name, t in [("x", x)] + [(name, p_) for name, p_ in net.named_parameters()]:
         if isinstance(t, torch.Tensor) and t.dtype == torch.float64:
@@ -246,8 +326,10 @@ def noisy_ocflow_train(x, net, prob, tspan, nt, sigma, seed, stepper="rk4", alph
     if pd_ is not None and int(pd_) != d:
         raise ValueError(f"the problem object has d={pd_} but x has d={d}")
     scale = noise_scale(sigma, nt, d, tspan, mask)
+    corr = () if rho is None else noise_corr_scales(sigma, rho, nt, d, tspan, mask)[1:]
     seed, row_offset = _check_seed(seed), _check_row_offset(row_offset)
     _lib.require_device_f32(x, "x")
     params = [p for _, p in net.named_parameters()]
-    Jc, means = _OCflowTrainNoisy.apply(x, net, prob, list(tspan), int(nt), stepper, alph, n_total, group, (scale, seed, row_offset), *params)
+    Jc, means = _OCflowTrainNoisy.apply(x, net, prob, list(tspan), int(nt), stepper, alph, n_total, group,
+                                        (scale, seed, row_offset) + tuple(corr), *params)
     return Jc, [means[i] for i in range(7)]

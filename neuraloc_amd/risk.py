@@ -17,7 +17,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .noise import _OCflowTrainNoisy, _check_row_offset, _check_seed, noise_scale
+from .noise import _OCflowTrainNoisy, _check_row_offset, _check_seed, noise_corr_scales, noise_scale
 from .train import _STEPPERS, _OCflowTrain, _OCflowTrainDisturbed
 
 RISKS = ("mean", "cvar", "entropic")
@@ -132,7 +132,7 @@ class _OCflowTrainWeighted(torch.autograd.Function):
         return _OCflowTrain._adjoint(ctx, gJ, wrow=ctx.wrow)
 
 
-def _checked_call(what, x, net, prob, tspan, nt, W, sigma, seed, mask, row_offset, stepper, alph, n_total, group, weights=None):
+def _checked_call(what, x, net, prob, tspan, nt, W, sigma, seed, mask, row_offset, stepper, alph, n_total, group, weights=None, rho=None):
     """every refusal of weighted_ocflow_train / risk_ocflow_train, in front of anything that touches a device -> (alph, dist)"""
     from .ensemble import PhiEnsemble
     if isinstance(net, PhiEnsemble):
@@ -144,6 +144,8 @@ def _checked_call(what, x, net, prob, tspan, nt, W, sigma, seed, mask, row_offse
     tensors = [("x", x), ("W", W), ("weights", weights)] + [(name, p_) for name, p_ in net.named_parameters()]
     if isinstance(sigma, torch.Tensor):
         tensors.append(("sigma", sigma))
+    if isinstance(rho, torch.Tensor):
+        tensors.append(("rho", rho))
     for name, t in tensors:
         if isinstance(t, torch.Tensor) and t.dtype == torch.float64:
             raise NotImplementedError(f"{what}: {name} is float64; double precision is not supported: the weighted adjoint is single precision only "
@@ -171,6 +173,8 @@ def _checked_call(what, x, net, prob, tspan, nt, W, sigma, seed, mask, row_offse
     if W is not None:
         if seed is not None:
             raise ValueError(f"{what}: seed belongs to sigma; W is a tensor of given disturbances")
+        if rho is not None:
+            raise ValueError(f"{what}: rho belongs to sigma (the noise drawn inside the kernel); W is a tensor of given disturbances")
         if not isinstance(W, torch.Tensor):
             raise TypeError("W must be a torch.Tensor")
         if tuple(W.shape) != (int(nt), n, d):
@@ -184,7 +188,8 @@ def _checked_call(what, x, net, prob, tspan, nt, W, sigma, seed, mask, row_offse
         if seed is None:
             raise ValueError(f"{what}: sigma needs a seed")
         scale = noise_scale(sigma, nt, d, tspan, mask)
-        dist = ("noise", (scale, _check_seed(seed), _check_row_offset(row_offset)))
+        corr = () if rho is None else tuple(noise_corr_scales(sigma, rho, nt, d, tspan, mask)[1:])
+        dist = ("noise", (scale, _check_seed(seed), _check_row_offset(row_offset)) + corr)
     if weights is not None:
         if not isinstance(weights, torch.Tensor):
             raise TypeError("weights must be a torch.Tensor")
@@ -203,7 +208,7 @@ def _require_device(x, W):
 
 
 def weighted_ocflow_train(x, net, prob, tspan, nt, weights, *, W=None, sigma=None, seed=None, mask=None, row_offset=0, stepper="rk4",
-                          alph=None, n_total=None, group=None):
+                          alph=None, n_total=None, group=None, rho=None):
     """The weighted sum of the per-sample training costs of a disturbed rollout:  Jw = sum_i weights[i] J_i ,
     J_i = L_i + a0 G_i + a3 HJt_i + a4 HJfin_i + a5 HJgrad_i, differentiable w.r.t. every parameter of `net` and w.r.t. x when x requires a
     gradient (x.grad[i] = weights[i] dJ_i/dx_i).  One recording forward and one launch of the weighted adjoint of the forward's family.
@@ -211,13 +216,14 @@ def weighted_ocflow_train(x, net, prob, tspan, nt, weights, *, W=None, sigma=Non
     :param W:     nt-by-nex-by-d disturbances (disturbed_ocflow_train's), or
     :param sigma, seed, mask, row_offset: the noise of noisy_ocflow_train, drawn inside the kernel.  Exactly one of W and sigma must be given;
                   sigma=0.0 (with any seed) runs undisturbed
+    :param rho:   with sigma: a float or [d] in [0, 1), the time-correlated noise of noisy_ocflow_train(..., rho=); refused together with W
     :return: (Jw, cs) -- cs the 7 UNWEIGHTED means, as disturbed_ocflow_train logs them
     Single precision, one GPU, one network: float64 anywhere, CPU tensors, n_total / group and ensembles are refused (NotImplementedError /
     RuntimeError), before anything is launched and with every .grad untouched."""
     if not isinstance(weights, torch.Tensor):
         raise TypeError("weights must be a torch.Tensor")
     alph, dist = _checked_call("weighted_ocflow_train", x, net, prob, tspan, nt, W, sigma, seed, mask, row_offset, stepper, alph,
-                               n_total, group, weights)
+                               n_total, group, weights, rho=rho)
     _require_device(x, W)
     params = [p for _, p in net.named_parameters()]
     Jw, means, _, _, _ = _OCflowTrainWeighted.apply(x, net, prob, list(tspan), int(nt), stepper, alph, dist, weights, *params)
@@ -225,17 +231,18 @@ def weighted_ocflow_train(x, net, prob, tspan, nt, weights, *, W=None, sigma=Non
 
 
 def risk_ocflow_train(x, net, prob, tspan, nt, risk, level, *, paths=None, mix=1.0, W=None, sigma=None, seed=None, mask=None, row_offset=0,
-                      stepper="rk4", alph=None, n_total=None, group=None):
+                      stepper="rk4", alph=None, n_total=None, group=None, rho=None):
     """A risk measure of the per-sample training costs as the objective: one recording forward, risk_weights on its table, and the weighted
     adjoint as the backward -- one forward launch and one adjoint launch, the cost of a mean.
     :param risk, level, paths, mix: risk_weights' ("cvar" with 0 <= level < 1, "entropic" with level = theta > 0, or "mean"; groups of `paths`
                   consecutive rows, the layout x.repeat_interleave(paths, 0) gives; mix blends the risk with the group's mean)
-    :param W / sigma, seed, mask, row_offset, stepper, alph: as for weighted_ocflow_train
+    :param W / sigma, seed, mask, row_offset, stepper, alph, rho: as for weighted_ocflow_train
     :return: (Jr, cs, info): Jr = risk_weights' value, differentiable w.r.t. the parameters and x -- the exact gradient of the value
              (everywhere for the entropic risk; wherever no group has a tie at the VaR boundary for CVaR); cs the 7 unweighted means;
              info = dict(weights [nex], persample [nex, 7], rho [groups])
     The refusals are weighted_ocflow_train's, and risk_weights' argument checks; all of them come before anything is launched."""
-    alph, dist = _checked_call("risk_ocflow_train", x, net, prob, tspan, nt, W, sigma, seed, mask, row_offset, stepper, alph, n_total, group)
+    alph, dist = _checked_call("risk_ocflow_train", x, net, prob, tspan, nt, W, sigma, seed, mask, row_offset, stepper, alph, n_total, group,
+                               rho=rho)
     level, mix = _check_risk(risk, level, paths, mix, x.shape[0])
     _require_device(x, W)
     params = [p for _, p in net.named_parameters()]

@@ -36,6 +36,10 @@ one process.  Member e trains under per-step Brownian state disturbances sigma_e
 The seed is noise_seed << 32 | iteration for ALL members (the --noise_rng counter convention, 0 <= noise_seed < 2**32): every member meets
 the same noise realisations scaled by its own level, so the members' costs are a paired comparison across sigma.  A level of 0 is the
 undisturbed member; validation stays undisturbed.  --members with --noise stays refused: this flag is the way in.
+--noise_rho RHO (addition, with --noise SIGMA): the disturbances are correlated in time -- an AR(1) / Ornstein-Uhlenbeck path per sample and
+component with lag-one correlation 0 < RHO < 1 and the white noise's variance at every step.  --noise_rng counter:
+drawn inside the kernels (neuraloc_amd.noisy_ocflow_train(..., rho=RHO)); --noise_rng torch: neuraloc_amd.brownian_disturbances(..., rho=RHO).
+The default 0 is the white noise of --noise.  --risk takes it; not with --members, --adv or --prec double.
 --risk cvar|entropic --risk_level A [--risk_paths R] [--risk_mix M] (addition, with --noise SIGMA --noise_rng counter): risk-sensitive
 training (neuraloc_amd.risk_ocflow_train).  Every training batch is repeated R times (repeat_interleave: R noise paths
 per start) and the objective is the risk of each start's R costs -- CVaR at level A, or the entropic risk with theta = A -- blended with their
@@ -99,6 +103,8 @@ _FLAGS = [
     ("noise_seed", int, 0, "(addition) seed of the disturbances for --noise (rank is added)"),
     ("noise_rng", str, "torch", "(addition) torch: every rank draws its shard's disturbances with torch.randn; counter: they are drawn inside "
                                 "the kernels from (noise_seed, iteration, global row) (neuraloc_amd.noisy_ocflow_train), the same on any number of ranks"),
+    ("noise_rho", float, 0.0, "(addition, with --noise) 0 <= RHO < 1: time-correlated (Ornstein-Uhlenbeck) disturbances of lag-one correlation RHO "
+                              "(neuraloc_amd.noisy_ocflow_train / brownian_disturbances with rho=RHO); 0: the white noise of --noise"),
     ("adv", float, 0.0, "(addition) EPS > 0: min-max training against the worst disturbance path of norm <= EPS per start "
                         "(neuraloc_amd.adversarial_step / pgd_ocflow_train); validation stays undisturbed; single precision only; not with --noise"),
     ("adv_mode", str, "free", "(addition) free: one persistent W per rank, one ascent step per Adam step from the joint adjoint; "
@@ -139,7 +145,25 @@ def parse_args(argv=None):
     a.alph = [float(v) for v in a.alph.split(",")]
     if a.new_alph is not None:
         a.new_alph = [float(v) for v in a.new_alph.split(",")]
+    noise_rho_refusals(a)
     return a
+
+
+def noise_rho_refusals(args):
+    """--noise_rho: everything the time-correlated noise does not take, refused by the parser itself"""
+    if args.noise_rho == 0:
+        return
+    if not 0.0 <= args.noise_rho < 1.0:                    # (a NaN fails both comparisons)
+        raise SystemExit("--noise_rho RHO must be a number with 0 <= RHO < 1")
+    if not args.noise > 0:
+        raise SystemExit("--noise_rho needs --noise SIGMA > 0: it shapes that noise in time")
+    if args.members is not None or args.members_alph is not None or args.members_family != "lane" or args.members_sigma is not None \
+            or args.members_risk is not None or args.members_risk_level is not None or args.members_adv is not None:
+        raise SystemExit("--noise_rho excludes --members: the time-correlated noise takes one network")
+    if args.adv > 0:
+        raise SystemExit("--noise_rho excludes --adv: one disturbance per rollout")
+    if args.prec == "double":
+        raise SystemExit("--noise_rho runs in single precision only (the double-precision rollout takes no disturbance)")
 
 
 def _level_in_range(risk, level):
@@ -483,6 +507,7 @@ def main(argv=None):
     noise_gen = torch.Generator(device=dev).manual_seed(args.noise_seed + rank) if args.noise > 0 and not noise_counter else None
     # --adv, free mode: one W per rank, kept across the iterations on a batch (zeroed with every new batch)
     adv_W = torch.zeros(args.nt, x0.shape[0], d, device=dev, requires_grad=True) if args.adv > 0 and args.adv_mode == "free" else None
+    rho_kw = {"rho": args.noise_rho} if args.noise_rho != 0 else {}     # --noise_rho 0: the white path and its entry points
     best_loss, best_params, total = float("inf"), None, 0.0
     net.train()
     prob.train()
@@ -492,12 +517,12 @@ def main(argv=None):
         if args.risk is not None:                         # R noise paths per start, rows [i R, (i + 1) R): the risk of each start's costs
             Jc, cs, _ = na.risk_ocflow_train(x0.repeat_interleave(args.risk_paths, 0), net, prob, tspan, args.nt, args.risk, args.risk_level,
                                              paths=args.risk_paths, mix=args.risk_mix, sigma=args.noise,
-                                             seed=(args.noise_seed << 32) | itr, stepper="rk4", alph=net.alph)
+                                             seed=(args.noise_seed << 32) | itr, stepper="rk4", alph=net.alph, **rho_kw)
         elif noise_counter:
             Jc, cs = na.noisy_ocflow_train(x0, net, prob, tspan, args.nt, args.noise, (args.noise_seed << 32) | itr, "rk4", net.alph,
-                                           row_offset=lo, group=True if dist else None)
+                                           row_offset=lo, group=True if dist else None, **rho_kw)
         elif noise_gen is not None:
-            W = na.brownian_disturbances(args.nt, x0.shape[0], d, args.noise, tspan=tspan, generator=noise_gen, device=dev)
+            W = na.brownian_disturbances(args.nt, x0.shape[0], d, args.noise, tspan=tspan, generator=noise_gen, device=dev, **rho_kw)
             Jc, cs = na.disturbed_ocflow_train(x0, net, prob, tspan, args.nt, W, "rk4", net.alph, group=True if dist else None)
         elif adv_W is not None:
             Jc, cs = na.adversarial_step(x0, net, prob, tspan, args.nt, adv_W, args.adv, 2.5 * args.adv / args.adv_steps, stepper="rk4",
