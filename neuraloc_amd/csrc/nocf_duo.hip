@@ -262,6 +262,15 @@ __device__ __forceinline__ void mfma_v(f32x4& acc, float w, float b) {
 #define DU_SLOWNAP 8               // 64-clock quanta between failed polls when a group has several tiles (du_spin)
 #endif
 #define DU_PIN(v) asm volatile("" : "+s"(v))
+// A lane mask (a per-lane compare whose operands never change: lane < 40, 4 lane + e < d, ...) and a wave-uniform test (row block < r, stage == last) are
+// loop-invariant, so the compiler forms each ONCE at kernel entry and holds it in an SGPR pair across the rollout: some thirty pairs, which is what
+// pushed the scalar file over its limit -- the pairs were spilled to VGPR lanes and every use in the tile body re-read them (two v_readlane and a
+// wait state per mask, VALU instructions that the co-resident role's MFMAs have to make room for).  A serial section instead takes an OPAQUE copy
+// of the lane index / scalar it tests (an empty asm the optimiser cannot look through or move out of the loop) and forms its masks where it uses
+// them: one v_cmp (or s_cmp) each, no register held between tiles.
+// (HEREM: a constant of the kernel -- the instantiations in which this measured faster, see there)
+#define DU_HERE_V(v) do { if (HEREM) asm volatile("" : "+v"(v)); } while (0)
+#define DU_HERE_S(v) do { if (HEREM) asm volatile("" : "+s"(v)); } while (0)
 
 struct DCtx {
     __amdgpu_buffer_rsrc_t xrs;    // this group's exchange area
@@ -336,13 +345,19 @@ __device__ __forceinline__ void du_wait_end(DCtx& g, const DWait& w, int lane) {
 __device__ __forceinline__ u32x4 du_ld(const DCtx& g, int vbyte, int sbyte) {
     return __builtin_amdgcn_raw_buffer_load_b128(g.xrs, vbyte, sbyte, 16 /*sc1: not through the CU's L1*/);
 }
+// "does this group keep its payloads in the XCD's L2?", formed HERE from the integer: one s_cmp and one scalar branch per store.  (Held as a boolean
+// across the rollout it became an SGPR pair, and every store six scalar instructions of mask bookkeeping.)
+// (PINF: the instantiations in which that measured faster -- the forward's one-tile launches; the others, and the adjoint, test g.fast as they did)
+template <bool PINF>
+__device__ __forceinline__ bool du_fast(const DCtx& g) { int f = g.fast; if (PINF) DU_PIN(f); return f != 0; }
+template <bool PINF = false>
 __device__ __forceinline__ void du_st(const DCtx& g, int vbyte, int sbyte, f32x4 v) {
     u32x4 u;
     u.x = __float_as_uint(v[0]); u.y = __float_as_uint(v[1]); u.z = __float_as_uint(v[2]); u.w = __float_as_uint(v[3]);
     // (round 6: the guard sits in the write-through branch only -- the branch where tools/store_hazard_check.py finds overwritten store data
     // without it, 24 places: the U store followed by the tanh's v_rcp.  A guard behind EVERY store pinned the stores between the written-out MFMAs
     // and cost 0.5 %; build() runs the checker over the ISA of every build and refuses a library with a finding)
-    if (g.fast) __builtin_amdgcn_raw_buffer_store_b128(u, g.xrs, vbyte, sbyte, DU_XST_AUX /*stays in the XCD's L2*/);
+    if (du_fast<PINF>(g)) __builtin_amdgcn_raw_buffer_store_b128(u, g.xrs, vbyte, sbyte, DU_XST_AUX /*stays in the XCD's L2*/);
     else {
         // (two wait states directly behind the store, fenced against the scheduler on both sides: an asm that merely NAMES the data as an input
         // lets the compiler rebuild a constant payload -- the sentinel -- in registers that overlap the store's, in between)
@@ -352,9 +367,10 @@ __device__ __forceinline__ void du_st(const DCtx& g, int vbyte, int sbyte, f32x4
         __builtin_amdgcn_sched_barrier(0);
     }
 }
+template <bool PINF = false>
 __device__ __forceinline__ void du_st_sent(const DCtx& g, int vbyte, int sbyte) {
     const f32x4 sv = {__uint_as_float(DU_SENT), __uint_as_float(DU_SENT), __uint_as_float(DU_SENT), __uint_as_float(DU_SENT)};
-    du_st(g, vbyte, sbyte, sv);
+    du_st<PINF>(g, vbyte, sbyte, sv);
 }
 __device__ __forceinline__ bool du_bad(const u32x4& v) {
     const unsigned a = v.x > v.y ? v.x : v.y, b = v.z > v.w ? v.z : v.w;
@@ -683,6 +699,13 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
     // the owner's step in two parts (own_state_split / own_book): where a group has ONE tile -- the fine geometry, and the one-tile launches of the
     // 256-wide geometry (MODE 1 there: n <= 1024) -- measured; with two tiles per group it loses in every geometry
     constexpr bool OSPLIT = GM == DU_GMAX || (GM == 4 && MODE == 1);
+    // (round 7, the serial sections' instruction streams: both measured per instantiation on one lease, profiles/duo_streams/ab.txt, and kept where
+    // they won.)  HEREM: lane masks and wave-uniform tests are formed where they are used instead of being held in SGPR pairs across the rollout
+    // (DU_HERE_V) -- launches with several tiles per group: n = 1024 -1.2 %, but +1.2 % with one tile per group (512 rows; 128 rows 0).
+    // PINF: the exchange stores test the group's "payloads stay in L2" flag as an integer pinned at the store (du_fast) -- one-tile launches: 512 rows
+    // -2.5 %, 128 rows -1.9 %, but +3 % at n = 1024.
+    constexpr bool HEREM = MODE == 0 && GM != DU_GMAX;
+    constexpr bool PINF = !HEREM;
     constexpr bool FLAGS = ONE || GM != DU_G;                   // the local owner's "about to publish" flag for the stage-state gatherers (see own_state)
     const int d = dp.d;
     const float hN = dp.hN;
@@ -742,7 +765,8 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
         if (lane == 0) lds[0] = __all(v == xcc) ? 1.f : 0.f;
     }
     __syncthreads();
-    g.fast = dp.fast && lds[0] != 0.f;
+    // (an INTEGER in a scalar register -- the bits of 1.f or +0.f --, provably wave-uniform: every store's `if (fast)` is a scalar compare and branch, see du_st)
+    { int fv = dp.fast ? __builtin_amdgcn_readfirstlane(__float_as_int(lds[0])) : 0; DU_PIN(fv); g.fast = fv; }
     __syncthreads();
 
     const int nstage = (ra.stepper == NOCF_RK4) ? 4 : 1;
@@ -848,21 +872,17 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
 
         // the owner's step, state part: gradient of evaluation e-1 -> RK update -> stage state of evaluation e published.
         // Leaves this lane's share of sum p^2 (q0) and its candidate for dPhi/dt (gdv) for the cost part.
-        auto own_state = [&](int s, int e, float hs, int pst, int pk, float t_pub, bool have, u32x4 (&pv)[G]) {
+        // (rk_wa, cx: the stage's weights, formed once per evaluation by the caller -- see rk_weights)
+        auto own_state = [&](int s, int e, float hs, int pst_, int pk, float t_pub, bool have, u32x4 (&pv)[G], float rk_wa, float cx) {
             const int t = s / SPM, j = s % SPM;
             const int parG = (e - 1) & 1, parS = e & 1;
+            int pst = pst_, pio = pi, dd = d; DU_HERE_S(pst); DU_HERE_V(pio); DU_HERE_S(dd);      // (the tests on them are formed here: DU_HERE_V)
             const bool rk_last = (pst == nstage - 1);
-            const float rk_wa = (nstage == 1) ? 1.f : ((pst == 0 || pst == 3) ? c16 : c26);
-            const float rk_wx = (pst < 2) ? 0.5f : 1.f;
             const int sbase = DAT + s * DS_STRIDE;
             DTL(40 * t + 0);
             const float4 z04 = L4[(sbase + DS_Z0 + pi) >> 2], zA4 = L4[(sbase + DS_ZA + pi) >> 2];      // (in flight while the partials are polled)
             if (!have) g_request(s, parG, pv);
-            unsigned qa = 0, qb = 0;
-            if (pst != nstage) {   // the cost scalars of this sample ride along (consumed by own_costs, behind P2): their round trip is off the critical path
-                const auto v2 = __builtin_amdgcn_raw_buffer_load_b64(g.xrs, 0, xQ + (((((e - 1) % 3) * NT + t) * G + member) * (2 * SPM) + 2 * j) * 4, 16);
-                qa = v2[0]; qb = v2[1];
-            }
+            // (the cost scalars of this sample no longer ride along: own_costs takes the answer of the request issued behind P2, so nothing read them)
             const f32x4 gs = gather_g(s, parG, true, pv);
             // (round 5) "the stage state of this tile is about to be published": the workgroup's waves that gather it start polling NOW -- one
             // owner's step and one store + landing later the payload is there, so a poll is in flight when it lands (the shortest hop there
@@ -871,11 +891,11 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
             DTL(40 * t + 1);
             float q0 = 0.f;
 #pragma unroll
-            for (int e4 = 0; e4 < 4; ++e4) if (pact && pi + e4 < d) q0 += gs[e4] * gs[e4];
+            for (int e4 = 0; e4 < 4; ++e4) if (pact && pio + e4 < dd) q0 = __builtin_fmaf(gs[e4], gs[e4], q0);      // (written out: the sum's bits must not hang on what the optimiser fuses)
             const float gdv = pd_e == 0 ? gs[0] : (pd_e == 1 ? gs[1] : (pd_e == 2 ? gs[2] : gs[3]));
-            const bool pctrl = (pst == nstage);                   // the evaluation just answered was a control evaluation (intermediates)
-            const long orow = rr.row0 + own_row(t, j);            // this sample's row in the caller's batch
-            const bool orow_ok = own_row(t, j) < ra.n;
+            const bool pctrl = ZF && (pst == nstage);             // the evaluation just answered was a control evaluation (intermediates only)
+            const long orow = ZF ? rr.row0 + own_row(t, j) : 0;   // this sample's row in the caller's batch
+            const bool orow_ok = ZF && own_row(t, j) < ra.n;
             if (pact) {
                 const float z0[4] = {z04.x, z04.y, z04.z, z04.w};
                 float zA[4] = {zA4.x, zA4.y, zA4.z, zA4.w}, zn[4];
@@ -884,18 +904,17 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
                 //   controls only:  x = z0 (the state stands);   last stage:  x = z_{k+1} = (z0 | zA) + wa K;   else:  zA += wa K, x = z0 + wx K)
                 const bool xFromA = !pctrl && rk_last && nstage != 1;      // x starts from the accumulator
                 const bool accum = !pctrl && !rk_last;                     // the accumulator takes this stage
-                const float cx = pctrl ? 0.f : (rk_last ? rk_wa : rk_wx);
 #pragma unroll
                 for (int e4 = 0; e4 < 4; ++e4) {
-                    const int i = pi + e4;
+                    const int i = pio + e4;
                     const float K = hs * -gs[e4];                          // dx = -grad_p H = -p (src/OCflow.py:134, :143-184)
                     const float xb = xFromA ? zA[e4] : z0[e4];
-                    const float x_ = pctrl ? z0[e4] : xb + cx * K;
-                    const float an = (pst == 0 ? z0[e4] : zA[e4]) + rk_wa * K;
+                    const float x_ = pctrl ? z0[e4] : __builtin_fmaf(cx, K, xb);            // (written out, like the accumulator: see q0)
+                    const float an = __builtin_fmaf(rk_wa, K, pst == 0 ? z0[e4] : zA[e4]);
                     zA[e4] = accum ? an : zA[e4];
                     zn[e4] = (rk_last && !pctrl) ? x_ : z0[e4];
-                    xs[e4] = (i < d) ? x_ : (i == d ? t_pub : 0.f);
-                    if (i >= d) { zn[e4] = 0.f; zA[e4] = 0.f; }
+                    xs[e4] = (i < dd) ? x_ : (i == dd ? t_pub : 0.f);
+                    if (i >= dd) { zn[e4] = 0.f; zA[e4] = 0.f; }
                 }
                 if (ZF && orow_ok) {
                     // intermediates (src/OCflow.py:37-55), time-major: the state at the end of step pk; the controls -p at (z_{k+1}, t_k)
@@ -908,8 +927,8 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
                     }
                 }
                 const int lp = (psl * 16 + SPM * member + j) * 16 + pmt * 1024;
-                du_st(g, lp, xS + ((parS * NT + t) * DU_KBD) * 1024, xs);
-                du_st_sent(g, lp, xS + (((parS ^ 1) * NT + t) * DU_KBD) * 1024);
+                du_st<PINF>(g, lp, xS + ((parS * NT + t) * DU_KBD) * 1024, xs);
+                du_st_sent<PINF>(g, lp, xS + (((parS ^ 1) * NT + t) * DU_KBD) * 1024);
                 if (!pctrl) {
                     if (rk_last) L4[(sbase + DS_Z0 + pi) >> 2] = make_float4(zn[0], zn[1], zn[2], zn[3]);
                     else L4[(sbase + DS_ZA + pi) >> 2] = make_float4(zA[0], zA[1], zA[2], zA[3]);
@@ -926,10 +945,10 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
             }
             DTL(40 * t + 2);
             // (behind the store: off the critical path) what the cost part needs, parked in LDS -- P1 and P2 run between the two
-            if (pst != nstage) {
+            if (!pctrl) {
                 const float sp2 = sum64(q0);
                 const float gt = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(gdv), pd_lane));
-                if (lane == 0) L4[(sbase + DS_OC) >> 2] = make_float4(sp2, gt, __uint_as_float(qa), __uint_as_float(qb));
+                if (lane == 0) L4[(sbase + DS_OC) >> 2] = make_float4(sp2, gt, 0.f, 0.f);
             }
         };
         // (round 6) The owner's step in TWO parts, for the FINE geometry (one tile per group, one own sample per member: OSPLIT).  On the path partial
@@ -947,9 +966,10 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
             const float rk_wa = (nstage == 1) ? 1.f : ((pst == 0 || pst == 3) ? c16 : c26);
             const float rk_wx = (pst < 2) ? 0.5f : 1.f;
             const int sbase = DAT + s * DS_STRIDE;
-            const bool pctrl = (pst == nstage);
+            const bool pctrl = ZF && (pst == nstage);
             const bool xFromA = !pctrl && rk_last && nstage != 1;
             const float cx = pctrl ? 0.f : (rk_last ? rk_wa : rk_wx);
+            int pio = pi, dd = d; DU_HERE_V(pio); DU_HERE_S(dd);      // (the range tests below are formed here: see DU_HERE_V)
             DTL(40 * t + 0);
             const float4 b4 = L4[(sbase + (xFromA ? DS_ZA : DS_Z0) + pi) >> 2];                            // (in flight while the partials are polled)
             g_request(s, parG, pv);
@@ -961,14 +981,14 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
                 f32x4 xs;
 #pragma unroll
                 for (int e4 = 0; e4 < 4; ++e4) {
-                    const int i = pi + e4;
+                    const int i = pio + e4;
                     const float K = hs * -gs[e4];
-                    const float x_ = pctrl ? xb[e4] : xb[e4] + cx * K;
-                    xs[e4] = (i < d) ? x_ : (i == d ? t_pub : 0.f);
+                    const float x_ = pctrl ? xb[e4] : __builtin_fmaf(cx, K, xb[e4]);
+                    xs[e4] = (i < dd) ? x_ : (i == dd ? t_pub : 0.f);
                 }
                 const int lp = (psl * 16 + SPM * member + j) * 16 + pmt * 1024;
-                du_st(g, lp, xS + ((parS * NT + t) * DU_KBD) * 1024, xs);
-                du_st_sent(g, lp, xS + (((parS ^ 1) * NT + t) * DU_KBD) * 1024);
+                du_st<PINF>(g, lp, xS + ((parS * NT + t) * DU_KBD) * 1024, xs);
+                du_st_sent<PINF>(g, lp, xS + (((parS ^ 1) * NT + t) * DU_KBD) * 1024);
                 L4[(sbase + DS_XS + pi) >> 2] = make_float4(xs[0], xs[1], xs[2], xs[3]);
                 L4[(sbase + DS_AZC + pi) >> 2] = make_float4(gs[0], gs[1], gs[2], gs[3]);                   // parked for own_book
             }
@@ -981,31 +1001,32 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
             const float rk_wa = (nstage == 1) ? 1.f : ((pst == 0 || pst == 3) ? c16 : c26);
             const float rk_wx = (pst < 2) ? 0.5f : 1.f;
             const int sbase = DAT + s * DS_STRIDE;
-            const bool pctrl = (pst == nstage);
+            const bool pctrl = ZF && (pst == nstage);
             const bool xFromA = !pctrl && rk_last && nstage != 1;
             const bool accum = !pctrl && !rk_last;
             const float cx = pctrl ? 0.f : (rk_last ? rk_wa : rk_wx);
             const float4 z04 = L4[(sbase + DS_Z0 + pi) >> 2], zA4 = L4[(sbase + DS_ZA + pi) >> 2], g4 = L4[(sbase + DS_AZC + pi) >> 2];
             const f32x4 gs = {g4.x, g4.y, g4.z, g4.w};
+            int pio = pi, dd = d; DU_HERE_V(pio); DU_HERE_S(dd);      // (the range tests below are formed here: see DU_HERE_V)
             float q0 = 0.f;
 #pragma unroll
-            for (int e4 = 0; e4 < 4; ++e4) if (pact && pi + e4 < d) q0 += gs[e4] * gs[e4];
+            for (int e4 = 0; e4 < 4; ++e4) if (pact && pio + e4 < dd) q0 = __builtin_fmaf(gs[e4], gs[e4], q0);      // (written out: the sum's bits must not hang on what the optimiser fuses)
             const float gdv = pd_e == 0 ? gs[0] : (pd_e == 1 ? gs[1] : (pd_e == 2 ? gs[2] : gs[3]));
-            const long orow = rr.row0 + own_row(t, j);
-            const bool orow_ok = own_row(t, j) < ra.n;
+            const long orow = ZF ? rr.row0 + own_row(t, j) : 0;
+            const bool orow_ok = ZF && own_row(t, j) < ra.n;
             if (pact) {
                 const float z0[4] = {z04.x, z04.y, z04.z, z04.w};
                 float zA[4] = {zA4.x, zA4.y, zA4.z, zA4.w}, zn[4];
 #pragma unroll
                 for (int e4 = 0; e4 < 4; ++e4) {
-                    const int i = pi + e4;
+                    const int i = pio + e4;
                     const float K = hs * -gs[e4];
                     const float xb = xFromA ? zA[e4] : z0[e4];
-                    const float x_ = pctrl ? z0[e4] : xb + cx * K;
-                    const float an = (pst == 0 ? z0[e4] : zA[e4]) + rk_wa * K;
+                    const float x_ = pctrl ? z0[e4] : __builtin_fmaf(cx, K, xb);            // (written out, like the accumulator: see q0)
+                    const float an = __builtin_fmaf(rk_wa, K, pst == 0 ? z0[e4] : zA[e4]);
                     zA[e4] = accum ? an : zA[e4];
                     zn[e4] = (rk_last && !pctrl) ? x_ : z0[e4];
-                    if (i >= d) { zn[e4] = 0.f; zA[e4] = 0.f; }
+                    if (i >= dd) { zn[e4] = 0.f; zA[e4] = 0.f; }
                 }
                 if (ZF && orow_ok) {
                     if (pctrl) {
@@ -1028,7 +1049,7 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
                     rec_row(ra.act + 4 * ra.actRows * MW + (((long)(e - 2)) * rr.n_total + rr.row0 + own_row(t, j)) * (d + 1), pi, gs[0], gs[1], gs[2], gs[3]);
             }
             sp2 = 0.f; gt = 0.f;
-            if (pst != nstage) {
+            if (!pctrl) {
                 sp2 = sum64(q0);
                 gt = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(gdv), pd_lane));
             }
@@ -1036,11 +1057,10 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
         // ... cost part (off the critical path: it runs behind P1, while the u0 exchange travels): sum p^2, dPhi/dt, the x-only terms
         // from role B -> the four cost integrals of evaluation e-1
         // (pre: qa_ / qb_ hold the answer of a request issued just before -- DU_X_SWAP -- instead of the one that rode with the partial gradients)
-        auto own_costs = [&](int s, int e, float hs, int pst, int pk, bool pre = false, unsigned qa_ = 0u, unsigned qb_ = 0u, float sp2_ = 0.f, float gt_ = 0.f) {
+        auto own_costs = [&](int s, int e, float hs, int pst_, int pk, float rk_wa, bool pre = false, unsigned qa_ = 0u, unsigned qb_ = 0u, float sp2_ = 0.f, float gt_ = 0.f) {
             const int t = s / SPM, j = s % SPM;
-            const int parG = (e - 1) & 1;
+            int pst = pst_, ln = lane; DU_HERE_S(pst); DU_HERE_V(ln);      // (see DU_HERE_V)
             const bool rk_last = (pst == nstage - 1);
-            const float rk_wa = (nstage == 1) ? 1.f : ((pst == 0 || pst == 3) ? c16 : c26);
             const int sbase = DAT + s * DS_STRIDE;
             float4 oc = make_float4(sp2_, gt_, 0.f, 0.f);            // (OSPLIT: own_book hands sum p^2 and dPhi/dt over in registers)
             if (!OSPLIT) oc = L4[(sbase + DS_OC) >> 2];
@@ -1060,7 +1080,7 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
                     if (du_spin(g, spins, DUK_Q)) break;
                 }
             }
-            if (lane < 4) {
+            if (ln < 4) {
                 // calcLHQW of the point-agent problems (Cross2D.py:73-87 returns the scaled Q, SwarmTraj.py:71-87 the raw one)
                 const float Qs = cAlphQ * q_;
                 const float Wv = cWantW ? w_ : 0.f;
@@ -1069,15 +1089,23 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
                 const float H = -Lg + sp2;
                 if (REC && ra.tapeSc && lane == 0 && own_row(t, j) < ra.n)      // tape: dPhi/dt - H and the x-only terms of evaluation e-1 (index e-2)
                     *reinterpret_cast<float4*>(ra.tapeSc + (((long)(e - 2)) * rr.n_total + rr.row0 + own_row(t, j)) * 4) = make_float4(gt - H, q_, w_, 0.f);
-                const float val = (lane == 0) ? Lg : (lane == 1) ? fabsf(gt - H) : (lane == 2) ? (PD == 2 ? Qs : q_) : Wv;
+                const float val = (ln == 0) ? Lg : (ln == 1) ? fabsf(gt - H) : (ln == 2) ? (PD == 2 ? Qs : q_) : Wv;
                 const float K = hs * val;
                 float* cz = lds + sbase + DS_CZ + lane;                     // [0..3] value, [4..7] RK accumulator
                 const float cz0 = cz[0], czA = cz[4];
+                // (ONE rounded product for both cases and a separate add -- what this section has always computed; written out so that the integrals' bits
+                // do not hang on whether the optimiser happens to share the product between the branches or fuses it into each)
+                float wK, cn, ca;
+                {
+#pragma clang fp contract(off)
+                    wK = rk_wa * K;
+                    cn = (nstage == 1 ? cz0 : czA) + wK;
+                    ca = (pst == 0 ? cz0 : czA) + wK;
+                }
                 if (rk_last) {
-                    const float cn = (nstage == 1 ? cz0 : czA) + rk_wa * K;
                     cz[0] = cn;
                     if (ZF && own_row(t, j) < ra.n) ra.zFull[((long)(pk + 1) * rr.n_total + rr.row0 + own_row(t, j)) * (d + 4) + d + lane] = cn;
-                } else cz[4] = (pst == 0 ? cz0 : czA) + rk_wa * K;
+                } else cz[4] = ca;
             }
             DTL(40 * t + 3);
         };
@@ -1086,6 +1114,7 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
         // LDS reads in batches that are in flight together (a dependent read costs ~130 cycles when waited for alone).
         auto azc_step = [&](int s, bool fin) {
             const int sbase = DAT + s * DS_STRIDE;
+            int rq = rA; DU_HERE_S(rq);                          // (the four row-block tests below are scalar compares formed here: see DU_HERE_V)
             {
                 const int q = lane >> 2, part = lane & 3;            // row of A, quarter of the dims (10 float4 each)
                 const int ia = ((DA_A + q * DU_DP) >> 2) + part * 10, ix = ((sbase + DS_XS) >> 2) + part * 10;
@@ -1107,7 +1136,7 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
                 float o[4] = {c4.x, c4.y, c4.z, c4.w};
 #pragma unroll
                 for (int qb = 0; qb < 16; qb += 4) {                 // rows of A beyond r are zero
-                    if (qb < rA) {
+                    if (qb < rq) {
                         const float4 z4 = L4[(sbase + DS_ZQ + qb) >> 2];
                         float4 a[4];
 #pragma unroll
@@ -1136,7 +1165,7 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
             const int t = s / SPM, j = s % SPM, sbase = DAT + s * DS_STRIDE;
             if (pact) {
                 const float4 x4 = L4[(sbase + DS_XS + pi) >> 2];
-                du_st(g, (psl * 16 + SPM * member + j) * 16 + pmt * 1024, xS + ((1 * NT + t) * DU_KBD) * 1024, (f32x4){x4.x, x4.y, x4.z, x4.w});
+                du_st<PINF>(g, (psl * 16 + SPM * member + j) * 16 + pmt * 1024, xS + ((1 * NT + t) * DU_KBD) * 1024, (f32x4){x4.x, x4.y, x4.z, x4.w});
             }
             if (REC && ra.sAll && own_row(t, j) < ra.n)
                 for (int i = lane; i <= d; i += 64) ra.sAll[(rr.row0 + own_row(t, j)) * (d + 1) + i] = lds[sbase + DS_XS + i];
@@ -1159,6 +1188,10 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
                 ++e;
                 const int par = e & 1;
                 DTL_EPOCH(e);
+                // rk_weights: the weights of the stage just answered (p_st), formed once per evaluation: its share of the step's sum, and the factor of K in
+                // the next stage state (the last stage: the same share)
+                const float p_wa = (nstage == 1) ? 1.f : ((p_st == 0 || p_st == 3) ? c16 : c26);
+                const float p_cx = (p_st == nstage - 1) ? p_wa : ((p_st < 2) ? 0.5f : 1.f);
                 // time of this evaluation: stepRK4's t0, t0 + h/2, t0 + h/2, t0 + h in double (src/OCflow.py:157-184); the terminal
                 // evaluation runs at tspan[1] (src/OCflow.py:62); the control evaluation of intermediates at the step's START time with the
                 // step's END state (src/OCflow.py:51-55: tk is advanced behind it)
@@ -1168,7 +1201,7 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
                     int sown = -1;                                  // this wave's own sample of the tile, if any: sample s belongs to wave s & 3
 #pragma unroll
                     for (int j = 0; j < SPM; ++j) if (((SPM * t + j) & 3) == wave) sown = SPM * t + j;
-                    if (e > 1 && sown >= 0) { if (OSPLIT) own_state_split(sown, e, p_hs, p_st, p_k, (float)te, pf); else own_state(sown, e, p_hs, p_st, p_k, (float)te, false, pf); }
+                    if (e > 1 && sown >= 0) { if (OSPLIT) own_state_split(sown, e, p_hs, p_st, p_k, (float)te, pf); else own_state(sown, e, p_hs, p_st, p_k, (float)te, false, pf, p_wa, p_cx); }
                     // ================= P1: o = K0[H_c,:] s + b0 ; u0 = sigma(o), tanh(o) =================
                     DTL(40 * t + 4);
                     // (the two waves that own nothing of this tile fetch the stage states: the owners have just stored theirs, and a load issued
@@ -1188,7 +1221,7 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
                         if (SPM == 2) { if (sown < 0) { wait_owner(); du_gather2<DU_KBD>(g, (wave ^ (wave >> 1)) & 1, lane, xS + ((par * NT + t) * DU_KBD) * 1024, DA_SF >> 2, DUK_S); } }
                         else if (SPM == 4) du_gather<DU_KBD>(g, wave, lane, xS + ((par * NT + t) * DU_KBD) * 1024, DA_SF >> 2, DUK_S);      // (every wave is an owner)
                         else { const int wh = ((wave - (t & 3)) & 3) - 1; if (wh >= 0 && wh < 2) { wait_owner(); du_gather2<DU_KBD>(g, wh, lane, xS + ((par * NT + t) * DU_KBD) * 1024, DA_SF >> 2, DUK_S); } }
-                    } else du_gather<DU_KBD>(g, wave, lane, xS + ((par * NT + t) * DU_KBD) * 1024, DA_SF >> 2, DUK_S);
+                    } else { int w1 = wave; DU_HERE_S(w1); du_gather<DU_KBD>(g, w1, lane, xS + ((par * NT + t) * DU_KBD) * 1024, DA_SF >> 2, DUK_S); }      // (the first evaluation only: its share tests are not held across the rollout)
                     DTLB(40 * t + 13);
                     __syncthreads();
                     DTL(40 * t + 5);
@@ -1201,7 +1234,7 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
                                 // done), a whole product + hop earlier than in the default form: P2 is only 64 MFMAs long there and its vmcnt(0) in front
                                 // of the V store would wait for these acknowledgements (H1 is unchanged: that wait still lies between them and V)
                                 const int fr = (((par ^ 1) * NT + t) * KBM + MTM * member + ft) * 1024;
-                                if (kh == 0) { du_st_sent(g, vb, xU + fr); du_st_sent(g, vb, xV + fr); } else du_st_sent(g, vb, xT + fr);
+                                if (kh == 0) { du_st_sent<PINF>(g, vb, xU + fr); du_st_sent<PINF>(g, vb, xV + fr); } else du_st_sent<PINF>(g, vb, xT + fr);
                             }
                         });
                         if (KS > 1) {       // the two halves of the contraction meet (fixed order: lower + upper k-blocks)
@@ -1218,8 +1251,8 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
                         for (int e4 = 0; e4 < 4; ++e4) { float s_, t_; act_pair(acc[e4] + b0v[e4], s_, t_); sg[e4] = s_; th[e4] = t_; }
                         const int fo = ((par * NT + t) * KBM + MTM * member + ft) * 1024;
                         // (fine form: both waves of a feature tile hold o; one publishes sigma(o), the other tanh(o))
-                        if (KS == 1 || kh == 0) du_st(g, vb, xU + fo, sg);
-                        if (KS == 1 || kh == 1) du_st(g, vb, xT + fo, th);
+                        if (KS == 1 || kh == 0) du_st<PINF>(g, vb, xU + fo, sg);
+                        if (KS == 1 || kh == 1) du_st<PINF>(g, vb, xT + fo, th);
                         if (REC && ra.act && (!fin || ra.tapeSc)) {    // activation record: 4 features of sample lane & 15 (64-byte runs per sample)
                             const int ro = rec_off(t);
                             if (KS == 1 || kh == 0) rec_store(rec_block(0, e - 1), ro, sg[0], sg[1], sg[2], sg[3]);
@@ -1246,7 +1279,7 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
                         const int fr = (((par ^ 1) * NT + t) * KBM + MTM * member + ft) * 1024;
                         float4 b1s, wvs;
                         auto resets = [&](int kb) {
-                            if (KS == 1 && kb == 1) { du_st_sent(g, vb, xU + fr); du_st_sent(g, vb, xT + fr); du_st_sent(g, vb, xV + fr); }      // (fine form: in P1)
+                            if (KS == 1 && kb == 1) { du_st_sent<PINF>(g, vb, xU + fr); du_st_sent<PINF>(g, vb, xT + fr); du_st_sent<PINF>(g, vb, xV + fr); }      // (fine form: in P1)
                             if (kb == KBW - 3) { b1s = L4[((DA_VEC + 64) >> 2) + 4 * ft + slot]; wvs = L4[((DA_VEC + 128) >> 2) + 4 * ft + slot]; }
                         };
                         f32x4 acc = du_gemm_lds<KBW, true>(W, (DA_UF >> 2) + kh * KBW * 64 + lane, resets);
@@ -1272,7 +1305,7 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
                         asm volatile("" : "+v"(v));
                         DTL(40 * t + 17);
 #endif
-                        if (KS == 1 || kh == 0) du_st(g, vb, xV + ((par * NT + t) * KBM + MTM * member + ft) * 1024, v);
+                        if (KS == 1 || kh == 0) du_st<PINF>(g, vb, xV + ((par * NT + t) * KBM + MTM * member + ft) * 1024, v);
                         if (PRED) du_anchor(g, t, lane);        // (predictive waiting: this wave's next waits for tile t count from here)
                         DTL(40 * t + 12);
                         if (REC && ra.act && (!fin || ra.tapeSc) && (KS == 1 || kh == 0))      // activation record: tanh(q)
@@ -1292,7 +1325,7 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
                             if (lane < 16) {
                                 const unsigned pu = __float_as_uint(pr);
                                 const int off = xP + (((t * G + member) * MTM + ft) * 16 + lane) * 4;
-                                if (g.fast) __builtin_amdgcn_raw_buffer_store_b32(pu, g.xrs, off, 0, 0);
+                                if (du_fast<PINF>(g)) __builtin_amdgcn_raw_buffer_store_b32(pu, g.xrs, off, 0, 0);
                                 else __builtin_amdgcn_raw_buffer_store_b32(pu, g.xrs, off, 0, 16);
                             }
                         }
@@ -1304,7 +1337,7 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
                     if (sown >= 0) {
                         // z / A^T z FIRST (round 6): it is vector work, and the SIMD's ALU is free while v travels (role B polls for it); the cost
                         // part is mostly the wait for role B's cost scalars, requested here so that the round trip runs under that work
-                        const bool oc = e > 1 && p_st != nstage;
+                        const bool oc = e > 1 && (!ZF || p_st != nstage);
                         unsigned pqa = DU_SENT, pqb = DU_SENT;
                         if (oc) {
                             const auto v2 = __builtin_amdgcn_raw_buffer_load_b64(g.xrs, 0, xQ + (((((e - 1) % 3) * NT + sown / SPM) * G + member) * (2 * SPM) + 2 * (sown % SPM)) * 4, 16);
@@ -1313,7 +1346,7 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
                         float sp2b = 0.f, gtb = 0.f;
                         if (OSPLIT && e > 1) own_book(sown, e, p_hs, p_st, p_k, sp2b, gtb);      // (reads the parked gradient: before azc_step rewrites its slot)
                         azc_step(sown, fin);
-                        if (oc) own_costs(sown, e, p_hs, p_st, p_k, true, pqa, pqb, sp2b, gtb);
+                        if (oc) own_costs(sown, e, p_hs, p_st, p_k, p_wa, true, pqa, pqb, sp2b, gtb);
                     }
                     DTL(40 * t + 9);
                 }
@@ -1415,10 +1448,11 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
                         spf_t = -1;
                         const f32x4 f = du_f(v);
                         if (tid < 40 * SPM) {                           // scatter into the [entry][4] layout, every agent twice (entries i and i + N)
+                            int ro = r_; DU_HERE_V(ro);                     // (the four range tests are formed here: see DU_HERE_V)
 #pragma unroll
                             for (int e4 = 0; e4 < 4; ++e4) {
                                 const int i = 4 * r_ + e4;
-                                if (i < d) {
+                                if (4 * ro + e4 < d) {
                                     const int ag = i / PD, k = i - PD * ag;
                                     lds[DB_XA + (j * 128 + ag) * 4 + k] = f[e4];
                                     lds[DB_XA + (j * 128 + ag + xp.N) * 4 + k] = f[e4];
@@ -1448,7 +1482,7 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
                         typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
                         const u32x2 pay = {__float_as_uint(q_), __float_as_uint(w_)};
                         const int off = xQ + ((((e % 3) * NT + t) * G + member) * (2 * SPM) + 2 * lane) * 4;          // (three slots: see the reset in P3)
-                        if (g.fast) __builtin_amdgcn_raw_buffer_store_b64(pay, g.xrs, off, 0, 0);
+                        if (du_fast<PINF>(g)) __builtin_amdgcn_raw_buffer_store_b64(pay, g.xrs, off, 0, 0);
                         else __builtin_amdgcn_raw_buffer_store_b64(pay, g.xrs, off, 0, 16);      // (the slot is reset below, behind the V gather)
                     }
                     DTL(40 * t + 23);
@@ -1476,12 +1510,12 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
                     if (KS > 1) thv = du_ld(g, vb, xT + fo);
                     const int gR = xG + ((((par ^ 1) * NT + t) * G + member) * DU_KBD) * 1024;
 #pragma unroll
-                    for (int mi = 0; mi < 3; ++mi) { const int mt = wave + 4 * mi; if (mt < DU_KBD) du_st_sent(g, vb, gR + mt * 1024); }
+                    for (int mi = 0; mi < 3; ++mi) { const int mt = wave + 4 * mi; if (mt < DU_KBD) du_st_sent<PINF>(g, vb, gR + mt * 1024); }
                     if (wave == 0 && lane < SPM) {
                         typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
                         const u32x2 sen = {DU_SENT, DU_SENT};
                         const int offr = xQ + (((((e + 1) % 3) * NT + t) * G + member) * (2 * SPM) + 2 * lane) * 4;
-                        if (g.fast) __builtin_amdgcn_raw_buffer_store_b64(sen, g.xrs, offr, 0, 0);
+                        if (du_fast<PINF>(g)) __builtin_amdgcn_raw_buffer_store_b64(sen, g.xrs, offr, 0, 0);
                         else __builtin_amdgcn_raw_buffer_store_b64(sen, g.xrs, offr, 0, 16);
                     }
                     if (KS == 1) thv = du_ld(g, vb, xT + fo);
@@ -1562,8 +1596,8 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
                     // two states behind an MFMA reads what the matrix pipe is still writing -- tools/mfma_hazard_check.py)
                     DU_FENCE4(a00, a01, a10, a11);
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // (H1: the resets issued in P3 have landed before a payload of this evaluation is stored)
-                    du_st(g, vb, gP + wave * 1024, a00 + a01);
-                    du_st(g, vb, gP + (wave + 4) * 1024, a10 + a11);
+                    du_st<PINF>(g, vb, gP + wave * 1024, a00 + a01);
+                    du_st<PINF>(g, vb, gP + (wave + 4) * 1024, a10 + a11);
                     if (third) {
                         f32x4 a20, a21;
                         mfma_v0(a20, w2[0].x, bf[0].x); mfma_v0(a21, w2[0].y, bf[0].y);
@@ -1574,7 +1608,7 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
                             mfma_v(a20, w2[kb].z, bf[kb].z); mfma_v(a21, w2[kb].w, bf[kb].w);
                         }
                         DU_FENCE2(a20, a21);
-                        du_st(g, vb, gP + (wave + 8) * 1024, a20 + a21);
+                        du_st<PINF>(g, vb, gP + (wave + 8) * 1024, a20 + a21);
                     }
                 } else {
                 float4 wf[2][MTM];
@@ -1605,7 +1639,7 @@ __global__ void __launch_bounds__(256, 2) rollout_duo_kernel(const DuoPlan* __re
                                 mfma_v(a0, w4[kb].z, bf[kb].z); mfma_v(a1, w4[kb].w, bf[kb].w);
                             }
                             DU_FENCE2(a0, a1);
-                            du_st(g, vb, gP + mt * 1024, a0 + a1);
+                            du_st<PINF>(g, vb, gP + mt * 1024, a0 + a1);
                         }
                     }
                 }
