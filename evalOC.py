@@ -17,7 +17,11 @@ disturbances (neuraloc_amd.disturb; single precision), one line per quantity and
 (neuraloc_amd.noise_study(..., rho=RHO), DESIGN.md section 3.18; the default 0 is the white noise);
 --worst EPS [--worst_steps K]: the disturbance path of energy ||W||_2 <= EPS that hurts the control objective L + alph0 G of xInit most
 (neuraloc_amd.worst_case_disturbances, K projected ascent steps; single precision), one line per quantity, nominal against worst case,
-and `<save>/figs/eval_<name>_worst.npz`."""
+and `<save>/figs/eval_<name>_worst.npz`;
+--hold K1,K2,... : what xInit costs when the control is refreshed only every K-th step and held in between (neuraloc_amd.hold_study,
+DESIGN.md section 3.19; single precision, the lane and one-CU kernels), one line per K with the plain closed loop as hold 0, and
+`<save>/figs/eval_<name>_hold.npz`; with --noise SIGMA [--noise_paths R --noise_seed S --noise_rho RHO] every K meets the same R disturbance
+paths (drawn inside the library from the seed) and the lines give the mean and the 5 / 50 / 95 % quantiles."""
 import argparse
 import os
 import time
@@ -53,6 +57,20 @@ p.add_argument("--noise_rho", type=float, default=0.0, metavar="RHO",
 p.add_argument("--worst", type=float, default=None, metavar="EPS",
                help="(addition) search the per-step state disturbances of path norm <= EPS that hurt xInit's L + G most (neuraloc_amd.worst_case_disturbances)")
 p.add_argument("--worst_steps", type=int, default=20, metavar="K", help="(addition) projected ascent steps for --worst")
+p.add_argument("--hold", type=str, default=None, metavar="K1,K2,...",
+               help="(addition) roll xInit out with the control refreshed every K-th step and held in between, for every K of the list "
+                    "(neuraloc_amd.hold_study); with --noise under the same disturbances for every K")
+
+
+def parse_holds(text):
+    """--hold: a comma-separated list of integers >= 1"""
+    try:
+        holds = [int(item) for item in text.split(",")]
+    except ValueError:
+        raise SystemExit("--hold K1,K2,... must be a comma-separated list of integers >= 1") from None
+    if not holds or min(holds) < 1:
+        raise SystemExit("--hold K1,K2,... must be a comma-separated list of integers >= 1")
+    return holds
 
 
 def noise_rho_refusals(args):
@@ -80,6 +98,11 @@ def main(argv=None):
         raise SystemExit("--noise_rng counter needs 0 <= --noise_seed < 2**64")
     if args.worst is not None and prec != torch.float32:
         raise SystemExit("--worst runs in single precision only (the double-precision rollout takes no disturbance)")
+    holds = None if args.hold is None else parse_holds(args.hold)
+    if holds is not None and prec != torch.float32:
+        raise SystemExit("--hold runs in single precision only (the double-precision rollout takes no held control)")
+    if holds is not None and args.noise is not None and not 0 <= args.noise_seed < 2 ** 64:
+        raise SystemExit("--hold with --noise needs 0 <= --noise_seed < 2**64")
     os.makedirs(os.path.join(args.save, "figs"), exist_ok=True)
     print(args)
     dev = f"cuda:{args.gpu}"
@@ -174,6 +197,35 @@ def main(argv=None):
             print("saved the worst-case disturbance to " + sPath)
             out["worst"] = {name: {"nominal": rows[name][0], "worst": rows[name][1]} for name in rows}
             out["worst"]["norm"] = float(res["W"].pow(2).sum().sqrt())
+        if holds is not None:
+            kw = {}
+            if args.noise is not None:
+                kw = dict(sigma=args.noise, seed=args.noise_seed, paths=args.noise_paths, rho=args.noise_rho if args.noise_rho != 0 else None)
+            st = na.hold_study(xInit, net, prob, nt, holds=holds, alph=alph, **kw)
+            names = ("L+G", "G", "L", "Q", "W")
+            save = {"holds": np.array([0] + holds), "sigma": np.nan if args.noise is None else args.noise,
+                    "paths": 1 if args.noise is None else args.noise_paths, "seed": args.noise_seed}
+            out["hold"] = {}
+            if args.noise is None:
+                print("hold %4s" % "K" + "".join(" %11s" % name for name in names))
+                for k in [0] + holds:
+                    print("hold %4d" % k + "".join(" %11.4e" % float(st[k][name][0]) for name in names))
+                    out["hold"][k] = {name: float(st[k][name][0]) for name in names}
+                    save.update({f"{k}/{name}": st[k][name].cpu().numpy() for name in names})
+            else:
+                keys = ("mean", "std", "q05", "q50", "q95")
+                print("hold sigma=%g, %d paths, seed %d (the same disturbances for every K; mean [5%%, 50%%, 95%%])" %
+                      (args.noise, args.noise_paths, args.noise_seed))
+                print("hold %4s" % "K" + "".join(" %47s" % name for name in names))
+                for k in [0] + holds:
+                    print("hold %4d" % k + "".join(" %11.4e [%10.3e,%10.3e,%10.3e]" % tuple(float(st[k][name][q][0]) for q in ("mean", "q05", "q50", "q95"))
+                                                   for name in names))
+                    out["hold"][k] = {name: {q: float(st[k][name][q][0]) for q in keys} for name in names}
+                    save.update({f"{k}/{name}/{q}": st[k][name][q].cpu().numpy() for name in names for q in keys})
+            save.update({f"{k}/persample": st[k]["persample"].cpu().numpy() for k in [0] + holds})
+            sPath = os.path.join(args.save, "figs", strTitle + "_hold.npz")
+            np.savez(sPath, **save)
+            print("saved the hold study to " + sPath)
     return out
 
 

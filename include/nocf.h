@@ -292,6 +292,36 @@ int nocf_rollout_record_noisy_corr_f32(const NocfPhi* phi, const NocfProb* prob,
                                        float* z_out, float* persample, float* cost_sums, float* s_all, float* act_rec, int32_t* recorded,
                                        void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * The zero-order-hold rollout: the control is sampled every hold-th step and applied, unchanged, until the next sample -- a deployed
+ * controller's rate, where every other rollout re-evaluates the feedback law at every Runge-Kutta stage.  hold = K >= 1; W nullable, device
+ * [nt, n, d], float32, time-major: exactly nocf_rollout_disturbed_f32's tensor; h, tk and the steppers are nocf_rollout_f32's.
+ *     z = [x, 0, 0, 0, 0]
+ *     for k in 0 .. nt-1:
+ *         if k % K == 0:  c = calcCtrls(x_k, grad_x Phi(x_k, t_k))      the state the controller really meets: W[k-1] is already on it
+ *         z = step(z) with the right-hand side  [ f(x, c) | L(x, c) | 0 | Q(x) | W(x) ]     RK4: four physics evaluations, c fixed; RK1: one
+ *         if W: z[:, :d] += W[k]
+ *         zFull[k+1] = z;  ctrlFull[k+1] = c                            the control APPLIED over step k (slot 0 stays zero)
+ *     terminal block: unchanged, at z(T) (G, HJfin, HJgrad: one network evaluation)
+ * Point agents (Cross2D, SwarmTraj): c = -p (d components), f = c, and L, Q, W are the reference's calcLHQW(x, p) at p = -c (the Cross2D /
+ * SwarmTraj difference in where alph_Q sits included).  Quadcopter, one craft: c = (u, tau) = calcCtrls, 4 components, tau = -p[9:12] / 2;
+ * f = [x[6:12], (u/m) f7(ang), (u/m) f8(ang), (u/m) f9(ang) - g, tau] with f7..f9 from the CURRENT angles; L = alph_Q Q + 2 + u^2 + |tau|^2
+ * (the reference's 2 + u^2 + sq / 4); W = 0.  Every problem: the HJt column (persample[:, 2], z[:, d+1]) is identically 0 -- a held control
+ * has no HJB residual.  persample [n, 7], cost_sums, cost_means and z_out keep their layouts.  K >= nt is the open-loop rollout of the
+ * initial control; a K that does not divide nt leaves a short last interval.  The call makes ceil(nt / K) + 1 network evaluations where
+ * nocf_rollout_f32 makes 4 nt + 1 (5 nt + 1 with zFull), and the same 4 nt physics evaluations.
+ * Dispatch: the register-resident small-network kernel, then the one-CU kernel, with their existing eligibility tests; every other shape
+ * (the per-tile and split-role families, nTh > 2, m > 128) and a quadcopter problem of more than one craft: NOCF_E_SHAPE.  hold < 1:
+ * NOCF_E_SHAPE.  The null rules are nocf_rollout_disturbed_f32's, except that W may be NULL.  float32 only; an evaluation (nothing is
+ * recorded for an adjoint); one network; no segments.  Every refusal returns before anything is enqueued.  nocf_last_rollout_kernel()
+ * reports "rollout_lane_kernel<hold>" / "rollout_lane_kernel<hold,dist>" (with W) and "rollout_mono_kernel<hold>" /
+ * "rollout_mono_kernel<hold,dist>".  nocf_version() is unchanged: callers probe for the symbol.
+ */
+int nocf_rollout_held_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, const float* W, int32_t hold, int64_t n,
+                          double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                          float* z_out, float* persample, float* cost_sums, float* cost_means, float* zFull, float* ctrlFull,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* host only: the four Philox words of (seed, row, k, i) as the kernels form them (no device is touched).  out == NULL: NOCF_E_NULL;
  * row, k or i < 0: NOCF_E_SHAPE. */
 int nocf_debug_noise_words(uint64_t seed, int64_t row, int32_t k, int32_t i, uint32_t out[4]);

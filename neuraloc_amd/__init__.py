@@ -21,6 +21,7 @@ from .ensemble_risk import ensemble_risk_weights, ensemble_weighted_ocflow_train
 from .ensemble_minmax import (ensemble_disturbed_rollout, ensemble_disturbed_ocflow_train, ensemble_minmax_ocflow_train,
                               ensemble_disturbance_gradient, ensemble_ascend_disturbances, ensemble_worst_case_disturbances,
                               ensemble_adversarial_step)
+from .hold import held_rollout, hold_study
 
 __all__ = ["Phi", "ResNN", "antiderivTanh", "derivTanh", "OCflow", "ocG", "Cross2D", "SwarmTraj",
            "Quadcopter", "initProb", "resample", "OCflow_sharded", "shard_rows", "reduce_cost_sums", "check_errors",
@@ -35,4 +36,4 @@ __all__ = ["Phi", "ResNN", "antiderivTanh", "derivTanh", "OCflow", "ocG", "Cross
            "ensemble_risk_weights", "ensemble_weighted_ocflow_train", "ensemble_risk_ocflow_train",
            "ensemble_disturbed_rollout", "ensemble_disturbed_ocflow_train", "ensemble_minmax_ocflow_train",
            "ensemble_disturbance_gradient", "ensemble_ascend_disturbances", "ensemble_worst_case_disturbances",
-           "ensemble_adversarial_step"]
+           "ensemble_adversarial_step", "held_rollout", "hold_study"]

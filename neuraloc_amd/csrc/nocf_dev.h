@@ -176,3 +176,8 @@ struct RollArgs {
     // of them moves.
     const float* nzScale1; const float* nzRho;
 };
+
+// The zero-order-hold rollout (include/nocf.h, nocf_rollout_held_f32): the control is refreshed every K-th step.  A
+// LAST kernel argument of the lane and the one-CU kernels, behind the existing ones (RollArgs and everything else stay where they are), read
+// by the HOLD instantiations only
+struct HoldArgs { int K; };

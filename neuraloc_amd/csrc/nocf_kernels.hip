@@ -1903,12 +1903,12 @@ static int rollout_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, const
         if (hipEventCreate(&ev0) || hipEventCreate(&ev1)) return (int)hipErrorUnknown;
         (void)hipEventRecord(ev0, st);
     }
-#define NOCF_LANE_ENS_LAUNCH(MPV, DPV) do { if (dist && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 1, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz); \
-                                             else if (dist) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 1, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz); \
-                                             else if (noise && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 2, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz); \
-                                             else if (noise) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 2, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz); \
-                                             else if (s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 0, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz); \
-                                             else hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 0, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz); } while (0)
+#define NOCF_LANE_ENS_LAUNCH(MPV, DPV) do { if (dist && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 1, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz, HoldArgs{}); \
+                                             else if (dist) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 1, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz, HoldArgs{}); \
+                                             else if (noise && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 2, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz, HoldArgs{}); \
+                                             else if (noise) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 2, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz, HoldArgs{}); \
+                                             else if (s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 0, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz, HoldArgs{}); \
+                                             else hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 0, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz, HoldArgs{}); } while (0)
     if (MPsel == 16) { if (DPsel == 8) { NOCF_LANE_ENS_LAUNCH(16, 8); } else if (DPsel == 16) { NOCF_LANE_ENS_LAUNCH(16, 16); } else { NOCF_LANE_ENS_LAUNCH(16, 32); } }
     else             { if (DPsel == 8) { NOCF_LANE_ENS_LAUNCH(32, 8); } else if (DPsel == 16) { NOCF_LANE_ENS_LAUNCH(32, 16); } else { NOCF_LANE_ENS_LAUNCH(32, 32); } }
 #undef NOCF_LANE_ENS_LAUNCH
@@ -2217,7 +2217,8 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
                         float* z_out, float* persample, float* cost_sums, float* zFull, float* ctrlFull,
                         void* workspace, size_t workspace_bytes, void* stream, float* s_all,
                         float* act = nullptr, int32_t* act_recorded = nullptr, float* tapeU1 = nullptr, float* tapeSc = nullptr,
-                        const SegTab* seg = nullptr, float* cost_means = nullptr, const float* distW = nullptr, const NoiseSpec* noise = nullptr) {
+                        const SegTab* seg = nullptr, float* cost_means = nullptr, const float* distW = nullptr, const NoiseSpec* noise = nullptr,
+                        int hold = 0) {
     if (act_recorded) *act_recorded = 0;
     // disturbance mode of this call: 0 none, 1 W from memory (distW), 2 drawn inside the kernels (noise), 3 drawn and correlated in time
     // (noise with rho).  `dist` below: any of the three, they share every rule and the dispatch
@@ -2236,6 +2237,9 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
     if (dist && tapeSc) return NOCF_E_NULL;
     if (dist && act && !s_all) return NOCF_E_NULL;
     if (dist && seg) return NOCF_E_SHAPE;
+    // the held rollout (nocf_rollout_held_f32: hold >= 1, the control refreshed every hold-th step): an evaluation on the lane and the one-CU
+    // kernels, with W from memory or without
+    if (hold && (s_all || act || tapeSc || seg || noise)) return NOCF_E_SHAPE;
     DevProb pb;
     rc = fill_prob(prob, phi->d, &pb);
     if (rc) return rc;
@@ -2273,10 +2277,17 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
         if (env_int("NOCF_MONO", 1) == 0 || make_mono_plan(pl, pb.nAgents, &probe) != 0 || workspace_bytes < mono_ws_bytes(probe))
             return NOCF_E_SHAPE;
     }
-    g_last_errp = nullptr;
     // small networks: one wave per sample, everything in registers (nocf_lane.inc); needs no packed images
     const bool lane_ok = env_int("NOCF_LANE", 1) != 0 && phi->nTh == 2 && phi->m <= 32 && phi->d + 1 <= 32 &&
                          pb.kind != NOCF_PROB_QUADCOPTER && pb.nAgents <= 16 && !g_stamp_buf && !seg;
+    if (hold && !lane_ok) {                       // held: lane, then one-CU, nothing else -- decided before anything is enqueued or reset
+        MonoPlan probe;
+        if (env_int("NOCF_MONO", 1) == 0 || make_mono_plan(pl, pb.nAgents, &probe) != 0 || workspace_bytes < mono_ws_bytes(probe))
+            return NOCF_E_SHAPE;
+        // (more than one craft would go through physics_finish's general quadcopter branch, whose thrusts are not held)
+        if (pb.kind == NOCF_PROB_QUADCOPTER && pb.nAgents != 1) return NOCF_E_SHAPE;
+    }
+    g_last_errp = nullptr;
     if (lane_ok) {
         LaneArgs la;
         la.P = DevPhi{phi->K0, phi->b0, phi->K, phi->b, phi->w, phi->A, phi->cw, phi->cb_dev};
@@ -2284,7 +2295,7 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
         // one launch per call (round 6, NOCF_LANE_ONE=1): with a ticket word the kernel's last workgroup forms the sums (and means) itself.
         // OFF by default -- measured on the MI355X (profiles/r6/07_lane_one_launch.txt): the agent-scope release every workgroup needs in front of
         // its ticket is an L2 write-back (buffer_wbl2 sc1), 256-512 of them cost 7-15 us, more than the 4-us kernel and launch gap they replace
-        unsigned* ticket = (cost_sums && !s_all && !dist && env_int("NOCF_LANE_ONE", 0) != 0) ? lane_ticket(st) : nullptr;
+        unsigned* ticket = (cost_sums && !s_all && !dist && !hold && env_int("NOCF_LANE_ONE", 0) != 0) ? lane_ticket(st) : nullptr;
         la.sums = ticket ? cost_sums : nullptr; la.ticket = ticket;
         la.means = mean_args.means; la.a0 = mean_args.a0; la.a3 = mean_args.a3; la.a4 = mean_args.a4; la.a5 = mean_args.a5;
         const int grid = (int)((n + 3) / 4);
@@ -2295,21 +2306,23 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
             (void)hipEventRecord(ev0, st);
         }
         const size_t laneLds = ticket ? (size_t)(256 * 7 * 8 + 16) : 0;      // (the last-workgroup reduction's scratch: only with a ticket)
-#define NOCF_LANE_LAUNCH(MPV, DPV) do { if (dmode == 3 && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 3>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}); \
-                                         else if (dmode == 3) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 3>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}); \
-                                         else if (dmode == 2 && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 2>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}); \
-                                         else if (dmode == 2) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 2>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}); \
-                                         else if (dist && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 1>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}); \
-                                         else if (dist) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 1>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}); \
-                                         else if (s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}); \
-                                         else if (ticket) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, true>), dim3(grid), dim3(256), laneLds, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}); \
-                                         else hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}); } while (0)
+#define NOCF_LANE_LAUNCH(MPV, DPV) do { if (hold && dist) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 1, false, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}, HoldArgs{hold}); \
+                                         else if (hold) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 0, false, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}, HoldArgs{hold}); \
+                                         else if (dmode == 3 && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 3>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}, HoldArgs{}); \
+                                         else if (dmode == 3) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 3>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}, HoldArgs{}); \
+                                         else if (dmode == 2 && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 2>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}, HoldArgs{}); \
+                                         else if (dmode == 2) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 2>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}, HoldArgs{}); \
+                                         else if (dist && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 1>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}, HoldArgs{}); \
+                                         else if (dist) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 1>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}, HoldArgs{}); \
+                                         else if (s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}, HoldArgs{}); \
+                                         else if (ticket) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, true>), dim3(grid), dim3(256), laneLds, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}, HoldArgs{}); \
+                                         else hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}, HoldArgs{}); } while (0)
         if (MPsel == 16) { if (DPsel == 8) { NOCF_LANE_LAUNCH(16, 8); } else if (DPsel == 16) { NOCF_LANE_LAUNCH(16, 16); } else { NOCF_LANE_LAUNCH(16, 32); } }
         else             { if (DPsel == 8) { NOCF_LANE_LAUNCH(32, 8); } else if (DPsel == 16) { NOCF_LANE_LAUNCH(32, 16); } else { NOCF_LANE_LAUNCH(32, 32); } }
 #undef NOCF_LANE_LAUNCH
         e = hipGetLastError();
         if (e) return (int)e;
-        g_last_kernel = dmode == 3 ? "rollout_lane_kernel<noise-corr>" : dmode == 2 ? "rollout_lane_kernel<noise>" : dist ? "rollout_lane_kernel<dist>" : "rollout_lane_kernel";
+        g_last_kernel = hold ? (dist ? "rollout_lane_kernel<hold,dist>" : "rollout_lane_kernel<hold>") : dmode == 3 ? "rollout_lane_kernel<noise-corr>" : dmode == 2 ? "rollout_lane_kernel<noise>" : dist ? "rollout_lane_kernel<dist>" : "rollout_lane_kernel";
         if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
         if (cost_sums && !ticket) {
             hipLaunchKernelGGL(cost_sum_kernel, dim3(1), dim3(256), 0, st, persample, (long)n, cost_sums, errp, mean_args);
@@ -2321,7 +2334,7 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
 #ifndef NOCF_JIT_ONLY
     // split-role weight-stationary kernel (nocf_duo.hip): wide two-layer networks (m = 512) on point-agent problems, any batch
     // size (chunks of 2048 rows), evaluation and the recording forward of training
-    if (env_int("NOCF_DUO", 1) != 0 && !seg && !dist) {
+    if (env_int("NOCF_DUO", 1) != 0 && !seg && !dist && !hold) {
         if (g_prof_on) {
             if (hipEventCreate(&ev0) || hipEventCreate(&ev1)) return (int)hipErrorUnknown;
         }
@@ -2364,7 +2377,7 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
         hipLaunchKernelGGL(mono_pack_kernel, dim3(64), dim3(256), 0, st, mpl, P, ws);
         const size_t ldsBytes = (size_t)mpl.pp.ldsFloats * 4;
         const void* fk = nullptr;
-#define NOCF_MONO_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) fk = dmode == 3 ? (s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, 3>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 3>)) : dmode == 2 ? (s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, 2>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 2>)) : dist ? (s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, 1>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 1>)) : s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false>);
+#define NOCF_MONO_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) fk = hold ? (dist ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 1, false, true>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 0, false, true>)) : dmode == 3 ? (s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, 3>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 3>)) : dmode == 2 ? (s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, 2>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 2>)) : dist ? (s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, 1>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 1>)) : s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false>);
         MONO_SHAPES(NOCF_MONO_PICK)
 #undef NOCF_MONO_PICK
         e = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes); if (e) return (int)e;
@@ -2380,11 +2393,12 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
         MonoEnsArgs noEns;                            // (read by the ENS instantiations only: nocf_rollout_mid_ensemble_f32)
         memset(&noEns, 0, sizeof(noEns));
         EnsNoiseArgs noNz{nullptr, nullptr};          // (read by the noisy ENS instantiations only: nocf_rollout_noisy_mid_ensemble_f32)
-        void* args[] = {(void*)&mpp, (void*)&pb, (void*)&ws, (void*)&ra, (void*)&noEns, (void*)&noNz};
+        HoldArgs hda{hold};                           // (read by the HOLD instantiations only: nocf_rollout_held_f32)
+        void* args[] = {(void*)&mpp, (void*)&pb, (void*)&ws, (void*)&ra, (void*)&noEns, (void*)&noNz, (void*)&hda};
         e = hipLaunchKernel(fk, dim3((int)((n + 15) / 16)), dim3(256), args, ldsBytes, st); if (e) return (int)e;
         ra.act = nullptr; ra.actRows = 0;
         if (mono_rec && act_recorded) *act_recorded = 1;
-        g_last_kernel = dmode == 3 ? "rollout_mono_kernel<noise-corr>" : dmode == 2 ? "rollout_mono_kernel<noise>" : dist ? "rollout_mono_kernel<dist>" : "rollout_mono_kernel";
+        g_last_kernel = hold ? (dist ? "rollout_mono_kernel<hold,dist>" : "rollout_mono_kernel<hold>") : dmode == 3 ? "rollout_mono_kernel<noise-corr>" : dmode == 2 ? "rollout_mono_kernel<noise>" : dist ? "rollout_mono_kernel<dist>" : "rollout_mono_kernel";
         e = hipGetLastError();
         if (e) return (int)e;
         if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
@@ -2403,6 +2417,7 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
         }
         return 0;
     }
+    if (hold) return NOCF_E_SHAPE;                    // (held: decided above; not reached)
     if (seg) return NOCF_E_SHAPE;                     // (segments: no one-CU instantiation for this shape -- the caller launches them one by one)
     {
         const size_t ldsBytes = (size_t)pl.ldsFloats * 4 + corrLds;
@@ -2513,6 +2528,16 @@ int nocf_rollout_disturbed_f32(const NocfPhi* phi, const NocfProb* prob, const f
     if (cost_means && !cost_sums) return NOCF_E_NULL;
     return rollout_impl(phi, prob, x, n, t0, t1, nt, stepper, alph, z_out, persample, cost_sums, zFull, ctrlFull,
                         workspace, workspace_bytes, stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, cost_means, W);
+}
+
+int nocf_rollout_held_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, const float* W, int32_t hold, int64_t n,
+                          double t0, double t1, int32_t nt, int32_t stepper, const float* alph,
+                          float* z_out, float* persample, float* cost_sums, float* cost_means, float* zFull, float* ctrlFull,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+    if (hold < 1) return NOCF_E_SHAPE;
+    if (cost_means && !cost_sums) return NOCF_E_NULL;
+    return rollout_impl(phi, prob, x, n, t0, t1, nt, stepper, alph, z_out, persample, cost_sums, zFull, ctrlFull,
+                        workspace, workspace_bytes, stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, cost_means, W, nullptr, hold);
 }
 
 int nocf_rollout_noisy_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, const float* scale, uint64_t seed, int64_t row0, int64_t n,
@@ -3171,7 +3196,8 @@ static int rollout_mid_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, c
         (void)hipEventRecord(ev0, st);
     }
     const MonoPlan* mpp = reinterpret_cast<const MonoPlan*>(ws + mpl.pp.oPlan);
-    void* args[] = {(void*)&mpp, (void*)&pb, (void*)&ws, (void*)&ra, (void*)&en, (void*)&nz};
+    HoldArgs noHold{};                                // (read by the HOLD instantiations only: nocf_rollout_held_f32)
+    void* args[] = {(void*)&mpp, (void*)&pb, (void*)&ws, (void*)&ra, (void*)&en, (void*)&nz, (void*)&noHold};
     e = hipLaunchKernel(fk, dim3((unsigned)((long)members * en.tiles)), dim3(256), args, ldsBytes, st);
     if (e) return (int)e;
     if (mono_rec && act_recorded) *act_recorded = 1;

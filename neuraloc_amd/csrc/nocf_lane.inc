@@ -56,8 +56,13 @@ struct EnsArgs { unsigned n; long xs; const float* alph; };
 // EnsNoiseArgs::ws == 0, one [nt, n, d] for all members.  The member's slice begins e * ws floats behind the base (wave-uniform, like the
 // member's other pointers) and is indexed by the step and the row INSIDE the member; the load stands where the DIST == 1 load stands, at the
 // top of the step, and every statement behind it is the DIST == 1 one
-template <int MP, int DP, bool REC, bool ONE = false, int DIST = 0, bool ENS = false>
-__global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb pb, RollArgs ra, EnsArgs ea, EnsNoiseArgs nz) {
+// HOLD (DIST 0 / 1; no REC, ONE, ENS): the zero-order-hold rollout.  The lane keeps the sampled grad Phi in ONE register (gh) across the steps
+// and calls grad_phi only when k % K == 0 -- at the step's first stage input, which carries W[k-1] already; every stage of every step is
+// rhs(s, gh), the physics and the cost quadrature at the current state with p = -c held (lane d + 1, the HJB residual, gives 0), and
+// ctrlFull[k+1] is the held -gh: no control evaluation behind the step.  Every HOLD test is `if constexpr`
+template <int MP, int DP, bool REC, bool ONE = false, int DIST = 0, bool ENS = false, bool HOLD = false>
+__global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb pb, RollArgs ra, EnsArgs ea, EnsNoiseArgs nz, HoldArgs hd) {
+    static_assert(!HOLD || (!REC && !ONE && !ENS && DIST <= 1), "the held rollout: evaluation of one network, W from memory or none");
     const int lane = threadIdx.x & 63;
     const long sample = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const bool live = sample < ra.n;
@@ -199,7 +204,7 @@ __global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb 
         const float gt = lane_bcast_u(g, d);
         float dz = -g;
         if (lane == d) dz = Lg;
-        else if (lane == d + 1) dz = fabsf(gt - H);
+        else if (lane == d + 1) { if constexpr (HOLD) dz = 0.f; else dz = fabsf(gt - H); }
         else if (lane == d + 2) dz = Qret;
         else if (lane == d + 3) dz = Wv;
         return (lane < d + 4) ? dz : 0.f;
@@ -214,6 +219,8 @@ __global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb 
     const float c16 = (float)(1.0 / 6.0), c26 = (float)(2.0 / 6.0);
     double tk = ra.t0;
     float dummy;
+    float gh = 0.f;                                     // HOLD: the sampled grad Phi, this lane's component
+    int kh = 0;                                         // HOLD: steps left until the next sample
     for (int k = 0; k < ra.nt; ++k) {
         const double t1k = tk + ra.h;
         const double hsd = t1k - tk;                      // stepRK4 re-derives h = t1 - t0 (src/OCflow.py:170)
@@ -224,6 +231,7 @@ __global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb 
         else if constexpr (DIST == 1 && ENS) wk = lane < d ? wmem[((long)k * ea.n + xr) * d + lane] : 0.f;
         else if constexpr (DIST == 1) wk = lane < d ? ra.dist[((long)k * ra.n + row) * d + lane] : 0.f;
         // training: the stage input s = [x, t] of every evaluation goes to sAll[(k*nstage + st)][sample][0..d] (one row per lane group)
+        auto stage_g = [&](float s) -> float { if constexpr (HOLD) return gh; else return grad_phi(s, false, dummy); };
         auto record = [&](int st, int nstage, float s) {
             if (REC && ra.sAll && live && lane <= d) ra.sAll[(((long)k * nstage + st) * ra.n + sample) * (d + 1) + lane] = s;
         };
@@ -231,34 +239,36 @@ __global__ void __launch_bounds__(256) rollout_lane_kernel(LaneArgs la, DevProb 
             const float z0 = z;
             float s = lane < d ? z0 : (lane == d ? (float)tk : 0.f);
             record(0, 4, s);
-            float K = hs * rhs(s, grad_phi(s, false, dummy));
+            if constexpr (HOLD) { if (kh == 0) { gh = grad_phi(s, false, dummy); kh = hd.K; } --kh; }
+            float K = hs * rhs(s, stage_g(s));
             float za = z0 + c16 * K;
             float xs = z0 + 0.5f * K;
             s = lane < d ? xs : (lane == d ? (float)(tk + hsd / 2) : 0.f);
             record(1, 4, s);
-            K = hs * rhs(s, grad_phi(s, false, dummy));
+            K = hs * rhs(s, stage_g(s));
             za += c26 * K;
             xs = z0 + 0.5f * K;
             s = lane < d ? xs : (lane == d ? (float)(tk + hsd / 2) : 0.f);
             record(2, 4, s);
-            K = hs * rhs(s, grad_phi(s, false, dummy));
+            K = hs * rhs(s, stage_g(s));
             za += c26 * K;
             xs = z0 + K;
             s = lane < d ? xs : (lane == d ? (float)(tk + hsd) : 0.f);
             record(3, 4, s);
-            K = hs * rhs(s, grad_phi(s, false, dummy));
+            K = hs * rhs(s, stage_g(s));
             z = za + c16 * K;
         } else {
             const float s = lane < d ? z : (lane == d ? (float)tk : 0.f);
             record(0, 1, s);
-            z = z + hs * rhs(s, grad_phi(s, false, dummy));
+            if constexpr (HOLD) { if (kh == 0) { gh = grad_phi(s, false, dummy); kh = hd.K; } --kh; }
+            z = z + hs * rhs(s, stage_g(s));
         }
         if constexpr (DIST) z += wk;                       // (lanes >= d hold 0: the four cost components are not displaced)
         tk += ra.h;
         if (ra.zFull) {
             // src/OCflow.py:51-55: z_{k+1}, and the control from grad Phi at (x_{k+1}, tk - h)
             const float s = lane < d ? z : (lane == d ? (float)(tk - ra.h) : 0.f);
-            const float g = grad_phi(s, false, dummy);
+            const float g = stage_g(s);                     // (HOLD: the control applied over step k)
             if (live) {
                 if (lane < d + 4) ra.zFull[((long)(k + 1) * ra.n + sample) * (d + 4) + lane] = z;
                 if (lane < d) ra.ctrlFull[((long)(k + 1) * ra.n + sample) * ra.cdim + lane] = -g;

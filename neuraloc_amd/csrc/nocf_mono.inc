@@ -211,9 +211,18 @@ __device__ __forceinline__ void mono_sincos(float x, float& sn, float& cs) {
 // [E, nt, n, d] member-major (EnsNoiseArgs::ws = nt n d) or one [nt, n, d] for all members (ws = 0).  The kernel's copy of ra.dist moves to the
 // member's slice once, with the member's other pointers (workgroup-uniform); ra.n and row0 are the member's, so the DIST == 1 load and add
 // below are the single-network statements on that slice
-template <int KBM, int KBD, bool REC, int DIST = 0, bool ENS = false>
+// HOLD (DIST 0 / 1; no REC, ENS; HoldArgs, nocf_dev.h): the zero-order-hold rollout (include/nocf.h, nocf_rollout_held_f32; DESIGN 3.19).  The
+// network runs at the first stage of every K-th step -- on the state rows as the previous step left them, W[k-1] included -- and at the final
+// time; every other evaluation is `held`: it skips the fragments, P1..P4, the gather and the gradient rows and goes straight to the physics.
+// k, st and K are kernel-uniform, so every barrier of the skipped section is skipped by all 256 threads.  What stays where it is: the gradient
+// rows Gl (point agents: physics_sums / physics_finish read p = -c from them) and the P4 partials GP (singlequad: the 16 lanes of a sample
+// re-form the same pv from them), and singlequad's thrust in one register per thread (uh) -- f7..f9 come from the current angles, u does not.
+// The HJB column's right-hand side is 0, the control evaluation behind a step with intermediates is gone (nsub = nstage) and ctrl_write
+// writes the held control behind the last stage.  One craft only: the dispatcher refuses the general quadcopter branch of physics_finish
+template <int KBM, int KBD, bool REC, int DIST = 0, bool ENS = false, bool HOLD = false>
 __global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __restrict__ mpp, DevProb pb, float* ws, RollArgs ra, MonoEnsArgs en,
-                                                           EnsNoiseArgs nz) {
+                                                           EnsNoiseArgs nz, HoldArgs hd) {
+    static_assert(!HOLD || (!REC && !ENS && DIST <= 1), "the held rollout: evaluation of one network, W from memory or none");
     constexpr int MT = (KBM + 3) / 4;              // hidden M-tiles per wave: tiles w, w+4, ...
     constexpr int T = 16;
     constexpr MonoFwdLds LL = mono_fwd_lds(KBM, KBD);
@@ -339,12 +348,14 @@ __global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __res
 
     const float c16 = (float)(1.0 / 6.0), c26 = (float)(2.0 / 6.0);
     const int nstage = (ra.stepper == NOCF_RK4) ? 4 : 1;
-    const int nsub = nstage + (ra.zFull ? 1 : 0);
+    const int nsub = nstage + ((ra.zFull && !HOLD) ? 1 : 0);
     const bool quad = (pb.kind == NOCF_PROB_QUADCOPTER);
     double tk = sg_t0;
     const bool quad1 = quad && pb.nAgents == 1 && d == 12 && KBD == 1;     // singlequad: wave-local physics below
     float qz0 = quad1 ? Z0[(tid >> 4) * ZLD + (tid & 15)] : 0.f, qzA = 0.f; // ... with component tid%16 of sample tid/16 of z in registers
     bool sf_ready = false;                                             // the RK update has already written the next stage state's fragments
+    float uh = 0.f;                                                    // HOLD, singlequad: the held thrust of this thread's sample
+    int kh = 0;                                                        // HOLD: steps left until the next sample
     float wcar[KBD + 1];                                               // DIST == 3: w_{k-1} of this thread's components of the write-back sweep
     if constexpr (DIST == 3) {
 #pragma unroll
@@ -382,12 +393,17 @@ __global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __res
             }
         }
         for (int st = 0; st < (fin ? 1 : nsub); ++st) {
+            bool held = false;                                         // HOLD: this evaluation takes the sampled control (kernel-uniform)
+            if constexpr (HOLD) {
+                if (!fin && st == 0) { if (kh == 0) kh = hd.K; else held = true; --kh; }
+                else held = !fin;
+            }
 #ifdef NOCF_STAMPS
             c.tl = (ra.stamps && blockIdx.x == 9 && k == 40 && st == 1) ? ra.stamps + 264 * 12 : nullptr;     // tools/slab_timeline.py mono
 #endif
             TL(c, 0);
             // ---- stage-state fragments from the state rows: (kb, lane) = sample lane%16, entries 16 kb + 4 (lane/16) + e of [x, t]
-            if (!sf_ready) {
+            if (!sf_ready && !held) {
                 for (int f = tid; f < KBD * 64; f += 256) {
                     const int l = f & 63, kb = f >> 6;
                     const float* srow = SB + (l & 15) * LDs + 16 * kb + 4 * (l >> 4);
@@ -420,152 +436,155 @@ __global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __res
             float* recB = (REC && recEv >= 0) ? ra.act + (recEv * ra.n + row0) * pl.m : nullptr;          // rows of this tile in the first section
             const long recSec = ra.actRows * pl.m;
             const unsigned recL = (unsigned)(lane & 15) * (unsigned)pl.m + 4u * (unsigned)slot;              // + 16 mt: this lane's 4 features of its sample
-            TL(c, 1);
-            // ================= P1: o = K0 s + b0, u0 = sigma(o), tanh(o);  z = A s rides along =================
-            f32x4 acc[MT], th0[MT], u0k[MT];
-            mono_gemm<MT, KBD, false>(K1, (mp.lSF >> 2) + lane, acc);
-            {
-                f32x4 zacc = {0.f, 0.f, 0.f, 0.f};
-                if (wave < KBD) {
-                    const float4 bz = L4[(mp.lSF >> 2) + wave * 64 + lane];
-                    f32x4 z0, z1;
-                    mfma16_vv0(z0, AZ[0], bz.x); mfma16_vv0(z1, AZ[1], bz.y); mfma16_vv(z0, AZ[2], bz.z); mfma16_vv(z1, AZ[3], bz.w);
-                    asm volatile("s_nop 7\n\ts_nop 4" : "+v"(z0), "+v"(z1));
-                    zacc = z0 + z1;
-                }
-                L4[(mp.lZP >> 2) + wave * 64 + lane] = make_float4(zacc[0], zacc[1], zacc[2], zacc[3]);     // lane: sample lane%16, rows 4 (lane/16) + e of A
-            }
-#pragma unroll
-            for (int mi = 0; mi < MT; ++mi) {
-                const int mt = wave + 4 * mi;
-                f32x4 sg, th;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { float s_, t_; act_pair(acc[mi][e] + b0v[mi][e], s_, t_); sg[e] = s_; th[e] = t_; }
-                th0[mi] = th; u0k[mi] = sg;
-                if (mt < KBM) L4[(mp.lUF >> 2) + mt * 64 + lane] = make_float4(sg[0], sg[1], sg[2], sg[3]);
-                if (recEv >= 0 && mt < KBM && 16 * mt + 4 * slot + 3 < pl.m && row0 + (lane & 15) < ra.n) {      // activation record: u0, tanh(o)
-                    *reinterpret_cast<float4*>(recB + (recL + 16u * mt)) = make_float4(sg[0], sg[1], sg[2], sg[3]);
-                    *reinterpret_cast<float4*>(recB + recSec + (recL + 16u * mt)) = make_float4(th[0], th[1], th[2], th[3]);
-                }
-            }
-            __syncthreads();
-            TL(c, 2);
-            // ================= P2: q = K1 u0 + b1 ; v = tanh(q) . w   (final time: also w . u_1 for Phi) =================
-            mono_gemm<MT, KBM, true>(W2, (mp.lUF >> 2) + lane, acc);
-            TL(c, 3);
-            float pr = 0.f;
-#pragma unroll
-            for (int mi = 0; mi < MT; ++mi) {
-                const int mt = wave + 4 * mi;
-                float4 v;
-                float vv[4], tq[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float q = acc[mi][e] + b1v[mi][e];
-                    tq[e] = tanh_fast(q);
-                    vv[e] = tq[e] * wv[mi][e];
-                    if (fin) pr += wv[mi][e] * (u0k[mi][e] + hN * sigma_act(q));          // src/Phi.py:91-96
-                }
-                v = make_float4(vv[0], vv[1], vv[2], vv[3]);
-                if (mt < KBM) L4[(mp.lVF >> 2) + mt * 64 + lane] = v;
-                if (recEv >= 0 && mt < KBM && 16 * mt + 4 * slot + 3 < pl.m && row0 + (lane & 15) < ra.n)            // activation record: tanh(q)
-                    *reinterpret_cast<float4*>(recB + 2 * recSec + (recL + 16u * mt)) = make_float4(tq[0], tq[1], tq[2], tq[3]);
-            }
-            if (fin) {
-                pr += __shfl_xor(pr, 16); pr += __shfl_xor(pr, 32);
-                if (lane < 16) lds[mp.lPHIP + wave * 16 + lane] = pr;
-            }
-            __syncthreads();
-            TL(c, 4);
-            // z = A s per sample (rows of the physics view): the fixed-order sum of the waves' partials
-            {
-                const int s_ = tid >> 4, row = tid & 15;
-                const float* zp = lds + mp.lZP + ((row >> 2) * 16 + s_) * 4 + (row & 3);
-                lds[pl.lZQ + s_ * ZQLD + row] = ((zp[0] + zp[256]) + zp[512]) + zp[768];
-            }
-            // ================= P3: a = w + hN K1^T v ; y = tanh(o) . a =================
-            mono_gemm<MT, KBM, true>(W3, (mp.lVF >> 2) + lane, acc);
-            TL(c, 5);
-#pragma unroll
-            for (int mi = 0; mi < MT; ++mi) {
-                const int mt = wave + 4 * mi;
-                const float4 a4 = make_float4(wv[mi][0] + hN * acc[mi][0], wv[mi][1] + hN * acc[mi][1], wv[mi][2] + hN * acc[mi][2], wv[mi][3] + hN * acc[mi][3]);
-                float4 y;
-                y.x = th0[mi][0] * a4.x; y.y = th0[mi][1] * a4.y;
-                y.z = th0[mi][2] * a4.z; y.w = th0[mi][3] * a4.w;
-                if (mt < KBM) L4[(mp.lUF >> 2) + mt * 64 + lane] = y;              // u0 is dead: every wave is past the barrier behind P2
-                if (recEv >= 0 && mt < KBM && 16 * mt + 4 * slot + 3 < pl.m && row0 + (lane & 15) < ra.n)            // activation record: a = w + hN K1' v
-                    *reinterpret_cast<float4*>(recB + 3 * recSec + (recL + 16u * mt)) = a4;
-            }
-            __syncthreads();
-            TL(c, 6);
-            // ================= P4: g = K0^T y + A^T z + c, the contraction over the hidden units split over the waves =================
-            {
-                // this wave's share: hidden k-blocks wave, wave+4, ... ; wave 0 adds the low-rank term (k = rows of A, one block)
-                float4 zf = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (wave == 0) {
-                    const float4 z0 = L4[(mp.lZP >> 2) + lane], z1 = L4[(mp.lZP >> 2) + 64 + lane];
-                    const float4 z2 = L4[(mp.lZP >> 2) + 128 + lane], z3 = L4[(mp.lZP >> 2) + 192 + lane];
-                    zf.x = ((z0.x + z1.x) + z2.x) + z3.x; zf.y = ((z0.y + z1.y) + z2.y) + z3.y;
-                    zf.z = ((z0.z + z1.z) + z2.z) + z3.z; zf.w = ((z0.w + z1.w) + z2.w) + z3.w;
-                }
-#pragma unroll
-                for (int dt = 0; dt < KBD; ++dt) {
-                    f32x4 a0, a1;
-                    float4 wf[MT], bf[MT];
-#pragma unroll
-                    for (int mi = 0; mi < MT; ++mi) {
-                        const int kb = wave + 4 * mi;
-                        wf[mi] = L4[(mp.lK4 >> 2) + (dt * KBM + (kb < KBM ? kb : 0)) * 64 + lane];
-                        bf[mi] = L4[(mp.lUF >> 2) + (kb < KBM ? kb : 0) * 64 + lane];
-                        if (kb >= KBM) wf[mi] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (!held) {                                               // (HOLD: a held evaluation goes straight to the physics)
+                TL(c, 1);
+                // ================= P1: o = K0 s + b0, u0 = sigma(o), tanh(o);  z = A s rides along =================
+                f32x4 acc[MT], th0[MT], u0k[MT];
+                mono_gemm<MT, KBD, false>(K1, (mp.lSF >> 2) + lane, acc);
+                {
+                    f32x4 zacc = {0.f, 0.f, 0.f, 0.f};
+                    if (wave < KBD) {
+                        const float4 bz = L4[(mp.lSF >> 2) + wave * 64 + lane];
+                        f32x4 z0, z1;
+                        mfma16_vv0(z0, AZ[0], bz.x); mfma16_vv0(z1, AZ[1], bz.y); mfma16_vv(z0, AZ[2], bz.z); mfma16_vv(z1, AZ[3], bz.w);
+                        asm volatile("s_nop 7\n\ts_nop 4" : "+v"(z0), "+v"(z1));
+                        zacc = z0 + z1;
                     }
-                    const float4 af = L4[(mp.lAT >> 2) + dt * 64 + lane];
+                    L4[(mp.lZP >> 2) + wave * 64 + lane] = make_float4(zacc[0], zacc[1], zacc[2], zacc[3]);     // lane: sample lane%16, rows 4 (lane/16) + e of A
+                }
 #pragma unroll
-                    for (int mi = 0; mi < MT; ++mi) {                          // two chains, started from the inline constant 0
-                        if (mi == 0) { mfma16_vv0(a0, wf[mi].x, bf[mi].x); mfma16_vv0(a1, wf[mi].y, bf[mi].y); }
-                        else { mfma16_vv(a0, wf[mi].x, bf[mi].x); mfma16_vv(a1, wf[mi].y, bf[mi].y); }
-                        mfma16_vv(a0, wf[mi].z, bf[mi].z); mfma16_vv(a1, wf[mi].w, bf[mi].w);
+                for (int mi = 0; mi < MT; ++mi) {
+                    const int mt = wave + 4 * mi;
+                    f32x4 sg, th;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { float s_, t_; act_pair(acc[mi][e] + b0v[mi][e], s_, t_); sg[e] = s_; th[e] = t_; }
+                    th0[mi] = th; u0k[mi] = sg;
+                    if (mt < KBM) L4[(mp.lUF >> 2) + mt * 64 + lane] = make_float4(sg[0], sg[1], sg[2], sg[3]);
+                    if (recEv >= 0 && mt < KBM && 16 * mt + 4 * slot + 3 < pl.m && row0 + (lane & 15) < ra.n) {      // activation record: u0, tanh(o)
+                        *reinterpret_cast<float4*>(recB + (recL + 16u * mt)) = make_float4(sg[0], sg[1], sg[2], sg[3]);
+                        *reinterpret_cast<float4*>(recB + recSec + (recL + 16u * mt)) = make_float4(th[0], th[1], th[2], th[3]);
                     }
-                    if (wave == 0) { mfma16_vv(a0, af.x, zf.x); mfma16_vv(a1, af.y, zf.y); mfma16_vv(a0, af.z, zf.z); mfma16_vv(a1, af.w, zf.w); }
-                    asm volatile("s_nop 7\n\ts_nop 4" : "+v"(a0), "+v"(a1));
-                    const f32x4 ps = a0 + a1;
-                    L4[(mp.lGP >> 2) + (dt * 4 + wave) * 64 + lane] = make_float4(ps[0], ps[1], ps[2], ps[3]);
                 }
-            }
-            __syncthreads();
-            TL(c, 7);
-            const bool g_rows = !quad1 || fin || st >= nstage;  // (singlequad's stage evaluations read the partials themselves)
-            if (g_rows)
-            for (int f = tid; f < KBD * 64; f += 256) {        // fixed-order sum of the four waves' partials, + c, into the gradient rows
-                const int l = f & 63, dt = f >> 6;
-                const float4 p0 = L4[(mp.lGP >> 2) + (dt * 4 + 0) * 64 + l], p1 = L4[(mp.lGP >> 2) + (dt * 4 + 1) * 64 + l];
-                const float4 p2 = L4[(mp.lGP >> 2) + (dt * 4 + 2) * 64 + l], p3 = L4[(mp.lGP >> 2) + (dt * 4 + 3) * 64 + l];
-                const float4 c4 = L4[(mp.lCW >> 2) + dt * 4 + (l >> 4)];
-                float4 gsum;
-                gsum.x = (((p0.x + p1.x) + p2.x) + p3.x) + c4.x; gsum.y = (((p0.y + p1.y) + p2.y) + p3.y) + c4.y;
-                gsum.z = (((p0.z + p1.z) + p2.z) + p3.z) + c4.z; gsum.w = (((p0.w + p1.w) + p2.w) + p3.w) + c4.w;
-                *reinterpret_cast<float4*>(lds + pl.lG + (l & 15) * GLD + 16 * dt + 4 * (l >> 4)) = gsum;
-            }
-            if (fin && tid < T) {
-                // Phi at the final time: w.u_1 (wave partials, fixed order) + 1/2 |A s|^2 + c.s + cb
-                const int s_ = tid;
-                float ph = ((lds[mp.lPHIP + s_] + lds[mp.lPHIP + 16 + s_]) + lds[mp.lPHIP + 32 + s_]) + lds[mp.lPHIP + 48 + s_];
-                float qd = 0.f;
-                for (int q = 0; q < r; ++q) { const float z = lds[pl.lZQ + s_ * ZQLD + q]; qd += 0.5f * z * z; }
-                float lin = 0.f;
-                for (int i = 0; i < D1; ++i) lin += lds[mp.lCW + i] * SB[s_ * LDs + i];
-                lds[pl.lPHI + s_] = ph + qd + lin + pl.cb;
-            }
-            if (g_rows) __syncthreads();
-            if (recEv >= 0 && g_rows) {                                        // activation record: grad Phi from the gradient rows
-                float* gdst = ra.act + 4 * ra.actRows * pl.m + (recEv * ra.n + row0) * D1;
-                for (int jx = tid; jx < T * D1; jx += 256) {
-                    const int t = jx / D1, i = jx - t * D1;
-                    if (row0 + t < ra.n) gdst[t * D1 + i] = lds[pl.lG + t * GLD + i];
+                __syncthreads();
+                TL(c, 2);
+                // ================= P2: q = K1 u0 + b1 ; v = tanh(q) . w   (final time: also w . u_1 for Phi) =================
+                mono_gemm<MT, KBM, true>(W2, (mp.lUF >> 2) + lane, acc);
+                TL(c, 3);
+                float pr = 0.f;
+#pragma unroll
+                for (int mi = 0; mi < MT; ++mi) {
+                    const int mt = wave + 4 * mi;
+                    float4 v;
+                    float vv[4], tq[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float q = acc[mi][e] + b1v[mi][e];
+                        tq[e] = tanh_fast(q);
+                        vv[e] = tq[e] * wv[mi][e];
+                        if (fin) pr += wv[mi][e] * (u0k[mi][e] + hN * sigma_act(q));          // src/Phi.py:91-96
+                    }
+                    v = make_float4(vv[0], vv[1], vv[2], vv[3]);
+                    if (mt < KBM) L4[(mp.lVF >> 2) + mt * 64 + lane] = v;
+                    if (recEv >= 0 && mt < KBM && 16 * mt + 4 * slot + 3 < pl.m && row0 + (lane & 15) < ra.n)            // activation record: tanh(q)
+                        *reinterpret_cast<float4*>(recB + 2 * recSec + (recL + 16u * mt)) = make_float4(tq[0], tq[1], tq[2], tq[3]);
                 }
+                if (fin) {
+                    pr += __shfl_xor(pr, 16); pr += __shfl_xor(pr, 32);
+                    if (lane < 16) lds[mp.lPHIP + wave * 16 + lane] = pr;
+                }
+                __syncthreads();
+                TL(c, 4);
+                // z = A s per sample (rows of the physics view): the fixed-order sum of the waves' partials
+                {
+                    const int s_ = tid >> 4, row = tid & 15;
+                    const float* zp = lds + mp.lZP + ((row >> 2) * 16 + s_) * 4 + (row & 3);
+                    lds[pl.lZQ + s_ * ZQLD + row] = ((zp[0] + zp[256]) + zp[512]) + zp[768];
+                }
+                // ================= P3: a = w + hN K1^T v ; y = tanh(o) . a =================
+                mono_gemm<MT, KBM, true>(W3, (mp.lVF >> 2) + lane, acc);
+                TL(c, 5);
+#pragma unroll
+                for (int mi = 0; mi < MT; ++mi) {
+                    const int mt = wave + 4 * mi;
+                    const float4 a4 = make_float4(wv[mi][0] + hN * acc[mi][0], wv[mi][1] + hN * acc[mi][1], wv[mi][2] + hN * acc[mi][2], wv[mi][3] + hN * acc[mi][3]);
+                    float4 y;
+                    y.x = th0[mi][0] * a4.x; y.y = th0[mi][1] * a4.y;
+                    y.z = th0[mi][2] * a4.z; y.w = th0[mi][3] * a4.w;
+                    if (mt < KBM) L4[(mp.lUF >> 2) + mt * 64 + lane] = y;              // u0 is dead: every wave is past the barrier behind P2
+                    if (recEv >= 0 && mt < KBM && 16 * mt + 4 * slot + 3 < pl.m && row0 + (lane & 15) < ra.n)            // activation record: a = w + hN K1' v
+                        *reinterpret_cast<float4*>(recB + 3 * recSec + (recL + 16u * mt)) = a4;
+                }
+                __syncthreads();
+                TL(c, 6);
+                // ================= P4: g = K0^T y + A^T z + c, the contraction over the hidden units split over the waves =================
+                {
+                    // this wave's share: hidden k-blocks wave, wave+4, ... ; wave 0 adds the low-rank term (k = rows of A, one block)
+                    float4 zf = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (wave == 0) {
+                        const float4 z0 = L4[(mp.lZP >> 2) + lane], z1 = L4[(mp.lZP >> 2) + 64 + lane];
+                        const float4 z2 = L4[(mp.lZP >> 2) + 128 + lane], z3 = L4[(mp.lZP >> 2) + 192 + lane];
+                        zf.x = ((z0.x + z1.x) + z2.x) + z3.x; zf.y = ((z0.y + z1.y) + z2.y) + z3.y;
+                        zf.z = ((z0.z + z1.z) + z2.z) + z3.z; zf.w = ((z0.w + z1.w) + z2.w) + z3.w;
+                    }
+#pragma unroll
+                    for (int dt = 0; dt < KBD; ++dt) {
+                        f32x4 a0, a1;
+                        float4 wf[MT], bf[MT];
+#pragma unroll
+                        for (int mi = 0; mi < MT; ++mi) {
+                            const int kb = wave + 4 * mi;
+                            wf[mi] = L4[(mp.lK4 >> 2) + (dt * KBM + (kb < KBM ? kb : 0)) * 64 + lane];
+                            bf[mi] = L4[(mp.lUF >> 2) + (kb < KBM ? kb : 0) * 64 + lane];
+                            if (kb >= KBM) wf[mi] = make_float4(0.f, 0.f, 0.f, 0.f);
+                        }
+                        const float4 af = L4[(mp.lAT >> 2) + dt * 64 + lane];
+#pragma unroll
+                        for (int mi = 0; mi < MT; ++mi) {                          // two chains, started from the inline constant 0
+                            if (mi == 0) { mfma16_vv0(a0, wf[mi].x, bf[mi].x); mfma16_vv0(a1, wf[mi].y, bf[mi].y); }
+                            else { mfma16_vv(a0, wf[mi].x, bf[mi].x); mfma16_vv(a1, wf[mi].y, bf[mi].y); }
+                            mfma16_vv(a0, wf[mi].z, bf[mi].z); mfma16_vv(a1, wf[mi].w, bf[mi].w);
+                        }
+                        if (wave == 0) { mfma16_vv(a0, af.x, zf.x); mfma16_vv(a1, af.y, zf.y); mfma16_vv(a0, af.z, zf.z); mfma16_vv(a1, af.w, zf.w); }
+                        asm volatile("s_nop 7\n\ts_nop 4" : "+v"(a0), "+v"(a1));
+                        const f32x4 ps = a0 + a1;
+                        L4[(mp.lGP >> 2) + (dt * 4 + wave) * 64 + lane] = make_float4(ps[0], ps[1], ps[2], ps[3]);
+                    }
+                }
+                __syncthreads();
+                TL(c, 7);
+                // (singlequad's stage evaluations read the partials themselves; HOLD with intermediates: ctrl_write reads the held p[9..11] from the rows)
+                const bool g_rows = !quad1 || fin || st >= nstage || (HOLD && ra.zFull);
+                if (g_rows)
+                for (int f = tid; f < KBD * 64; f += 256) {        // fixed-order sum of the four waves' partials, + c, into the gradient rows
+                    const int l = f & 63, dt = f >> 6;
+                    const float4 p0 = L4[(mp.lGP >> 2) + (dt * 4 + 0) * 64 + l], p1 = L4[(mp.lGP >> 2) + (dt * 4 + 1) * 64 + l];
+                    const float4 p2 = L4[(mp.lGP >> 2) + (dt * 4 + 2) * 64 + l], p3 = L4[(mp.lGP >> 2) + (dt * 4 + 3) * 64 + l];
+                    const float4 c4 = L4[(mp.lCW >> 2) + dt * 4 + (l >> 4)];
+                    float4 gsum;
+                    gsum.x = (((p0.x + p1.x) + p2.x) + p3.x) + c4.x; gsum.y = (((p0.y + p1.y) + p2.y) + p3.y) + c4.y;
+                    gsum.z = (((p0.z + p1.z) + p2.z) + p3.z) + c4.z; gsum.w = (((p0.w + p1.w) + p2.w) + p3.w) + c4.w;
+                    *reinterpret_cast<float4*>(lds + pl.lG + (l & 15) * GLD + 16 * dt + 4 * (l >> 4)) = gsum;
+                }
+                if (fin && tid < T) {
+                    // Phi at the final time: w.u_1 (wave partials, fixed order) + 1/2 |A s|^2 + c.s + cb
+                    const int s_ = tid;
+                    float ph = ((lds[mp.lPHIP + s_] + lds[mp.lPHIP + 16 + s_]) + lds[mp.lPHIP + 32 + s_]) + lds[mp.lPHIP + 48 + s_];
+                    float qd = 0.f;
+                    for (int q = 0; q < r; ++q) { const float z = lds[pl.lZQ + s_ * ZQLD + q]; qd += 0.5f * z * z; }
+                    float lin = 0.f;
+                    for (int i = 0; i < D1; ++i) lin += lds[mp.lCW + i] * SB[s_ * LDs + i];
+                    lds[pl.lPHI + s_] = ph + qd + lin + pl.cb;
+                }
+                if (g_rows) __syncthreads();
+                if (recEv >= 0 && g_rows) {                                        // activation record: grad Phi from the gradient rows
+                    float* gdst = ra.act + 4 * ra.actRows * pl.m + (recEv * ra.n + row0) * D1;
+                    for (int jx = tid; jx < T * D1; jx += 256) {
+                        const int t = jx / D1, i = jx - t * D1;
+                        if (row0 + t < ra.n) gdst[t * D1 + i] = lds[pl.lG + t * GLD + i];
+                    }
+                }
+                if (fin) break;
             }
-            if (fin) break;
 
             TL(c, 8);
             // ================= one quadcopter per sample (singlequad): physics + RK wave-locally, 16 lanes per sample =================
@@ -607,7 +626,8 @@ __global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __res
                 const float f8 = -cps * sph + sps * sth * cph;
                 const float f9 = cth * cph;
                 const float fsum = f7 * pv[6] + f8 * pv[7] + f9 * pv[8];
-                const float u = (float)(-1.0 / (2.0 * pb.mass)) * fsum;
+                float u = (float)(-1.0 / (2.0 * pb.mass)) * fsum;
+                if constexpr (HOLD) { if (held) u = uh; else uh = u; }        // (the thrust of the sampling instant; f7..f9 above are the current angles')
                 const float sq = pv[9] * pv[9] + pv[10] * pv[10] + pv[11] * pv[11];
                 float Lg = (float)pb.alphQ * 0.f;                              // Quadcopter.py:116-122: no obstacle implemented; one craft: W = 0
                 Lg = Lg + 2.f + u * u + 0.25f * sq;
@@ -621,14 +641,14 @@ __global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __res
                     if (nstage == 1) tnext = t1k;
                     else tnext = (st < 2) ? (tk + hsd / 2) : (st == 2 ? (tk + hsd) : t1k);
                     const bool last = (st == nstage - 1);
-                    if (last && ra.zFull) tnext = t1k - sg_h;
+                    if (last && ra.zFull && !HOLD) tnext = t1k - sg_h;
                     // (selects over named registers: a lane-indexed xv[6 + j] would become a loop over the lanes' distinct indices;
                     // every candidate is formed first so that the choice compiles to v_cndmask, not to a ladder of branches)
                     const float xsel = j == 0 ? xv[6] : j == 1 ? xv[7] : j == 2 ? xv[8] : j == 3 ? xv[9] : j == 4 ? xv[10] : xv[11];
                     const float psel = -0.5f * (j == 9 ? pv[9] : (j == 10 ? pv[10] : pv[11]));
                     const float f7u = um * f7, f8u = um * f8, f9u = um * f9 - grav;
                     const float fsel = j == 6 ? f7u : (j == 7 ? f8u : f9u);
-                    const float hj = fabsf(pv[12] - H);
+                    const float hj = HOLD ? 0.f : fabsf(pv[12] - H);          // (a held control has no HJB residual)
                     float dzi = 0.f;                                           // Q, W
                     dzi = (j == 13) ? hj : dzi;
                     dzi = (j == 12) ? Lg : dzi;
@@ -659,6 +679,12 @@ __global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __res
                     lds[mp.lSF + ((j >> 2) * 16 + s_) * 4 + (j & 3)] = (j < 12) ? xs_ : (j == 12 ? tn : 0.f);
                     sf_ready = true;
                     if (last && ra.zFull && row0 + s_ < ra.n) ra.zFull[((sg_slot + k + 1) * ra.n + row0 + s_) * (d + 4) + j] = xs_;
+                    if constexpr (HOLD) {
+                        if (last && ra.zFull) {                                // the control applied over step k: the held thrust (SC) and -p[9..11] / 2 (Gl)
+                            __syncthreads();
+                            ctrl_write(c, pl, pb, ra.ctrlFull + (sg_slot + k + 1) * ra.n * ra.cdim, row0, ra.n, ra.cdim);
+                        }
+                    }
                 } else {
                     __syncthreads();
                     ctrl_write(c, pl, pb, ra.ctrlFull + (sg_slot + k + 1) * ra.n * ra.cdim, row0, ra.n, ra.cdim);
@@ -677,12 +703,12 @@ __global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __res
                 if (nstage == 1) tnext = t1k;
                 else tnext = (st < 2) ? (tk + hsd / 2) : (st == 2 ? (tk + hsd) : t1k);
                 const bool last = (st == nstage - 1);
-                if (last && ra.zFull) tnext = t1k - sg_h;      // with intermediates the next evaluation is the control at (z_{k+1}, (tk+h)-h)
+                if (last && ra.zFull && !HOLD) tnext = t1k - sg_h;      // with intermediates the next evaluation is the control at (z_{k+1}, (tk+h)-h)
                 if (tid < T) {
                     const int s_ = tid;
                     const Costs cs = physics_finish(c, pl, pb, s_);          // quadcopter: also -grad_p H -> DZ rows, thrusts -> SC
                     DZ[s_ * ZLD + d] = cs.L;
-                    DZ[s_ * ZLD + d + 1] = fabsf(Gl[s_ * GLD + d] - cs.H);
+                    DZ[s_ * ZLD + d + 1] = HOLD ? 0.f : fabsf(Gl[s_ * GLD + d] - cs.H);
                     DZ[s_ * ZLD + d + 2] = cs.Q;
                     DZ[s_ * ZLD + d + 3] = cs.W;
                 }
@@ -728,6 +754,9 @@ __global__ void __launch_bounds__(256) rollout_mono_kernel(const MonoPlan* __res
                     if (last && ra.zFull && row0 + t < ra.n) ra.zFull[((sg_slot + k + 1) * ra.n + row0 + t) * (d + 4) + i] = xs;
                 }
                 if (tid < T) SB[tid * LDs + d] = (float)tnext;
+                if constexpr (HOLD) {                          // the control applied over step k: the held -p of the gradient rows
+                    if (last && ra.zFull) ctrl_write(c, pl, pb, ra.ctrlFull + (sg_slot + k + 1) * ra.n * ra.cdim, row0, ra.n, ra.cdim);
+                }
             } else {
                 if (quad && tid < T) (void)physics_finish(c, pl, pb, tid);         // thrusts for calcCtrls
                 if (quad) __syncthreads();

@@ -20,6 +20,18 @@ def _tool(name):
     return shutil.which(name) or "/opt/rocm/llvm/bin/" + name
 
 
+# rollout_lane_kernel / rollout_mono_kernel gained a trailing template parameter HOLD; an instantiation without it
+# keeps the spelling it had before, so this table and its siblings' (tools/noise_corr_resources.py) still name it
+_HOLD_OFF = re.compile(r"^(rollout_lane_kernel<(?:[^,<>]+, ){5}[^,<>]+|rollout_mono_kernel<(?:[^,<>]+, ){4}[^,<>]+), false>$")
+
+
+def spelling(name):
+    """the demangled kernel name without its argument list, HOLD = false dropped"""
+    name = re.sub(r"^void |\(.*$", "", name)
+    m = _HOLD_OFF.match(name)
+    return m.group(1) + ">" if m else name
+
+
 def kernels(path):
     """demangled kernel name -> (V, A, S, scratch, occupancy, sS, vS)"""
     text = subprocess.run([_tool("llvm-readelf"), "--notes", path], capture_output=True, text=True, check=True).stdout
@@ -34,7 +46,7 @@ def kernels(path):
         names.append(re.search(r"(?m)^\s*\.name:\s*(\S+)", blk).group(1))
         rows.append((v - a, a, s, scr, min(8, 512 // max(total, 8)), ss, vs))
     plain = subprocess.run([shutil.which("llvm-cxxfilt") or shutil.which("c++filt") or "c++filt"], input="\n".join(names), capture_output=True, text=True, check=True).stdout.split("\n")
-    return {re.sub(r"^void |\(.*$", "", p): r for p, r in zip(plain, rows)}
+    return {spelling(p): r for p, r in zip(plain, rows)}
 
 
 def fmt(r):
