@@ -24,20 +24,35 @@ def ocG(z, xtarget):
     return z[:, 0:d] - xtarget
 
 
-def _launch64(x, Phi, prob, tspan, nt, stepper, alph, intermediates):
-    """the double-precision rollout (nocf_rollout_f64): the reference's --prec double (evalOC.py:19,28-31)"""
-    x = _lib.require_device_f64(x, "x")
+def _check_args(x, Phi, nt, stepper, alph, rows=False, W=None):
+    """the argument checks of every single-network rollout call -> (n, d).  rows: an empty batch is refused too; W: a disturbance tensor,
+    held against nt-by-nex-by-d and x's device"""
     if x.dim() != 2:
         raise ValueError("x must be nex-by-d")
     n, d = x.shape
     if d != Phi.d:
         raise ValueError(f"x has d={d} but Phi was built for d={Phi.d}")
     if int(nt) < 1:
+        # the reference divides by zero here (src/OCflow.py:25); SURVEY 8a note 10
         raise ValueError("nt must be >= 1")
+    if rows and n < 1:
+        raise ValueError("x has no rows")
+    if W is not None and tuple(W.shape) != (int(nt), n, d):
+        raise ValueError(f"W must be nt-by-nex-by-d = {(int(nt), n, d)}, got {tuple(W.shape)}")
+    if W is not None and W.device != x.device:
+        raise ValueError("x and W must be on the same device")
     if stepper not in _STEPPERS:
+        # the reference silently integrates nothing for an unknown stepper (src/OCflow.py:46-49)
         raise ValueError(f"stepper must be 'rk4' or 'rk1', got {stepper!r}")
     if len(alph) < 6:
         raise ValueError("alph needs 6 entries")
+    return n, d
+
+
+def _launch64(x, Phi, prob, tspan, nt, stepper, alph, intermediates):
+    """the double-precision rollout (nocf_rollout_f64): the reference's --prec double (evalOC.py:19,28-31)"""
+    x = _lib.require_device_f64(x, "x")
+    n, d = _check_args(x, Phi, nt, stepper, alph)
     # (only the mean path is differentiable -- OCflow routes it to train._OCflowTrain64 before it gets here; noMean / intermediates under
     # autograd raise like the single-precision launch does, instead of returning detached tensors)
     Phi._guard_no_autograd(x, "OCflow")
@@ -62,61 +77,82 @@ def _launch64(x, Phi, prob, tspan, nt, stepper, alph, intermediates):
     return persample, sums, zFull, ctrlFull
 
 
-def _launch(x, Phi, prob, tspan, nt, stepper, alph, intermediates, means=None):
-    """run the HIP rollout; returns (persample [n,7], sums [8], zFull_tm, ctrlFull_tm).  means: an 8-float device tensor that the same
-    launch sequence fills with the 7 batch means and Jc (nocf_rollout_means_f32: for callers without an all-reduce behind the sums)"""
-    if isinstance(x, torch.Tensor) and x.dtype == torch.float64:
-        return _launch64(x, Phi, prob, tspan, nt, stepper, alph, intermediates)
+_NO_W = object()                                           # (the entry takes no disturbance tensor; None: it takes one and the caller has none)
+
+
+def _evaluate(what, name, x, Phi, prob, tspan, nt, stepper, alph, intermediates, extra=(), W=_NO_W, shipped=False, shape_error=None,
+              plain=False, means=None):
+    """One single-network evaluation call, shared by OCflow, disturbed_rollout, noisy_rollout and held_rollout: the argument checks, the
+    buffers, the call of entry `name`, its return code and the rollout status -> (means [8], persample [n, 7], sums [8], z_final [n, d+4],
+    zFull, ctrlFull), the last two time-major, or None without intermediates.  Nothing touches a device before every check has passed.
+    W, extra: what the entry takes between x and n -- the disturbance tensor (checked here) and then the entries of extra; host tensors
+              among them travel to x's device behind the checks
+    shipped:  the entry lives in the shipped library only (otherwise: the shape's library, the shipped one when that is an older build)
+    shape_error: raised in place of NOCF_E_SHAPE
+    plain:    OCflow's own call.  An empty batch is the library's to refuse; there is no z_final; `means` is the caller's buffer or None
+              (nocf_rollout_f32 has no slot for it); a per-shape library cached before nocf_rollout_means_f32 existed runs nocf_rollout_f32
+              and then fills `means` itself; only this call can reach the split-role kernel, so only it is under _lib.duo_guard; and the
+              caller decides whether to wait for the status"""
     x = _lib.require_device_f32(x, "x")
-    if x.dim() != 2:
-        raise ValueError("x must be nex-by-d")
-    n, d = x.shape
-    if d != Phi.d:
-        raise ValueError(f"x has d={d} but Phi was built for d={Phi.d}")
-    if int(nt) < 1:
-        # the reference divides by zero here (src/OCflow.py:25); SURVEY 8a note 10
-        raise ValueError("nt must be >= 1")
-    if stepper not in _STEPPERS:
-        # the reference silently integrates nothing for an unknown stepper (src/OCflow.py:46-49)
-        raise ValueError(f"stepper must be 'rk4' or 'rk1', got {stepper!r}")
-    if len(alph) < 6:
-        raise ValueError("alph needs 6 entries")
-    Phi._guard_no_autograd(x, "OCflow")
+    if W is not _NO_W and W is not None:
+        W = _lib.require_device_f32(W, "W")
+    n, d = _check_args(x, Phi, nt, stepper, alph, rows=not plain, W=None if W is _NO_W else W)
+    Phi._guard_no_autograd(x, what)
     _lib.check_errors()                                    # a failed earlier rollout whose status has arrived raises here
     phi_st, keep1, ws = Phi._c_struct(n)
     prob_st, keep2 = prob._c_struct(x.device)
     dev = x.device
     persample = torch.empty(n, 7, dtype=torch.float32, device=dev)
     sums = torch.empty(8, dtype=torch.float32, device=dev)
+    z_final = None
+    if not plain:
+        means = torch.empty(8, dtype=torch.float32, device=dev)
+        z_final = torch.empty(n, d + 4, dtype=torch.float32, device=dev)
     zFull = ctrlFull = None
     if intermediates:
         cdim = _lib.lib().nocf_ctrl_dim(C.byref(prob_st), d)
         zFull = torch.empty(nt + 1, n, d + 4, dtype=torch.float32, device=dev)
         ctrlFull = torch.empty(nt + 1, n, cdim, dtype=torch.float32, device=dev)
     alph_c = (C.c_float * 6)(*[float(a) for a in alph[:6]])
+    between = (() if W is _NO_W else (W,)) + tuple(t.to(dev) if isinstance(t, torch.Tensor) else t for t in extra)
+    entry, old = name, False
     with torch.cuda.device(dev):
-        L = _lib.lib_for(Phi.d, Phi.m, Phi.nTh, phi_st.r, prob_st.n_agents, fwd=prob_st.kind != _lib.PROB_QUADCOPTER)
-        if means is not None and hasattr(L, "nocf_rollout_means_f32"):
-            rc = L.nocf_rollout_means_f32(C.byref(phi_st), C.byref(prob_st), _lib.ptr(x), n,
-                                          float(tspan[0]), float(tspan[1]), int(nt), _STEPPERS[stepper], alph_c,
-                                          None, _lib.ptr(persample), _lib.ptr(sums), _lib.ptr(means),
-                                          _lib.ptr(zFull), _lib.ptr(ctrlFull),
-                                          _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+        if shipped:
+            L = _lib.lib()
+            (f,) = _lib.require(L, (entry,), what)
         else:
-            rc = L.nocf_rollout_f32(C.byref(phi_st), C.byref(prob_st), _lib.ptr(x), n,
-                                    float(tspan[0]), float(tspan[1]), int(nt), _STEPPERS[stepper], alph_c,
-                                    None, _lib.ptr(persample), _lib.ptr(sums),
-                                    _lib.ptr(zFull), _lib.ptr(ctrlFull),
-                                    _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-            if means is not None and rc == 0:
-                # a per-shape library cached before nocf_rollout_means_f32 existed: the library that RAN fills `means` with its own
-                # nocf_cost_means_f32 (every build has it), so the caller never sees an unwritten buffer
-                rc = L.nocf_cost_means_f32(_lib.ptr(sums), alph_c, _lib.ptr(means), _lib.stream_ptr(dev))
-    _lib.check(rc, "nocf_rollout_f32")
-    _lib.track_rollout_status(L, dev, "OCflow")
-    if _lib.duo_guard(L, "OCflow"):
-        return _launch(x, Phi, prob, tspan, nt, stepper, alph, intermediates, means)
-    return persample, sums, zFull, ctrlFull
+            L = _lib.lib_for(Phi.d, Phi.m, Phi.nTh, phi_st.r, prob_st.n_agents, fwd=prob_st.kind != _lib.PROB_QUADCOPTER)
+            old = plain and means is not None and not hasattr(L, entry)
+            if old:
+                entry = "nocf_rollout_f32"
+            L, (f,) = _lib.entry_for(L, (entry,), what)
+        outs = (z_final, persample, sums) + (() if entry == "nocf_rollout_f32" else (means,)) + (zFull, ctrlFull)
+        # (the workspace is a uint8 tensor, Phi._pool_get: numel() is its size in bytes)
+        rc = f(C.byref(phi_st), C.byref(prob_st), _lib.ptr(x), *[_lib.ptr(t) if isinstance(t, torch.Tensor) else t for t in between], n,
+               float(tspan[0]), float(tspan[1]), int(nt), _STEPPERS[stepper], alph_c, *[_lib.ptr(t) for t in outs],
+               _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+        if old and rc == 0:
+            # the library that RAN fills `means` with its own nocf_cost_means_f32 (every build has it): the caller never sees an unwritten buffer
+            rc = L.nocf_cost_means_f32(_lib.ptr(sums), alph_c, _lib.ptr(means), _lib.stream_ptr(dev))
+    if rc == -2 and shape_error is not None:               # NOCF_E_SHAPE: refused before anything was enqueued
+        raise shape_error
+    _lib.check(rc, "nocf_rollout_f32" if plain else entry)
+    _lib.track_rollout_status(L, dev, what)
+    if plain and _lib.duo_guard(L, what):
+        return _evaluate(what, name, x, Phi, prob, tspan, nt, stepper, alph, intermediates, plain=True, means=means)
+    if intermediates and not plain:
+        _lib.check_errors(sync=True)                       # consumed on the host (plots, files): a failed launch raises here
+    return means, persample, sums, z_final, zFull, ctrlFull
+
+
+def _launch(x, Phi, prob, tspan, nt, stepper, alph, intermediates, means=None):
+    """run the HIP rollout; returns (persample [n,7], sums [8], zFull_tm, ctrlFull_tm).  means: an 8-float device tensor that the same
+    launch sequence fills with the 7 batch means and Jc (nocf_rollout_means_f32: for callers without an all-reduce behind the sums)"""
+    if isinstance(x, torch.Tensor) and x.dtype == torch.float64:
+        return _launch64(x, Phi, prob, tspan, nt, stepper, alph, intermediates)
+    name = "nocf_rollout_f32" if means is None else "nocf_rollout_means_f32"
+    out = _evaluate("OCflow", name, x, Phi, prob, tspan, nt, stepper, alph, intermediates, plain=True, means=means)
+    return out[1], out[2], out[4], out[5]
 
 
 MAX_SEGMENTS = 16

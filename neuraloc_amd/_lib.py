@@ -217,184 +217,187 @@ def lib_for(d, m, nTh, r, n_agents, fwd=False):
     return L
 
 
+# ---- the prototypes of include/nocf.h, by hand: PROTOTYPES[name] = (restype, argtypes) of every entry point the package binds.
+# tests/test_prototypes_cpu.py holds the table against the header, argument by argument.  The blocks most entries are made of:
+_i32, _i64, _u64, _dbl, _vp, _sz = C.c_int32, C.c_int64, C.c_uint64, C.c_double, C.c_void_p, C.c_size_t
+_pi32, _pdbl = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+_PHI, _PROB, _PHI64, _PROB64 = C.POINTER(NocfPhi), C.POINTER(NocfProb), C.POINTER(NocfPhi64), C.POINTER(NocfProb64)
+_HEAD = [_PHI, _PROB, _vp]                                       # phi, prob, x
+_TIME = [_dbl, _dbl, _i32, _i32, fp]                             # t0, t1, nt, stepper, alph
+_TAIL = [_vp, _sz, _vp]                                          # workspace, its bytes, stream
+_EVAL = [_vp] * 6                                                # z_final, persample, sums, means, zFull, ctrlFull
+_REC = [_vp] * 5 + [_pi32]                                       # z_final, persample, sums, s_all, act, recorded
+_ADJ = [_PHI, _PROB, _i64, _i32, _i32, _dbl, fp, _dbl] + [_vp] * 3       # phi, prob, n, nt, stepper, t1, alph, inv_n, s_all, z_final, hs
+_ADJ_RW = _ADJ[:7] + [_vp] + _ADJ[8:]                            # ... with `const float* wrow` where `double inv_n` stands
+_HEAD64 = [_PHI64, _PROB64, _vp, _i64, _dbl, _dbl, _i32, _i32, _pdbl]    # phi, prob, x, n, t0, t1, nt, stepper, alph
+_FLOATS = [_i32, _i32, _i32, _i64, _i32, _i32]                   # d, m, nTh, n, nt, stepper
+_BASE = [_i32, _i64, _i32, _dbl]                                 # (behind prob) d, n, nt, ...: the baseline solvers' common start
+_ADAM = _BASE + [_dbl] * 4 + [_i32, _i32] + [_vp] * 8
+_LBFGS = _BASE + [_dbl, _i32, _i32, _dbl, _dbl, _i32] + [_vp] * 6 + _TAIL
+_NOISE = [_vp, _u64, _i64]                                       # scale, seed, row0 (behind x)
+_NOISE_CORR = [_vp] * 3 + [_u64, _i64]                           # scale0, scale1, rho, seed, row0
+# the ensemble entries: x_member_stride behind (n, members), one alph row per member (a device table, not six host floats)
+_ENS = _HEAD + [_i64, _i32, _i64] + [_dbl, _dbl, _i32, _i32, _vp]
+_ENS_NOISY = _ENS[:6] + [_vp, _vp, _i64] + _ENS[6:]              # ... scale [E, d], seeds [E], row0
+_ENS_W = _ENS[:6] + [_vp, _i64] + _ENS[6:]                       # ... W, w_member_stride
+_ENS_ADJ = [_PHI, _PROB, _i64, _i32, _i32, _i32, _dbl, _vp, _dbl] + [_vp] * 3    # phi, prob, n, members, nt, stepper, t1, alph, inv_n, s_all, z_final, hs
+_ENS_ADJ_RW = _ENS_ADJ[:8] + [_vp] + _ENS_ADJ[9:]
+
+PROTOTYPES = {
+    "nocf_version": (C.c_int, []),
+    "nocf_set_knob": (C.c_int, [C.c_char_p, _i32, _i32]),
+    "nocf_last_rollout_kernel": (C.c_char_p, []),
+    "nocf_last_rollout_status_async": (C.c_int, [_vp, _vp]),
+    "nocf_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "nocf_rollout_workspace_bytes": (_sz, [_i32, _i32, _i32, _i64]),
+    "nocf_ctrl_dim": (C.c_int, [_PROB, _i32]),
+    # single-network rollouts: evaluation ...
+    "nocf_rollout_f32": (C.c_int, _HEAD + [_i64] + _TIME + [_vp] * 5 + _TAIL),
+    "nocf_rollout_means_f32": (C.c_int, _HEAD + [_i64] + _TIME + _EVAL + _TAIL),
+    "nocf_rollout_segments_f32": (C.c_int, _HEAD + [_i64, _i32, _i64, _pdbl, _dbl, _pi32, _pi32, _i32, fp] + [_vp] * 5 + _TAIL),
+    "nocf_segments_supported": (C.c_int, [_PHI, _PROB]),
+    "nocf_rollout_disturbed_f32": (C.c_int, _HEAD + [_vp, _i64] + _TIME + _EVAL + _TAIL),
+    "nocf_rollout_held_f32": (C.c_int, _HEAD + [_vp, _i32, _i64] + _TIME + _EVAL + _TAIL),
+    "nocf_rollout_noisy_f32": (C.c_int, _HEAD + _NOISE + [_i64] + _TIME + _EVAL + _TAIL),
+    "nocf_rollout_noisy_corr_f32": (C.c_int, _HEAD + _NOISE_CORR + [_i64] + _TIME + _EVAL + _TAIL),
+    "nocf_noise_fill_f32": (C.c_int, [_vp, _i64, _i32, _i32] + _NOISE + [_vp]),
+    "nocf_noise_fill_corr_f32": (C.c_int, [_vp, _i64, _i32, _i32] + _NOISE_CORR + [_vp]),
+    "nocf_cost_means_f32": (C.c_int, [_vp, fp, _vp, _vp]),
+    # ... the recording forwards ...
+    "nocf_rollout_record_f32": (C.c_int, _HEAD + [_i64] + _TIME + [_vp] * 4 + _TAIL),
+    "nocf_rollout_record_act_f32": (C.c_int, _HEAD + [_i64] + _TIME + _REC + _TAIL),
+    "nocf_rollout_tape_f32": (C.c_int, _HEAD + [_i64] + _TIME + _REC + _TAIL),
+    "nocf_rollout_record_disturbed_f32": (C.c_int, _HEAD + [_vp, _i64] + _TIME + _REC + _TAIL),
+    "nocf_rollout_record_noisy_f32": (C.c_int, _HEAD + _NOISE + [_i64] + _TIME + _REC + _TAIL),
+    "nocf_rollout_record_noisy_corr_f32": (C.c_int, _HEAD + _NOISE_CORR + [_i64] + _TIME + _REC + _TAIL),
+    "nocf_activation_record_floats": (_sz, _FLOATS),
+    "nocf_tape_floats": (_sz, _FLOATS),
+    # ... and the adjoints
+    "nocf_small_grad_floats": (_i64, [_i32, _i32]),
+    "nocf_mid_grad_rows": (_i64, [_i32] * 5 + [_i64]),
+    "nocf_rollout_bwd_small_f32": (C.c_int, _ADJ + [_vp] * 3),
+    "nocf_rollout_bwd_mid_f32": (C.c_int, _ADJ + [_vp, _vp, _i64, _vp] + _TAIL),
+    "nocf_rollout_bwd_f32": (C.c_int, _ADJ + [_vp] * 11 + _TAIL),
+    "nocf_rollout_bwd_act_f32": (C.c_int, _ADJ + [_vp] * 12 + _TAIL),
+    "nocf_rollout_bwd_small_w_f32": (C.c_int, _ADJ + [_vp] * 4),
+    "nocf_rollout_bwd_mid_w_f32": (C.c_int, _ADJ + [_vp, _vp, _i64, _vp, _vp] + _TAIL),
+    "nocf_rollout_bwd_act_w_f32": (C.c_int, _ADJ + [_vp] * 13 + _TAIL),
+    "nocf_rollout_bwd_small_rw_f32": (C.c_int, _ADJ_RW + [_vp] * 3),
+    "nocf_rollout_bwd_mid_rw_f32": (C.c_int, _ADJ_RW + [_vp, _vp, _i64, _vp] + _TAIL),
+    "nocf_rollout_bwd_act_rw_f32": (C.c_int, _ADJ_RW + [_vp] * 12 + _TAIL),
+    "nocf_rollout_bwd_states_f32": (C.c_int, _ADJ + [_vp] * 3 + _TAIL),
+    "nocf_disturbance_ascent_f32": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _dbl, _dbl, _vp]),
+    "nocf_rollout_bwd_tape_f32": (C.c_int, [_PHI, _PROB, _i64, _i32, _i32, fp, _dbl] + [_vp] * 11 + [_vp, _vp, _vp, _sz, _pi32] + _TAIL),
+    "nocf_rollout_bwd_tape_sums_f32": (C.c_int, [_PHI, _PROB, _i64, _i32, _i32, fp, _dbl] + [_vp] * 10 + [_vp, _vp, _vp, _sz, _pi32] +
+                                       [_vp, _sz] + _TAIL),
+    "nocf_dw_scratch_floats": (_sz, []),
+    "nocf_bwd_colsum_floats": (_sz, [_i64]),
+    "nocf_poison_if_failed_f32": (C.c_int, [_vp, _i64, _vp]),
+    "nocf_contract_f32": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i32] + _TAIL),
+    "nocf_colsum_f32": (C.c_int, [_vp, _i64, _i32, _vp, _i32] + _TAIL),
+    # Phi alone, the problem alone
+    "nocf_phi_forward_f32": (C.c_int, [_PHI, _vp, _i64, _vp] + _TAIL),
+    "nocf_phi_grad_f32": (C.c_int, [_PHI, _vp, _i64, _vp] + _TAIL),
+    "nocf_phi_value_bwd_f32": (C.c_int, [_PHI, _vp, _i64, _vp] + [_vp] * 9 + _TAIL),
+    "nocf_phi_grad_bwd_f32": (C.c_int, [_PHI, _vp, _i64, _vp, _vp] + [_vp] * 9 + _TAIL),
+    "nocf_prob_eval_f32": (C.c_int, [_PROB, _i32, _vp, _vp, _i64] + [_vp] * 4),
+    # ensembles: lane family, one-CU family, their weighted / noisy / disturbed siblings
+    "nocf_rollout_ensemble_f32": (C.c_int, _ENS + _EVAL + _TAIL),
+    "nocf_rollout_record_ensemble_f32": (C.c_int, _ENS + [_vp] * 4 + _TAIL),
+    "nocf_rollout_bwd_small_ensemble_f32": (C.c_int, _ENS_ADJ + [_vp] * 3),
+    "nocf_mid_ensemble_workspace_bytes": (_sz, [_i32] * 5),
+    "nocf_rollout_mid_ensemble_f32": (C.c_int, _ENS + _EVAL + _TAIL),
+    "nocf_rollout_record_mid_ensemble_f32": (C.c_int, _ENS + _REC + _TAIL),
+    "nocf_rollout_bwd_mid_ensemble_f32": (C.c_int, _ENS_ADJ + [_vp, _vp, _i64, _vp] + _TAIL),
+    "nocf_rollout_bwd_small_ensemble_rw_f32": (C.c_int, _ENS_ADJ_RW + [_vp] * 3),
+    "nocf_rollout_bwd_mid_ensemble_rw_f32": (C.c_int, _ENS_ADJ_RW + [_vp, _vp, _i64, _vp] + _TAIL),
+    "nocf_rollout_noisy_ensemble_f32": (C.c_int, _ENS_NOISY + _EVAL + _TAIL),
+    "nocf_rollout_record_noisy_ensemble_f32": (C.c_int, _ENS_NOISY + [_vp] * 4 + _TAIL),
+    "nocf_rollout_noisy_mid_ensemble_f32": (C.c_int, _ENS_NOISY + _EVAL + _TAIL),
+    "nocf_rollout_record_noisy_mid_ensemble_f32": (C.c_int, _ENS_NOISY + _REC + _TAIL),
+    "nocf_rollout_disturbed_ensemble_f32": (C.c_int, _ENS_W + _EVAL + _TAIL),
+    "nocf_rollout_record_disturbed_ensemble_f32": (C.c_int, _ENS_W + [_vp] * 4 + _TAIL),
+    "nocf_rollout_disturbed_mid_ensemble_f32": (C.c_int, _ENS_W + _EVAL + _TAIL),
+    "nocf_rollout_record_disturbed_mid_ensemble_f32": (C.c_int, _ENS_W + _REC + _TAIL),
+    "nocf_rollout_bwd_small_ensemble_w_f32": (C.c_int, _ENS_ADJ + [_vp] * 4),
+    "nocf_rollout_bwd_mid_ensemble_w_f32": (C.c_int, _ENS_ADJ + [_vp, _vp, _i64, _vp, _vp] + _TAIL),
+    "nocf_rollout_bwd_small_ensemble_states_f32": (C.c_int, _ENS_ADJ + [_vp] * 3),
+    "nocf_rollout_bwd_mid_ensemble_states_f32": (C.c_int, _ENS_ADJ + [_vp] * 3 + _TAIL),
+    "nocf_disturbance_ascent_ensemble_f32": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    # the direct-control baselines
+    "nocf_baseline_max_nt": (C.c_int, [_PROB, _i32, _i32, _i32]),
+    "nocf_baseline_eval_f32": (C.c_int, [_PROB] + _BASE + [_vp] * 7),
+    "nocf_baseline_adam_f32": (C.c_int, [_PROB] + _ADAM),
+    "nocf_baseline_quad_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "nocf_baseline_quad_eval_f32": (C.c_int, [_PROB] + _BASE + [_vp] * 7),
+    "nocf_baseline_quad_lbfgs_f32": (C.c_int, [_PROB] + _LBFGS),
+    "nocf_baseline_eval_f64": (C.c_int, [_PROB64] + _BASE + [_vp] * 7),
+    "nocf_baseline_adam_f64": (C.c_int, [_PROB64] + _ADAM),
+    "nocf_baseline_quad_workspace_bytes_f64": (_sz, [_i64, _i32, _i32]),
+    "nocf_baseline_quad_eval_f64": (C.c_int, [_PROB64] + _BASE + [_vp] * 7),
+    "nocf_baseline_quad_lbfgs_f64": (C.c_int, [_PROB64] + _LBFGS),
+    # double precision
+    "nocf_workspace_bytes_f64": (_sz, [_i32, _i32, _i32]),
+    "nocf_rollout_f64": (C.c_int, _HEAD64 + [_vp] * 5 + _TAIL),
+    "nocf_rollout_record_f64": (C.c_int, _HEAD64 + [_vp] * 4 + _TAIL),
+    "nocf_rollout_bwd_f64": (C.c_int, [_PHI64, _PROB64, _i64, _i32, _i32, _dbl, _pdbl, _dbl] + [_vp] * 14 + _TAIL),
+    "nocf_prob_eval_f64": (C.c_int, [_PROB64, _i32, _vp, _vp, _i64] + [_vp] * 4),
+    "nocf_phi_f64": (C.c_int, [_PHI64, _vp, _i64, _vp, _vp] + _TAIL),
+    # diagnostics
+    "nocf_profile_begin": (C.c_int, []),
+    "nocf_profile_end": (C.c_int, [_pdbl, _pi32]),
+    "nocf_debug_reload_env": (None, []),
+    "nocf_debug_tile_plan": (C.c_int, [_i32] * 6 + [_pi32]),
+    "nocf_debug_f64_plan": (C.c_int, [_i32] * 5 + [_i64, _i32, _pi32]),
+    "nocf_debug_set_stamp_buffer": (C.c_int, [_vp]),
+    "nocf_selftest_mfma": (C.c_int, [_vp, _vp, _i32, _vp, _vp]),
+}
+
+# what every library must export, the shipped one and a per-shape build alike: a library without one of them fails at load
+_REQUIRED = ("nocf_version", "nocf_last_rollout_kernel", "nocf_last_rollout_status_async", "nocf_workspace_bytes",
+             "nocf_rollout_workspace_bytes", "nocf_ctrl_dim", "nocf_rollout_f32", "nocf_cost_means_f32", "nocf_rollout_record_f32",
+             "nocf_rollout_record_act_f32", "nocf_activation_record_floats", "nocf_small_grad_floats", "nocf_rollout_bwd_small_f32",
+             "nocf_rollout_bwd_f32", "nocf_rollout_bwd_act_f32", "nocf_contract_f32", "nocf_colsum_f32", "nocf_phi_forward_f32",
+             "nocf_phi_grad_f32", "nocf_prob_eval_f32", "nocf_workspace_bytes_f64", "nocf_rollout_f64", "nocf_prob_eval_f64", "nocf_phi_f64",
+             "nocf_profile_begin", "nocf_profile_end", "nocf_debug_reload_env", "nocf_debug_tile_plan", "nocf_debug_set_stamp_buffer",
+             "nocf_selftest_mfma")
+
+
 def _bind(L):
-    L.nocf_version.restype = C.c_int
-    if hasattr(L, "nocf_set_knob"):
-        L.nocf_set_knob.restype = C.c_int
-        L.nocf_set_knob.argtypes = [C.c_char_p, C.c_int32, C.c_int32]
-        if _duo_fallback["on"]:
-            L.nocf_set_knob(b"NOCF_DUO", 0, 0)
-    L.nocf_last_rollout_kernel.restype = C.c_char_p
-    L.nocf_workspace_bytes.restype = C.c_size_t
-    L.nocf_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    L.nocf_rollout_workspace_bytes.restype = C.c_size_t
-    L.nocf_rollout_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64]
-    L.nocf_ctrl_dim.restype = C.c_int
-    L.nocf_ctrl_dim.argtypes = [C.POINTER(NocfProb), C.c_int32]
-    L.nocf_rollout_f32.restype = C.c_int
-    L.nocf_rollout_f32.argtypes = [C.POINTER(NocfPhi), C.POINTER(NocfProb), C.c_void_p, C.c_int64,
-                                   C.c_double, C.c_double, C.c_int32, C.c_int32, fp,
-                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                   C.c_void_p, C.c_size_t, C.c_void_p]
-    if hasattr(L, "nocf_rollout_means_f32"):
-        L.nocf_rollout_means_f32.restype = C.c_int
-        L.nocf_rollout_means_f32.argtypes = [C.POINTER(NocfPhi), C.POINTER(NocfProb), C.c_void_p, C.c_int64,
-                                             C.c_double, C.c_double, C.c_int32, C.c_int32, fp,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_size_t, C.c_void_p]
-    if hasattr(L, "nocf_rollout_segments_f32"):
-        L.nocf_rollout_segments_f32.restype = C.c_int
-        L.nocf_rollout_segments_f32.argtypes = [C.POINTER(NocfPhi), C.POINTER(NocfProb), C.c_void_p, C.c_int64,
-                                                C.c_int32, C.c_int64, C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, fp,
-                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                C.c_void_p, C.c_size_t, C.c_void_p]
-    if hasattr(L, "nocf_segments_supported"):
-        L.nocf_segments_supported.restype = C.c_int
-        L.nocf_segments_supported.argtypes = [C.POINTER(NocfPhi), C.POINTER(NocfProb)]
-    L.nocf_small_grad_floats.restype = C.c_int64
-    L.nocf_small_grad_floats.argtypes = [C.c_int32, C.c_int32]
-    L.nocf_rollout_bwd_small_f32.restype = C.c_int
-    L.nocf_rollout_bwd_small_f32.argtypes = [C.POINTER(NocfPhi), C.POINTER(NocfProb), C.c_int64, C.c_int32, C.c_int32, C.c_double,
-                                             fp, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    if hasattr(L, "nocf_rollout_bwd_mid_f32"):
-        L.nocf_mid_grad_rows.restype = C.c_int64
-        L.nocf_mid_grad_rows.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64]
-        L.nocf_rollout_bwd_mid_f32.restype = C.c_int
-        L.nocf_rollout_bwd_mid_f32.argtypes = [C.POINTER(NocfPhi), C.POINTER(NocfProb), C.c_int64, C.c_int32, C.c_int32, C.c_double,
-                                               fp, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    if hasattr(L, "nocf_phi_value_bwd_f32"):
-        L.nocf_phi_value_bwd_f32.restype = C.c_int
-        L.nocf_phi_value_bwd_f32.argtypes = [C.POINTER(NocfPhi), C.c_void_p, C.c_int64, C.c_void_p] + [C.c_void_p] * 9 + [C.c_void_p, C.c_size_t, C.c_void_p]
-        L.nocf_phi_grad_bwd_f32.restype = C.c_int
-        L.nocf_phi_grad_bwd_f32.argtypes = [C.POINTER(NocfPhi), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_void_p] * 9 + [C.c_void_p, C.c_size_t, C.c_void_p]
-    L.nocf_contract_f32.restype = C.c_int
-    L.nocf_contract_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
-                                    C.c_void_p, C.c_size_t, C.c_void_p]
-    L.nocf_cost_means_f32.restype = C.c_int
-    L.nocf_cost_means_f32.argtypes = [C.c_void_p, fp, C.c_void_p, C.c_void_p]
-    L.nocf_rollout_record_f32.restype = C.c_int
-    L.nocf_rollout_record_f32.argtypes = [C.POINTER(NocfPhi), C.POINTER(NocfProb), C.c_void_p, C.c_int64,
-                                          C.c_double, C.c_double, C.c_int32, C.c_int32, fp,
-                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_void_p, C.c_size_t, C.c_void_p]
-    L.nocf_rollout_bwd_f32.restype = C.c_int
-    L.nocf_rollout_bwd_f32.argtypes = [C.POINTER(NocfPhi), C.POINTER(NocfProb), C.c_int64, C.c_int32, C.c_int32, C.c_double,
-                                       fp, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_void_p] * 11 + \
-                                      [C.c_void_p, C.c_size_t, C.c_void_p]
-    L.nocf_activation_record_floats.restype = C.c_size_t
-    L.nocf_activation_record_floats.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]
-    L.nocf_rollout_record_act_f32.restype = C.c_int
-    L.nocf_rollout_record_act_f32.argtypes = [C.POINTER(NocfPhi), C.POINTER(NocfProb), C.c_void_p, C.c_int64,
-                                              C.c_double, C.c_double, C.c_int32, C.c_int32, fp,
-                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
-                                              C.c_void_p, C.c_size_t, C.c_void_p]
-    L.nocf_rollout_bwd_act_f32.restype = C.c_int
-    L.nocf_rollout_bwd_act_f32.argtypes = [C.POINTER(NocfPhi), C.POINTER(NocfProb), C.c_int64, C.c_int32, C.c_int32, C.c_double,
-                                           fp, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_void_p] * 11 + \
-                                          [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    if hasattr(L, "nocf_tape_floats"):
-        L.nocf_tape_floats.restype = C.c_size_t
-        L.nocf_tape_floats.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]
-        L.nocf_rollout_tape_f32.restype = C.c_int
-        L.nocf_rollout_tape_f32.argtypes = L.nocf_rollout_record_act_f32.argtypes
-        L.nocf_rollout_bwd_tape_f32.restype = C.c_int
-        L.nocf_rollout_bwd_tape_f32.argtypes = [C.POINTER(NocfPhi), C.POINTER(NocfProb), C.c_int64, C.c_int32, C.c_int32,
-                                                fp, C.c_double] + [C.c_void_p] * 11 + \
-                                               [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32)] + \
-                                               [C.c_void_p, C.c_size_t, C.c_void_p]
-        L.nocf_dw_scratch_floats.restype = C.c_size_t
-        if hasattr(L, "nocf_bwd_colsum_floats"):                  # (a per-shape library cached by an older build has no such entry: train.py then streams the dw rows)
-            L.nocf_bwd_colsum_floats.restype = C.c_size_t
-            L.nocf_bwd_colsum_floats.argtypes = [C.c_int64]
-            L.nocf_rollout_bwd_tape_sums_f32.restype = C.c_int
-            L.nocf_rollout_bwd_tape_sums_f32.argtypes = [C.POINTER(NocfPhi), C.POINTER(NocfProb), C.c_int64, C.c_int32, C.c_int32,
-                                                         fp, C.c_double] + [C.c_void_p] * 10 + \
-                                                        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32)] + \
-                                                        [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.nocf_poison_if_failed_f32.restype = C.c_int
-        L.nocf_poison_if_failed_f32.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
-    for name in ("nocf_phi_grad_f32", "nocf_phi_forward_f32"):
-        f = getattr(L, name)
-        f.restype = C.c_int
-        f.argtypes = [C.POINTER(NocfPhi), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.nocf_prob_eval_f32.restype = C.c_int
-    L.nocf_prob_eval_f32.argtypes = [C.POINTER(NocfProb), C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
-                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    if hasattr(L, "nocf_baseline_eval_f32"):
-        L.nocf_baseline_eval_f32.restype = C.c_int
-        L.nocf_baseline_eval_f32.argtypes = [C.POINTER(NocfProb), C.c_int32, C.c_int64, C.c_int32, C.c_double] + [C.c_void_p] * 6 + \
-                                            [C.c_void_p]
-        L.nocf_baseline_adam_f32.restype = C.c_int
-        L.nocf_baseline_adam_f32.argtypes = [C.POINTER(NocfProb), C.c_int32, C.c_int64, C.c_int32, C.c_double,
-                                             C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32] + \
-                                            [C.c_void_p] * 7 + [C.c_void_p]
-    if hasattr(L, "nocf_baseline_quad_eval_f32"):
-        L.nocf_baseline_quad_workspace_bytes.restype = C.c_size_t
-        L.nocf_baseline_quad_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
-        L.nocf_baseline_quad_eval_f32.restype = C.c_int
-        L.nocf_baseline_quad_eval_f32.argtypes = [C.POINTER(NocfProb), C.c_int32, C.c_int64, C.c_int32, C.c_double] + \
-                                                 [C.c_void_p] * 6 + [C.c_void_p]
-        L.nocf_baseline_quad_lbfgs_f32.restype = C.c_int
-        L.nocf_baseline_quad_lbfgs_f32.argtypes = [C.POINTER(NocfProb), C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_double,
-                                                   C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32] + \
-                                                  [C.c_void_p] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p]
-    if hasattr(L, "nocf_baseline_eval_f64"):
-        L.nocf_baseline_max_nt.restype = C.c_int
-        L.nocf_baseline_max_nt.argtypes = [C.POINTER(NocfProb), C.c_int32, C.c_int32, C.c_int32]
-        L.nocf_baseline_eval_f64.restype = C.c_int
-        L.nocf_baseline_eval_f64.argtypes = [C.POINTER(NocfProb64), C.c_int32, C.c_int64, C.c_int32, C.c_double] + [C.c_void_p] * 6 + \
-                                            [C.c_void_p]
-        L.nocf_baseline_adam_f64.restype = C.c_int
-        L.nocf_baseline_adam_f64.argtypes = [C.POINTER(NocfProb64), C.c_int32, C.c_int64, C.c_int32, C.c_double,
-                                             C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32] + \
-                                            [C.c_void_p] * 7 + [C.c_void_p]
-        L.nocf_baseline_quad_workspace_bytes_f64.restype = C.c_size_t
-        L.nocf_baseline_quad_workspace_bytes_f64.argtypes = [C.c_int64, C.c_int32, C.c_int32]
-        L.nocf_baseline_quad_eval_f64.restype = C.c_int
-        L.nocf_baseline_quad_eval_f64.argtypes = [C.POINTER(NocfProb64), C.c_int32, C.c_int64, C.c_int32, C.c_double] + \
-                                                 [C.c_void_p] * 6 + [C.c_void_p]
-        L.nocf_baseline_quad_lbfgs_f64.restype = C.c_int
-        L.nocf_baseline_quad_lbfgs_f64.argtypes = [C.POINTER(NocfProb64), C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_double,
-                                                   C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32] + \
-                                                  [C.c_void_p] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p]
-    L.nocf_profile_begin.restype = C.c_int
-    L.nocf_profile_end.restype = C.c_int
-    L.nocf_profile_end.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int32)]
-    L.nocf_colsum_f32.restype = C.c_int
-    L.nocf_colsum_f32.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.nocf_workspace_bytes_f64.restype = C.c_size_t
-    L.nocf_workspace_bytes_f64.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    L.nocf_rollout_f64.restype = C.c_int
-    L.nocf_rollout_f64.argtypes = [C.POINTER(NocfPhi64), C.POINTER(NocfProb64), C.c_void_p, C.c_int64,
-                                   C.c_double, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_double),
-                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    if hasattr(L, "nocf_rollout_bwd_f64"):
-        L.nocf_rollout_record_f64.restype = C.c_int
-        L.nocf_rollout_record_f64.argtypes = [C.POINTER(NocfPhi64), C.POINTER(NocfProb64), C.c_void_p, C.c_int64,
-                                              C.c_double, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_double),
-                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.nocf_rollout_bwd_f64.restype = C.c_int
-        L.nocf_rollout_bwd_f64.argtypes = [C.POINTER(NocfPhi64), C.POINTER(NocfProb64), C.c_int64, C.c_int32, C.c_int32, C.c_double,
-                                           C.POINTER(C.c_double), C.c_double, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_void_p] * 11 + \
-                                          [C.c_void_p, C.c_size_t, C.c_void_p]
-    L.nocf_prob_eval_f64.restype = C.c_int
-    L.nocf_prob_eval_f64.argtypes = [C.POINTER(NocfProb64), C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.nocf_phi_f64.restype = C.c_int
-    L.nocf_phi_f64.argtypes = [C.POINTER(NocfPhi64), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.nocf_debug_reload_env.restype = None
-    L.nocf_debug_tile_plan.restype = C.c_int
-    L.nocf_debug_tile_plan.argtypes = [C.c_int32] * 6 + [C.POINTER(C.c_int32)]
-    if hasattr(L, "nocf_debug_f64_plan"):
-        L.nocf_debug_f64_plan.restype = C.c_int
-        L.nocf_debug_f64_plan.argtypes = [C.c_int32] * 5 + [C.c_int64, C.c_int32, C.POINTER(C.c_int32)]
-    L.nocf_last_rollout_status_async.restype = C.c_int
-    L.nocf_last_rollout_status_async.argtypes = [C.c_void_p, C.c_void_p]
-    L.nocf_debug_set_stamp_buffer.restype = C.c_int
-    L.nocf_debug_set_stamp_buffer.argtypes = [C.c_void_p]
-    L.nocf_selftest_mfma.restype = C.c_int
-    L.nocf_selftest_mfma.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    """set the prototype of every entry of PROTOTYPES that L exports; every library reaches Python through here"""
+    for name in _REQUIRED:
+        getattr(L, name)
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        if hasattr(L, name):
+            f = getattr(L, name)
+            f.restype, f.argtypes = restype, argtypes
+    if _duo_fallback["on"] and hasattr(L, "nocf_set_knob"):
+        L.nocf_set_knob(b"NOCF_DUO", 0, 0)
     return L
+
+
+def entries(L, names):
+    """the entries `names` of library L as a tuple, or None when L lacks one of them (a per-shape library cached by an older build)"""
+    if not all(hasattr(L, name) for name in names):
+        return None
+    return tuple(getattr(L, name) for name in names)
+
+
+def require(L, names, what):
+    """entries(L, names); a library that lacks one is an error that names the missing ones, never a fallback"""
+    missing = [name for name in names if not hasattr(L, name)]
+    if missing:
+        raise RuntimeError(f"{what}: the HIP library does not export " + " / ".join(missing) + "; rebuild it")
+    return tuple(getattr(L, name) for name in names)
+
+
+def entry_for(L, names, what):
+    """(library, entries): L's, or the shipped library's when L is a per-shape library cached by an older build"""
+    f = entries(L, names)
+    if f is not None:
+        return L, f
+    L = lib()
+    return L, require(L, names, what)
 
 
 # ---- asynchronous rollout status (include/nocf.h: nocf_last_rollout_status_async).  The split-role kernel reports a timed-out

@@ -6,35 +6,20 @@ behind step k, which every adjoint kernel holds.  nocf_rollout_bwd_states_f32 is
 and those cotangents written out; nocf_disturbance_ascent_f32 is one projected ascent step.  An iteration of the search is three launches
 (recording forward, state-only adjoint, ascent step) and no host round trip.  Single precision.  There is no CPU or eager-torch fallback."""
 import ctypes as C
-import os
 
 import torch
 
 from . import _lib
-from .train import _STEPPERS, _disturbed_entry, _step_sizes
+from .train import _STEPPERS, _activation_record, _step_sizes
 
 OBJECTIVES = ("Jc", "control")
 
-_STATES_ARGTYPES = [C.POINTER(_lib.NocfPhi), C.POINTER(_lib.NocfProb), C.c_int64, C.c_int32, C.c_int32, C.c_double,
-                    _lib.fp, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                    C.c_void_p, C.c_size_t, C.c_void_p]
-_ASCENT_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p]
+_ENTRIES = ("nocf_rollout_record_disturbed_f32", "nocf_rollout_bwd_states_f32", "nocf_disturbance_ascent_f32")
 
 
 def _entries(L):
-    """(nocf_rollout_record_disturbed_f32, nocf_rollout_bwd_states_f32, nocf_disturbance_ascent_f32) of library L with their prototypes
-    set, or None when L lacks one of them"""
-    rec = _disturbed_entry(L)
-    if rec is None or not hasattr(L, "nocf_rollout_bwd_states_f32") or not hasattr(L, "nocf_disturbance_ascent_f32"):
-        return None
-    st, asc = L.nocf_rollout_bwd_states_f32, L.nocf_disturbance_ascent_f32
-    if st.argtypes is None:
-        st.restype = C.c_int
-        st.argtypes = _STATES_ARGTYPES
-    if asc.argtypes is None:
-        asc.restype = C.c_int
-        asc.argtypes = _ASCENT_ARGTYPES
-    return rec, st, asc
+    """the three entries _ENTRIES of library L, or None when L lacks one of them"""
+    return _lib.entries(L, _ENTRIES)
 
 
 def _check(fn, x, net, prob, nt, W, alph, stepper, objective, extra=()):
@@ -103,23 +88,9 @@ class _Search:
         self.inv_n = float(inv_n)
         with torch.cuda.device(dev):
             L = _lib.lib_for(net.d, net.m, net.nTh, self.phi_st.r, self.prob_st.n_agents, fwd=self.prob_st.kind != _lib.PROB_QUADCOPTER)
-            f = _entries(L)
-            if f is None:                                  # a per-shape library cached by an older build: the shipped library has the entries
-                L = _lib.lib()
-                f = _entries(L)
-            if f is None:
-                raise RuntimeError(f"{fn}: the HIP library does not export nocf_rollout_bwd_states_f32 / nocf_disturbance_ascent_f32; "
-                                   "rebuild it")
-            self.L, (self.f_rec, self.f_states, self.f_ascent) = L, f
+            self.L, (self.f_rec, self.f_states, self.f_ascent) = _lib.entry_for(L, _ENTRIES, fn)
             # the activation record is the one-CU kernel's (m <= 128), as in train._OCflowTrainDisturbed
-            nact = 0 if (os.environ.get("NOCF_ACT_REC", "1") in ("0", "") or net.m > 128) else int(
-                L.nocf_activation_record_floats(int(d), int(net.m), int(net.nTh), int(n), self.nt, _STEPPERS[stepper]))
-            self.act = None
-            if nact:
-                try:
-                    self.act = torch.empty(nact, device=dev)
-                except torch.OutOfMemoryError:             # the record is an optimisation: without it the adjoint recomputes
-                    self.act = None
+            self.act = _activation_record(self.L, net, n, self.nt, stepper, dev, one_cu_only=True)
         self.forward_kernel = self.adjoint_kernel = None
 
     def gradient(self, W):

@@ -9,29 +9,18 @@ step, by a caller-supplied W [nt, n, d] (time-major like the kernels' zFull):
 and per-tile kernels take W as one more input.  The split-role kernel does not: m = 512 point-agent networks run on the per-tile kernel here.
 Single precision, no segments.  These calls are evaluations (no autograd); training through disturbed rollouts is
 train.disturbed_ocflow_train (nocf_rollout_record_disturbed_f32).  There is no CPU or eager-torch fallback."""
-import ctypes as C
 import math
 
 import torch
 
 from . import _lib
-from .OCflow import _STEPPERS
-
-_ARGTYPES = [C.POINTER(_lib.NocfPhi), C.POINTER(_lib.NocfProb), C.c_void_p, C.c_void_p, C.c_int64,
-             C.c_double, C.c_double, C.c_int32, C.c_int32, _lib.fp,
-             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-             C.c_void_p, C.c_size_t, C.c_void_p]
+from .OCflow import _evaluate
 
 
 def _entry(L):
-    """nocf_rollout_disturbed_f32 of library L with its prototype set, or None when L does not export it"""
-    if not hasattr(L, "nocf_rollout_disturbed_f32"):
-        return None
-    f = L.nocf_rollout_disturbed_f32
-    if f.argtypes is None:
-        f.restype = C.c_int
-        f.argtypes = _ARGTYPES
-    return f
+    """nocf_rollout_disturbed_f32 of library L, or None when L does not export it"""
+    f = _lib.entries(L, ("nocf_rollout_disturbed_f32",))
+    return f and f[0]
 
 
 def disturbed_rollout(x, Phi, prob, nt, W, tspan=(0., 1.), alph=None, stepper="rk4", intermediates=False):
@@ -52,59 +41,13 @@ def disturbed_rollout(x, Phi, prob, nt, W, tspan=(0., 1.), alph=None, stepper="r
         if isinstance(t, torch.Tensor) and t.dtype == torch.float64:
             raise RuntimeError(f"disturbed_rollout: {name} is float64; the disturbed rollout is single precision only "
                                "(the double-precision kernel takes no disturbance)")
-    x = _lib.require_device_f32(x, "x")
-    W = _lib.require_device_f32(W, "W")
-    if x.dim() != 2:
-        raise ValueError("x must be nex-by-d")
-    n, d = x.shape
-    if d != Phi.d:
-        raise ValueError(f"x has d={d} but Phi was built for d={Phi.d}")
-    if int(nt) < 1:
-        raise ValueError("nt must be >= 1")
-    if n < 1:
-        raise ValueError("x has no rows")
-    if tuple(W.shape) != (int(nt), n, d):
-        raise ValueError(f"W must be nt-by-nex-by-d = {(int(nt), n, d)}, got {tuple(W.shape)}")
-    if W.device != x.device:
-        raise ValueError("x and W must be on the same device")
-    if stepper not in _STEPPERS:
-        raise ValueError(f"stepper must be 'rk4' or 'rk1', got {stepper!r}")
-    if len(alph) < 6:
-        raise ValueError("alph needs 6 entries")
-    Phi._guard_no_autograd(x, "disturbed_rollout")
-    with torch.no_grad():
-        _lib.check_errors()
-        phi_st, keep1, ws = Phi._c_struct(n)
-        prob_st, keep2 = prob._c_struct(x.device)
-        dev = x.device
-        persample = torch.empty(n, 7, dtype=torch.float32, device=dev)
-        sums = torch.empty(8, dtype=torch.float32, device=dev)
-        means = torch.empty(8, dtype=torch.float32, device=dev)
-        z_final = torch.empty(n, d + 4, dtype=torch.float32, device=dev)
-        zFull = ctrlFull = None
-        if intermediates:
-            cdim = _lib.lib().nocf_ctrl_dim(C.byref(prob_st), d)
-            zFull = torch.empty(nt + 1, n, d + 4, dtype=torch.float32, device=dev)
-            ctrlFull = torch.empty(nt + 1, n, cdim, dtype=torch.float32, device=dev)
-        alph_c = (C.c_float * 6)(*[float(a) for a in alph[:6]])
-        with torch.cuda.device(dev):
-            L = _lib.lib_for(Phi.d, Phi.m, Phi.nTh, phi_st.r, prob_st.n_agents, fwd=prob_st.kind != _lib.PROB_QUADCOPTER)
-            f = _entry(L)
-            if f is None:                                  # a per-shape library cached by an older build: the shipped library has the entry
-                L = _lib.lib()
-                f = _entry(L)
-            if f is None:
-                raise RuntimeError("disturbed_rollout: the HIP library does not export nocf_rollout_disturbed_f32; rebuild it")
-            rc = f(C.byref(phi_st), C.byref(prob_st), _lib.ptr(x), _lib.ptr(W), n,
-                   float(tspan[0]), float(tspan[1]), int(nt), _STEPPERS[stepper], alph_c,
-                   _lib.ptr(z_final), _lib.ptr(persample), _lib.ptr(sums), _lib.ptr(means), _lib.ptr(zFull), _lib.ptr(ctrlFull),
-                   _lib.ptr(ws), ws.numel() * ws.element_size(), _lib.stream_ptr(dev))
-        _lib.check(rc, "nocf_rollout_disturbed_f32")
-        _lib.track_rollout_status(L, dev, "disturbed_rollout")
-        out = {"Jc": means[7], "cs": [means[i] for i in range(7)], "persample": persample, "z_final": z_final}
-        if intermediates:
-            _lib.check_errors(sync=True)                   # consumed on the host (plots, files): a failed launch raises here
-            out["traj"], out["ctrl"] = zFull.permute(1, 2, 0), ctrlFull.permute(1, 2, 0)
+    if not isinstance(W, torch.Tensor):                    # (to _evaluate, None is the held call's "no disturbance")
+        raise TypeError("W must be a torch.Tensor")
+    means, persample, _sums, z_final, zFull, ctrlFull = _evaluate("disturbed_rollout", "nocf_rollout_disturbed_f32", x, Phi, prob, tspan, nt,
+                                                                  stepper, alph, intermediates, W=W)
+    out = {"Jc": means[7], "cs": [means[i] for i in range(7)], "persample": persample, "z_final": z_final}
+    if intermediates:
+        out["traj"], out["ctrl"] = zFull.permute(1, 2, 0), ctrlFull.permute(1, 2, 0)
     return out
 
 

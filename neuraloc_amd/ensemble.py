@@ -34,79 +34,29 @@ MID_LIMITS = ("nTh = 2, a width with a one-CU instantiation (m <= 128; training:
               "Quadcopter with at most 8 agents when d + 1 <= 16 and at most 16 beyond (MONO_NAG)")
 FAMILIES = ("lane", "mid")
 
-_HEAD = [C.POINTER(_lib.NocfPhi), C.POINTER(_lib.NocfProb), C.c_void_p, C.c_int64, C.c_int32, C.c_int64,
-         C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_void_p]
-_ARGTYPES = {
-    "nocf_rollout_ensemble_f32": _HEAD + [C.c_void_p] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p],
-    "nocf_rollout_record_ensemble_f32": _HEAD + [C.c_void_p] * 4 + [C.c_void_p, C.c_size_t, C.c_void_p],
-    "nocf_rollout_bwd_small_ensemble_f32": [C.POINTER(_lib.NocfPhi), C.POINTER(_lib.NocfProb), C.c_int64, C.c_int32, C.c_int32, C.c_int32,
-                                            C.c_double, C.c_void_p, C.c_double] + [C.c_void_p] * 5 + [C.c_void_p],
-}
-
-
-_TAIL = [C.c_void_p, C.c_size_t, C.c_void_p]                       # workspace, its bytes, the stream
-_ARGTYPES_MID = {
-    "nocf_rollout_mid_ensemble_f32": _HEAD + [C.c_void_p] * 6 + _TAIL,
-    "nocf_rollout_record_mid_ensemble_f32": _HEAD + [C.c_void_p] * 5 + [C.POINTER(C.c_int32)] + _TAIL,
-    "nocf_rollout_bwd_mid_ensemble_f32": [C.POINTER(_lib.NocfPhi), C.POINTER(_lib.NocfProb), C.c_int64, C.c_int32, C.c_int32, C.c_int32,
-                                          C.c_double, C.c_void_p, C.c_double] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p] + _TAIL,
-}
-
-
+_LANE = ("nocf_rollout_ensemble_f32", "nocf_rollout_record_ensemble_f32", "nocf_rollout_bwd_small_ensemble_f32")
+_MID = ("nocf_rollout_mid_ensemble_f32", "nocf_rollout_record_mid_ensemble_f32", "nocf_rollout_bwd_mid_ensemble_f32")
+_MID_WORKSPACE = ("nocf_mid_ensemble_workspace_bytes",)
 # the weighted ensemble adjoints (ensemble_risk.py): the two adjoint entries above with `const float* wrow` [E, n] in place of `double inv_n`
-_ARGTYPES_RW = {
-    "lane": ("nocf_rollout_bwd_small_ensemble_rw_f32",
-             [C.POINTER(_lib.NocfPhi), C.POINTER(_lib.NocfProb), C.c_int64, C.c_int32, C.c_int32, C.c_int32,
-              C.c_double, C.c_void_p, C.c_void_p] + [C.c_void_p] * 5 + [C.c_void_p]),
-    "mid": ("nocf_rollout_bwd_mid_ensemble_rw_f32",
-            [C.POINTER(_lib.NocfPhi), C.POINTER(_lib.NocfProb), C.c_int64, C.c_int32, C.c_int32, C.c_int32,
-             C.c_double, C.c_void_p, C.c_void_p] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p] + _TAIL),
-}
+_WEIGHTED = {"lane": "nocf_rollout_bwd_small_ensemble_rw_f32", "mid": "nocf_rollout_bwd_mid_ensemble_rw_f32"}
 
 
 def weighted_entry(L, family):
-    """the weighted ensemble adjoint of a family in library L, prototype set; RuntimeError when L does not export BOTH (a library is rebuilt
-    as a whole)"""
-    missing = [name for name, _ in _ARGTYPES_RW.values() if not hasattr(L, name)]
-    if missing:
-        raise RuntimeError("ensemble: the HIP library does not export " + " / ".join(missing) + "; rebuild it")
-    name, argtypes = _ARGTYPES_RW[family]
-    f = getattr(L, name)
-    if f.argtypes is None:
-        f.restype = C.c_int
-        f.argtypes = argtypes
-    return f
+    """the weighted ensemble adjoint of a family in library L; RuntimeError when L does not export BOTH (a library is rebuilt as a whole)"""
+    f = _lib.require(L, tuple(_WEIGHTED.values()), "ensemble")
+    return f[list(_WEIGHTED).index(family)]
 
 
 def _entries_mid(L):
-    """(nocf_rollout_mid_ensemble_f32, nocf_rollout_record_mid_ensemble_f32, nocf_rollout_bwd_mid_ensemble_f32) of library L with their
-    prototypes set (and nocf_mid_ensemble_workspace_bytes'), or None when L lacks one of the four"""
-    if not hasattr(L, "nocf_mid_ensemble_workspace_bytes"):
-        return None
-    q = L.nocf_mid_ensemble_workspace_bytes
-    if q.argtypes is None:
-        q.restype = C.c_size_t
-        q.argtypes = [C.c_int32] * 5
-    out = []
-    for name, argtypes in _ARGTYPES_MID.items():
-        if not hasattr(L, name):
-            return None
-        f = getattr(L, name)
-        if f.argtypes is None:
-            f.restype = C.c_int
-            f.argtypes = argtypes
-        out.append(f)
-    return tuple(out)
+    """the three entries _MID of library L, or None when L lacks one of them or nocf_mid_ensemble_workspace_bytes"""
+    f = _lib.entries(L, _MID_WORKSPACE + _MID)
+    return f and f[1:]
 
 
 def _shipped_mid():
     """the shipped library and its three one-CU ensemble entries"""
     L = _lib.lib()
-    f = _entries_mid(L)
-    if f is None:
-        raise RuntimeError("ensemble: the HIP library does not export nocf_mid_ensemble_workspace_bytes / nocf_rollout_mid_ensemble_f32 / "
-                           "nocf_rollout_record_mid_ensemble_f32 / nocf_rollout_bwd_mid_ensemble_f32; rebuild it")
-    return L, f
+    return L, _lib.require(L, _MID_WORKSPACE + _MID, "ensemble")[1:]
 
 
 def _mid_eligible(nTh, m, d, r, n_agents, train=False):
@@ -117,28 +67,14 @@ def _mid_eligible(nTh, m, d, r, n_agents, train=False):
 
 
 def _entries(L):
-    """(nocf_rollout_ensemble_f32, nocf_rollout_record_ensemble_f32, nocf_rollout_bwd_small_ensemble_f32) of library L with their prototypes
-    set, or None when L lacks one of them"""
-    out = []
-    for name, argtypes in _ARGTYPES.items():
-        if not hasattr(L, name):
-            return None
-        f = getattr(L, name)
-        if f.argtypes is None:
-            f.restype = C.c_int
-            f.argtypes = argtypes
-        out.append(f)
-    return tuple(out)
+    """the three entries _LANE of library L, or None when L lacks one of them"""
+    return _lib.entries(L, _LANE)
 
 
 def _shipped():
     """the shipped library and its three ensemble entries (the lane family needs no per-shape library)"""
     L = _lib.lib()
-    f = _entries(L)
-    if f is None:
-        raise RuntimeError("ensemble: the HIP library does not export nocf_rollout_ensemble_f32 / nocf_rollout_record_ensemble_f32 / "
-                           "nocf_rollout_bwd_small_ensemble_f32; rebuild it")
-    return L, f
+    return L, _lib.require(L, _LANE, "ensemble")
 
 
 class _Stacked(nn.Module):
@@ -568,7 +504,7 @@ class _EnsembleTrain(torch.autograd.Function):
         L, (_f_eval, _f_rec, f_bwd) = _shipped()
         what = "nocf_rollout_bwd_small_ensemble_f32"
         if wrow is not None:
-            f_bwd, what = weighted_entry(L, "lane"), _ARGTYPES_RW["lane"][0]
+            f_bwd, what = weighted_entry(L, "lane"), _WEIGHTED["lane"]
         lamW = ()
         if joint is not None:
             f_bwd, what, lamW = joint[0], joint[1], (_lib.ptr(joint[2]),)
@@ -639,7 +575,7 @@ class _EnsembleTrainMid(torch.autograd.Function):
         L, (_f_eval, _f_rec, f_bwd) = _shipped_mid()
         what = "nocf_rollout_bwd_mid_ensemble_f32"
         if wrow is not None:
-            f_bwd, what = weighted_entry(L, "mid"), _ARGTYPES_RW["mid"][0]
+            f_bwd, what = weighted_entry(L, "mid"), _WEIGHTED["mid"]
         lamW = ()
         if joint is not None:
             f_bwd, what, lamW = joint[0], joint[1], (_lib.ptr(joint[2]),)

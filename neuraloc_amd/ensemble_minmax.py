@@ -25,55 +25,22 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib, ensemble
 from .adversary import OBJECTIVES
-from .ensemble import _HEAD, _TAIL, _refuse
+from .ensemble import _refuse
 from .train import _STEPPERS, _step_sizes
 
-_W = [C.c_void_p, C.c_int64]                                         # W, w_member_stride: behind x_member_stride
-_HEADW = _HEAD[:6] + _W + _HEAD[6:]
-_BWD = [C.POINTER(_lib.NocfPhi), C.POINTER(_lib.NocfProb), C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_double,
-        C.c_void_p, C.c_void_p, C.c_void_p]                           # ... alph, inv_n, s_all, z_final, hs
-_FORWARD = {
-    "lane": {"nocf_rollout_disturbed_ensemble_f32": _HEADW + [C.c_void_p] * 6 + _TAIL,
-             "nocf_rollout_record_disturbed_ensemble_f32": _HEADW + [C.c_void_p] * 4 + _TAIL},
-    "mid": {"nocf_rollout_disturbed_mid_ensemble_f32": _HEADW + [C.c_void_p] * 6 + _TAIL,
-            "nocf_rollout_record_disturbed_mid_ensemble_f32": _HEADW + [C.c_void_p] * 5 + [C.POINTER(C.c_int32)] + _TAIL},
-}
+_FORWARD = {"lane": ("nocf_rollout_disturbed_ensemble_f32", "nocf_rollout_record_disturbed_ensemble_f32"),
+            "mid": ("nocf_rollout_disturbed_mid_ensemble_f32", "nocf_rollout_record_disturbed_mid_ensemble_f32")}
 # the joint (gpart, lam0, lamW) and the state-only (lam0, lamW) ensemble adjoints of a family
-_ADJOINT = {
-    "lane": {"nocf_rollout_bwd_small_ensemble_w_f32": _BWD + [C.c_void_p] * 3 + [C.c_void_p],
-             "nocf_rollout_bwd_small_ensemble_states_f32": _BWD + [C.c_void_p] * 2 + [C.c_void_p]},
-    "mid": {"nocf_rollout_bwd_mid_ensemble_w_f32": _BWD + [C.c_void_p] * 2 + [C.c_int64] + [C.c_void_p] * 2 + _TAIL,
-            "nocf_rollout_bwd_mid_ensemble_states_f32": _BWD + [C.c_void_p] * 3 + _TAIL},
-}
-_ASCENT = {"nocf_disturbance_ascent_ensemble_f32": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
-                                                    C.c_void_p, C.c_void_p, C.c_void_p]}
+_ADJOINT = {"lane": ("nocf_rollout_bwd_small_ensemble_w_f32", "nocf_rollout_bwd_small_ensemble_states_f32"),
+            "mid": ("nocf_rollout_bwd_mid_ensemble_w_f32", "nocf_rollout_bwd_mid_ensemble_states_f32")}
 # (in the header's order: the four forwards, the two joint adjoints, the two state-only ones, the ascent step)
-SYMBOLS = tuple(_FORWARD["lane"]) + tuple(_FORWARD["mid"]) + tuple(tuple(_ADJOINT[fam])[which] for which in (0, 1) for fam in ("lane", "mid")) + \
-          tuple(_ASCENT)
-
-
-def _protos():
-    """name -> argtypes of all nine entries"""
-    out = {}
-    for table in (_FORWARD["lane"], _FORWARD["mid"], _ADJOINT["lane"], _ADJOINT["mid"], _ASCENT):
-        out.update(table)
-    return out
+SYMBOLS = _FORWARD["lane"] + _FORWARD["mid"] + tuple(_ADJOINT[fam][which] for which in (0, 1) for fam in ("lane", "mid")) + \
+          ("nocf_disturbance_ascent_ensemble_f32",)
 
 
 def _entries(L):
-    """name -> entry of library L for all nine symbols, prototypes set; RuntimeError naming the missing ones (a library is rebuilt as a whole)"""
-    protos = _protos()
-    missing = [name for name in SYMBOLS if not hasattr(L, name)]
-    if missing:
-        raise RuntimeError("ensemble_minmax: the HIP library does not export " + " / ".join(missing) + "; rebuild it")
-    out = {}
-    for name in SYMBOLS:
-        f = getattr(L, name)
-        if f.argtypes is None:
-            f.restype = C.c_int
-            f.argtypes = protos[name]
-        out[name] = f
-    return out
+    """name -> entry of library L for all nine symbols; RuntimeError naming the missing ones (a library is rebuilt as a whole)"""
+    return dict(zip(SYMBOLS, _lib.require(L, SYMBOLS, "ensemble_minmax")))
 
 
 class _Disturbance:

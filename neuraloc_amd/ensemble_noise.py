@@ -22,34 +22,17 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib, ensemble
 from .disturb import path_statistics
-from .ensemble import _HEAD, _TAIL, _refuse
+from .ensemble import _refuse
 from .noise import _check_row_offset, _check_seed
 
-_NOISE = [C.c_void_p, C.c_void_p, C.c_int64]                         # scale [E, d], seeds [E], row0: behind x_member_stride
-_HEADN = _HEAD[:6] + _NOISE + _HEAD[6:]
-_ARGTYPES = {
-    "lane": {"nocf_rollout_noisy_ensemble_f32": _HEADN + [C.c_void_p] * 6 + _TAIL,
-             "nocf_rollout_record_noisy_ensemble_f32": _HEADN + [C.c_void_p] * 4 + _TAIL},
-    "mid": {"nocf_rollout_noisy_mid_ensemble_f32": _HEADN + [C.c_void_p] * 6 + _TAIL,
-            "nocf_rollout_record_noisy_mid_ensemble_f32": _HEADN + [C.c_void_p] * 5 + [C.POINTER(C.c_int32)] + _TAIL},
-}
-SYMBOLS = tuple(name for fam in _ARGTYPES.values() for name in fam)
+_NAMES = {"lane": ("nocf_rollout_noisy_ensemble_f32", "nocf_rollout_record_noisy_ensemble_f32"),
+          "mid": ("nocf_rollout_noisy_mid_ensemble_f32", "nocf_rollout_record_noisy_mid_ensemble_f32")}
+SYMBOLS = _NAMES["lane"] + _NAMES["mid"]
 
 
 def _entries(L, family):
-    """(evaluation entry, recording entry, their names) of library L for one family, prototypes set; RuntimeError when L lacks one"""
-    names = tuple(_ARGTYPES[family])
-    missing = [name for name in names if not hasattr(L, name)]
-    if missing:
-        raise RuntimeError("ensemble_noise: the HIP library does not export " + " / ".join(missing) + "; rebuild it")
-    out = []
-    for name in names:
-        f = getattr(L, name)
-        if f.argtypes is None:
-            f.restype = C.c_int
-            f.argtypes = _ARGTYPES[family][name]
-        out.append(f)
-    return out[0], out[1], names
+    """(evaluation entry, recording entry, their names) of library L for one family; RuntimeError when L lacks one"""
+    return _lib.require(L, _NAMES[family], "ensemble_noise") + (_NAMES[family],)
 
 
 def scale_table(sigma, members, nt, d, tspan=(0., 1.), mask=None):
@@ -128,7 +111,7 @@ def _prepare(fn, x, ens, prob, tspan, nt, sigma, seed, stepper, train, mask, row
         table = seeds = None
     row_offset = _check_row_offset(row_offset)
     E, n, d, _own = _refuse(fn, x, ens, prob, nt, stepper, train, family=family)
-    if family in _ARGTYPES:
+    if family in _NAMES:
         _entries(_lib.lib(), family)                                 # (a library without the symbols: RuntimeError, before any launch)
     return E, n, d, _Noise(table, seeds, row_offset)
 

@@ -21,7 +21,7 @@ from .ensemble_noise import _Noise, scale_table, seed_list
 from .noise import _check_row_offset
 from .risk import _check_risk, _row_costs, risk_weights
 
-SYMBOLS = tuple(ensemble._ARGTYPES_RW[family][0] for family in FAMILIES)
+SYMBOLS = tuple(ensemble._WEIGHTED[family] for family in FAMILIES)
 
 
 def _per_member(value, members, name):

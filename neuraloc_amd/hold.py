@@ -15,32 +15,21 @@ The network runs ceil(nt / K) + 1 times where OCflow runs it 4 nt + 1 times; a h
 alone, the control coming from registers or LDS.  The lane (m <= 32, point agents) and one-CU (m <= 128) kernels only; single precision; an
 evaluation (no autograd); one network; quadcopter problems with one craft.  There is no CPU or eager-torch fallback, and every check raises
 before anything is enqueued."""
-import ctypes as C
 import numbers
 
 import torch
 
 from . import _lib
-from .OCflow import _STEPPERS, _launch
+from .OCflow import _evaluate, _launch
 from .disturb import disturbed_rollout, path_statistics
 
-_ARGTYPES = [C.POINTER(_lib.NocfPhi), C.POINTER(_lib.NocfProb), C.c_void_p, C.c_void_p, C.c_int32, C.c_int64,
-             C.c_double, C.c_double, C.c_int32, C.c_int32, _lib.fp,
-             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-             C.c_void_p, C.c_size_t, C.c_void_p]
 _FAMILIES = ("the held rollout runs on the lane kernel (nTh = 2, m <= 32, d + 1 <= 32, point agents, at most 16 of them) and on the one-CU "
              "kernel (nTh = 2, m <= 128, d + 1 <= 32) only")
 
 
 def _entry(L):
-    """nocf_rollout_held_f32 of library L with its prototype set; a library without it is an error, never a fallback"""
-    if not hasattr(L, "nocf_rollout_held_f32"):
-        raise RuntimeError("held_rollout: the HIP library does not export nocf_rollout_held_f32; rebuild it")
-    f = L.nocf_rollout_held_f32
-    if f.argtypes is None:
-        f.restype = C.c_int
-        f.argtypes = _ARGTYPES
-    return f
+    """nocf_rollout_held_f32 of library L; a library without it is an error, never a fallback"""
+    return _lib.require(L, ("nocf_rollout_held_f32",), "held_rollout")[0]
 
 
 def check_hold(hold, what="held_rollout"):
@@ -95,56 +84,11 @@ def _held(x, net, prob, tspan, nt, hold, W, stepper, alph, intermediates, what="
     """the launch behind held_rollout -> (means [8], persample, z_final, zFull, ctrlFull), the last two time-major or None"""
     hold = _refuse(what, x, net, prob, hold, W)
     alph = list(net.alph if alph is None else alph)
-    x = _lib.require_device_f32(x, "x")
-    if W is not None:
-        W = _lib.require_device_f32(W, "W")
-    if x.dim() != 2:
-        raise ValueError("x must be nex-by-d")
-    n, d = x.shape
-    if d != net.d:
-        raise ValueError(f"x has d={d} but Phi was built for d={net.d}")
-    if int(nt) < 1:
-        raise ValueError("nt must be >= 1")
-    if n < 1:
-        raise ValueError("x has no rows")
-    if W is not None and tuple(W.shape) != (int(nt), n, d):
-        raise ValueError(f"W must be nt-by-nex-by-d = {(int(nt), n, d)}, got {tuple(W.shape)}")
-    if W is not None and W.device != x.device:
-        raise ValueError("x and W must be on the same device")
-    if stepper not in _STEPPERS:
-        raise ValueError(f"stepper must be 'rk4' or 'rk1', got {stepper!r}")
-    if len(alph) < 6:
-        raise ValueError("alph needs 6 entries")
-    with torch.no_grad():
-        _lib.check_errors()
-        phi_st, keep1, ws = net._c_struct(n)
-        prob_st, keep2 = prob._c_struct(x.device)
-        dev = x.device
-        persample = torch.empty(n, 7, dtype=torch.float32, device=dev)
-        sums = torch.empty(8, dtype=torch.float32, device=dev)
-        means = torch.empty(8, dtype=torch.float32, device=dev)
-        z_final = torch.empty(n, d + 4, dtype=torch.float32, device=dev)
-        zFull = ctrlFull = None
-        if intermediates:
-            cdim = _lib.lib().nocf_ctrl_dim(C.byref(prob_st), d)
-            zFull = torch.empty(nt + 1, n, d + 4, dtype=torch.float32, device=dev)
-            ctrlFull = torch.empty(nt + 1, n, cdim, dtype=torch.float32, device=dev)
-        alph_c = (C.c_float * 6)(*[float(a) for a in alph[:6]])
-        with torch.cuda.device(dev):
-            # (the shipped library: a per-shape build specialises the per-tile kernels, which take no held control)
-            L = _lib.lib()
-            f = _entry(L)
-            rc = f(C.byref(phi_st), C.byref(prob_st), _lib.ptr(x), _lib.ptr(W), hold, n,
-                   float(tspan[0]), float(tspan[1]), int(nt), _STEPPERS[stepper], alph_c,
-                   _lib.ptr(z_final), _lib.ptr(persample), _lib.ptr(sums), _lib.ptr(means), _lib.ptr(zFull), _lib.ptr(ctrlFull),
-                   _lib.ptr(ws), ws.numel() * ws.element_size(), _lib.stream_ptr(dev))
-        if rc == -2:                                       # NOCF_E_SHAPE: refused before anything was enqueued
-            raise NotImplementedError(f"{what}: nTh = {net.nTh}, m = {net.m}, d = {net.d}, r = {phi_st.r}: no lane and no one-CU "
-                                      f"instantiation takes this shape; {_FAMILIES}")
-        _lib.check(rc, "nocf_rollout_held_f32")
-        _lib.track_rollout_status(L, dev, what)
-        if intermediates:
-            _lib.check_errors(sync=True)                   # consumed on the host (plots, files): a failed launch raises here
+    refused = NotImplementedError(f"{what}: nTh = {net.nTh}, m = {net.m}, d = {net.d}, r = {net.A.shape[0]}: no lane and no one-CU "
+                                  f"instantiation takes this shape; {_FAMILIES}")
+    # (the shipped library: a per-shape build specialises the per-tile kernels, which take no held control)
+    means, persample, _sums, z_final, zFull, ctrlFull = _evaluate(what, "nocf_rollout_held_f32", x, net, prob, tspan, nt, stepper, alph,
+                                                                  intermediates, extra=(hold,), W=W, shipped=True, shape_error=refused)
     return means, persample, z_final, zFull, ctrlFull
 
 

@@ -86,13 +86,11 @@ def ascend_disturbances(W, g, eps, step_size, mask=None):
         raise ValueError("W must be contiguous (it is updated in place)")
     nt, n, d = W.shape
     dev = W.device
-    entries = adversary._entries(_lib.lib())
-    if entries is None:
-        raise RuntimeError("ascend_disturbances: the HIP library does not export nocf_disturbance_ascent_f32; rebuild it")
+    (ascent,) = _lib.require(_lib.lib(), ("nocf_disturbance_ascent_f32",), "ascend_disturbances")
     gc = g.detach().contiguous()
     mk = None if mask is None else (mask.reshape(-1) != 0).to(device=dev, dtype=torch.float32).contiguous()
     with torch.cuda.device(dev):
-        rc = entries[2](_lib.ptr(W.detach()), _lib.ptr(gc), _lib.ptr(mk), int(n), int(nt), int(d), step_size, eps, _lib.stream_ptr(dev))
+        rc = ascent(_lib.ptr(W.detach()), _lib.ptr(gc), _lib.ptr(mk), int(n), int(nt), int(d), step_size, eps, _lib.stream_ptr(dev))
     _lib.check(rc, "nocf_disturbance_ascent_f32")
     return W
 

@@ -16,53 +16,25 @@ the kernels (nocf_noise_fill_corr_f32, nocf_rollout_noisy_corr_f32, nocf_rollout
 its entry points, untouched, and rho=0.0 gives the white values through the new ones.
 
 Single precision only; no CPU or eager-torch fallback; every check raises before a device is touched."""
-import ctypes as C
 import math
-import os
 
 import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .OCflow import _STEPPERS
-from .train import _OCflowTrain
-
-_FILL_ARGTYPES = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_int64, C.c_void_p]
-_NOISY_ARGTYPES = [C.POINTER(_lib.NocfPhi), C.POINTER(_lib.NocfProb), C.c_void_p, C.c_void_p, C.c_uint64, C.c_int64, C.c_int64,
-                   C.c_double, C.c_double, C.c_int32, C.c_int32, _lib.fp,
-                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                   C.c_void_p, C.c_size_t, C.c_void_p]
-_RECORD_ARGTYPES = [C.POINTER(_lib.NocfPhi), C.POINTER(_lib.NocfProb), C.c_void_p, C.c_void_p, C.c_uint64, C.c_int64, C.c_int64,
-                    C.c_double, C.c_double, C.c_int32, C.c_int32, _lib.fp,
-                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
-                    C.c_void_p, C.c_size_t, C.c_void_p]
-# (the correlated entries: scale0, scale1, rho where `scale` stands)
-_PROTOTYPES = {"nocf_noise_fill_f32": _FILL_ARGTYPES, "nocf_rollout_noisy_f32": _NOISY_ARGTYPES,
-               "nocf_rollout_record_noisy_f32": _RECORD_ARGTYPES,
-               "nocf_noise_fill_corr_f32": _FILL_ARGTYPES[:4] + [C.c_void_p] * 3 + _FILL_ARGTYPES[5:],
-               "nocf_rollout_noisy_corr_f32": _NOISY_ARGTYPES[:3] + [C.c_void_p] * 3 + _NOISY_ARGTYPES[4:],
-               "nocf_rollout_record_noisy_corr_f32": _RECORD_ARGTYPES[:3] + [C.c_void_p] * 3 + _RECORD_ARGTYPES[4:]}
+from .OCflow import _check_args, _evaluate
+from .train import _OCflowTrain, _record_forward, _structs
 
 
 def _entry(L, name):
-    """entry `name` of library L with its prototype set, or None when L does not export it"""
-    if not hasattr(L, name):
-        return None
-    f = getattr(L, name)
-    if f.argtypes is None:
-        f.restype = C.c_int
-        f.argtypes = _PROTOTYPES[name]
-    return f
+    """entry `name` of library L, or None when L does not export it"""
+    f = _lib.entries(L, (name,))
+    return f and f[0]
 
 
 def _entry_for(L, name, what):
     """(library, entry): L's, or the shipped library's when L is a per-shape library cached by an older build"""
-    f = _entry(L, name)
-    if f is None:
-        L = _lib.lib()
-        f = _entry(L, name)
-    if f is None:
-        raise RuntimeError(f"{what}: the HIP library does not export {name}; rebuild it")
+    L, (f,) = _lib.entry_for(L, (name,), what)
     return L, f
 
 
@@ -178,20 +150,7 @@ def _check_call(what, x, net, nt, stepper, alph):
         raise RuntimeError(f"{what}: x is float64; the noisy rollout is single precision only (the double-precision kernel takes no disturbance)")
     if not isinstance(x, torch.Tensor):
         raise TypeError("x must be a torch.Tensor")
-    if x.dim() != 2:
-        raise ValueError("x must be nex-by-d")
-    n, d = x.shape
-    if d != net.d:
-        raise ValueError(f"x has d={d} but Phi was built for d={net.d}")
-    if int(nt) < 1:
-        raise ValueError("nt must be >= 1")
-    if n < 1:
-        raise ValueError("x has no rows")
-    if stepper not in _STEPPERS:
-        raise ValueError(f"stepper must be 'rk4' or 'rk1', got {stepper!r}")
-    if len(alph) < 6:
-        raise ValueError("alph needs 6 entries")
-    return n, d
+    return _check_args(x, net, nt, stepper, alph, rows=True)
 
 
 def noisy_rollout(x, Phi, prob, nt, sigma, seed, tspan=(0., 1.), alph=None, stepper="rk4", intermediates=False, mask=None, row_offset=0,
@@ -210,42 +169,12 @@ def noisy_rollout(x, Phi, prob, nt, sigma, seed, tspan=(0., 1.), alph=None, step
     scale = noise_scale(sigma, nt, d, tspan, mask)
     corr = None if rho is None else noise_corr_scales(sigma, rho, nt, d, tspan, mask)[1:]
     seed, row_offset = _check_seed(seed), _check_row_offset(row_offset)
-    x = _lib.require_device_f32(x, "x")
-    Phi._guard_no_autograd(x, "noisy_rollout")
-    with torch.no_grad():
-        _lib.check_errors()
-        phi_st, keep1, ws = Phi._c_struct(n)
-        prob_st, keep2 = prob._c_struct(x.device)
-        dev = x.device
-        scale = scale.to(dev)
-        name = "nocf_rollout_noisy_f32" if corr is None else "nocf_rollout_noisy_corr_f32"
-        tables = (_lib.ptr(scale),)
-        if corr is not None:
-            corr = tuple(t.to(dev) for t in corr)
-            tables += (_lib.ptr(corr[0]), _lib.ptr(corr[1]))
-        persample = torch.empty(n, 7, dtype=torch.float32, device=dev)
-        sums = torch.empty(8, dtype=torch.float32, device=dev)
-        means = torch.empty(8, dtype=torch.float32, device=dev)
-        z_final = torch.empty(n, d + 4, dtype=torch.float32, device=dev)
-        zFull = ctrlFull = None
-        if intermediates:
-            cdim = _lib.lib().nocf_ctrl_dim(C.byref(prob_st), d)
-            zFull = torch.empty(nt + 1, n, d + 4, dtype=torch.float32, device=dev)
-            ctrlFull = torch.empty(nt + 1, n, cdim, dtype=torch.float32, device=dev)
-        alph_c = (C.c_float * 6)(*[float(a) for a in alph[:6]])
-        with torch.cuda.device(dev):
-            L = _lib.lib_for(Phi.d, Phi.m, Phi.nTh, phi_st.r, prob_st.n_agents, fwd=prob_st.kind != _lib.PROB_QUADCOPTER)
-            L, f = _entry_for(L, name, "noisy_rollout")
-            rc = f(C.byref(phi_st), C.byref(prob_st), _lib.ptr(x), *tables, seed, row_offset, n,
-                   float(tspan[0]), float(tspan[1]), int(nt), _STEPPERS[stepper], alph_c,
-                   _lib.ptr(z_final), _lib.ptr(persample), _lib.ptr(sums), _lib.ptr(means), _lib.ptr(zFull), _lib.ptr(ctrlFull),
-                   _lib.ptr(ws), ws.numel() * ws.element_size(), _lib.stream_ptr(dev))
-        _lib.check(rc, name)
-        _lib.track_rollout_status(L, dev, "noisy_rollout")
-        out = {"Jc": means[7], "cs": [means[i] for i in range(7)], "persample": persample, "z_final": z_final}
-        if intermediates:
-            _lib.check_errors(sync=True)                   # consumed on the host (plots, files): a failed launch raises here
-            out["traj"], out["ctrl"] = zFull.permute(1, 2, 0), ctrlFull.permute(1, 2, 0)
+    name = "nocf_rollout_noisy_f32" if corr is None else "nocf_rollout_noisy_corr_f32"
+    means, persample, _sums, z_final, zFull, ctrlFull = _evaluate("noisy_rollout", name, x, Phi, prob, tspan, nt, stepper, alph, intermediates,
+                                                                  extra=(scale,) + tuple(corr or ()) + (seed, row_offset))
+    out = {"Jc": means[7], "cs": [means[i] for i in range(7)], "persample": persample, "z_final": z_final}
+    if intermediates:
+        out["traj"], out["ctrl"] = zFull.permute(1, 2, 0), ctrlFull.permute(1, 2, 0)
     return out
 
 
@@ -259,45 +188,11 @@ class _OCflowTrainNoisy(torch.autograd.Function):
         ctx.x_needs_grad = bool(x.requires_grad)
         x = _lib.require_device_f32(x.detach(), "x")
         scale, seed, row_offset = noise[:3]                # (with rho: two more entries, the tables s1 and rho; scale is then s0)
-        n, d = x.shape
-        dev = x.device
-        scale = scale.to(dev)
-        corr = tuple(t.to(dev) for t in noise[3:])
-        name = "nocf_rollout_record_noisy_corr_f32" if corr else "nocf_rollout_record_noisy_f32"
-        tables = (_lib.ptr(scale),) + tuple(_lib.ptr(t) for t in corr)
-        phi_st, keep1, ws = net._c_struct(n)
-        prob_st, keep2 = prob._c_struct(dev)
-        nstage = 4 if stepper == "rk4" else 1
-        persample = torch.empty(n, 7, device=dev)
-        sums = torch.empty(8, device=dev)
-        z_out = torch.empty(n, d + 4, device=dev)
-        s_all = torch.empty(nt * nstage, n, d + 1, device=dev)
-        alph_c = (C.c_float * 6)(*[float(a) for a in alph[:6]])
-        _lib.check_errors()
-        ctx.tape = None
-        with torch.cuda.device(dev):
-            L = _lib.lib_for(net.d, net.m, net.nTh, phi_st.r, prob_st.n_agents, fwd=prob_st.kind != _lib.PROB_QUADCOPTER)
-            L, f = _entry_for(L, name, "noisy_ocflow_train")
-            ctx.mid_rows = int(L.nocf_mid_grad_rows(int(d), int(net.m), int(net.nTh), int(phi_st.r), int(prob_st.n_agents), int(n))) \
-                if hasattr(L, "nocf_rollout_bwd_mid_f32") else 0
-            # (the activation record is the one-CU kernel's here, as in _OCflowTrainDisturbed: m = 512 records on the per-tile kernel)
-            nact = 0 if (os.environ.get("NOCF_ACT_REC", "1") in ("0", "") or net.m > 128) else int(
-                L.nocf_activation_record_floats(int(d), int(net.m), int(net.nTh), int(n), int(nt), _STEPPERS[stepper]))
-            act = None
-            if nact:
-                try:
-                    act = torch.empty(nact, device=dev)
-                except torch.OutOfMemoryError:                 # the record is an optimisation: without it the adjoint recomputes
-                    act = None
-            recorded = C.c_int32(0)
-            rc = f(C.byref(phi_st), C.byref(prob_st), _lib.ptr(x), *tables, seed, row_offset, n,
-                   float(tspan[0]), float(tspan[1]), int(nt), _STEPPERS[stepper], alph_c,
-                   _lib.ptr(z_out), _lib.ptr(persample), _lib.ptr(sums), _lib.ptr(s_all), _lib.ptr(act), C.byref(recorded),
-                   _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-        _lib.check(rc, name)
-        ctx.act = act if recorded.value else None
-        ctx.persample = persample                          # (the [n, 7] table: risk._OCflowTrainWeighted forms the per-sample costs from it)
-        return _OCflowTrain._forward_tail(ctx, L, dev, net, prob, tspan, nt, stepper, alph, n_total, group, n, sums, s_all, z_out)
+        tables = [t.to(x.device) for t in (scale,) + tuple(noise[3:])]
+        name = "nocf_rollout_record_noisy_corr_f32" if noise[3:] else "nocf_rollout_record_noisy_f32"
+        # (the activation record is the one-CU kernel's here, as in _OCflowTrainDisturbed: m = 512 records on the per-tile kernel)
+        return _record_forward(ctx, _structs(x, net, prob), name, "noisy_ocflow_train", x, tuple(_lib.ptr(t) for t in tables) + (seed, row_offset),
+                               net, prob, tspan, nt, stepper, alph, n_total, group, one_cu_only=True)
 
     @staticmethod
     @once_differentiable

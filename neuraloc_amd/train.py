@@ -134,73 +134,50 @@ class _OCflowTrain(torch.autograd.Function):
         if pd_ is not None and int(pd_) != d:
             raise ValueError(f"the problem object has d={pd_} but x has d={d}")
         dev = x.device
-        phi_st, keep1, ws = net._c_struct(n)
-        prob_st, keep2 = prob._c_struct(dev)
+        S = _structs(x, net, prob)                       # (the recording forward; the adjoint below asks for its library again)
+        phi_st, prob_st, ws, L = S[:4]
         nstage = 4 if stepper == "rk4" else 1
-        persample = torch.empty(n, 7, device=dev)
-        sums = torch.empty(8, device=dev)
-        z_out = torch.empty(n, d + 4, device=dev)
-        alph_c = (C.c_float * 6)(*[float(a) for a in alph[:6]])
-        _lib.check_errors()
         ctx.tape = None
         ctx.mid_rows = 0
-        with torch.cuda.device(dev):
-            L = _lib.lib_for(net.d, net.m, net.nTh, phi_st.r, prob_st.n_agents, fwd=prob_st.kind != _lib.PROB_QUADCOPTER)      # (the recording forward; the adjoint below asks again)
-            # Training tape (wide two-layer networks on the split-role kernel): the recording forward keeps what autograd would keep of the
-            # unrolled graph -- u0, tanh(o), tanh(q), a, grad Phi and three scalars of every evaluation, the terminal one included, 2.9 GB for
-            # swarm50 -- and the backward is the split-role adjoint (csrc/nocf_duo_bwd.inc).  NOCF_DUO_BWD=0: the per-tile adjoint below.
-            # (nocf_tape_floats knows the network's shape only: the split-role ADJOINT also needs a point-agent problem and r <= 10 -- asked
-            # here, so that a shape the tape cannot serve takes the activation-record path below instead of holding 2.9 GB for nothing)
-            tape_ok = (hasattr(L, "nocf_tape_floats") and os.environ.get("NOCF_ACT_REC", "1") not in ("0", "")
-                       and prob_st.kind != _lib.PROB_QUADCOPTER and phi_st.r <= 10)
-            ntape = int(L.nocf_tape_floats(int(d), int(net.m), int(net.nTh), int(n), int(nt), _STEPPERS[stepper])) if tape_ok else 0
-            tape = None
-            if ntape:
-                try:
-                    tape = torch.empty(ntape, device=dev)
-                except torch.OutOfMemoryError:
-                    tape = None
-            if tape is not None:
-                s_all = torch.empty(nt * nstage + 1, n, d + 1, device=dev)
-                recorded = C.c_int32(0)
+        # Training tape (wide two-layer networks on the split-role kernel): the recording forward keeps what autograd would keep of the
+        # unrolled graph -- u0, tanh(o), tanh(q), a, grad Phi and three scalars of every evaluation, the terminal one included, 2.9 GB for
+        # swarm50 -- and the backward is the split-role adjoint (csrc/nocf_duo_bwd.inc).  NOCF_DUO_BWD=0: the per-tile adjoint below.
+        # (nocf_tape_floats knows the network's shape only: the split-role ADJOINT also needs a point-agent problem and r <= 10 -- asked
+        # here, so that a shape the tape cannot serve takes the activation-record path below instead of holding 2.9 GB for nothing)
+        tape_ok = (hasattr(L, "nocf_tape_floats") and os.environ.get("NOCF_ACT_REC", "1") not in ("0", "")
+                   and prob_st.kind != _lib.PROB_QUADCOPTER and phi_st.r <= 10)
+        ntape = int(L.nocf_tape_floats(int(d), int(net.m), int(net.nTh), int(n), int(nt), _STEPPERS[stepper])) if tape_ok else 0
+        tape = None
+        if ntape:
+            try:
+                tape = torch.empty(ntape, device=dev)
+            except torch.OutOfMemoryError:
+                tape = None
+        if tape is not None:
+            persample = torch.empty(n, 7, device=dev)
+            sums = torch.empty(8, device=dev)
+            z_out = torch.empty(n, d + 4, device=dev)
+            s_all = torch.empty(nt * nstage + 1, n, d + 1, device=dev)
+            alph_c = (C.c_float * 6)(*[float(a) for a in alph[:6]])
+            recorded = C.c_int32(0)
+            _lib.check_errors()
+            with torch.cuda.device(dev):
                 rc = L.nocf_rollout_tape_f32(C.byref(phi_st), C.byref(prob_st), _lib.ptr(x), n,
                                              float(tspan[0]), float(tspan[1]), int(nt), _STEPPERS[stepper], alph_c,
                                              _lib.ptr(z_out), _lib.ptr(persample), _lib.ptr(sums), _lib.ptr(s_all),
                                              _lib.ptr(tape), C.byref(recorded),
                                              _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-                _lib.check(rc, "nocf_rollout_tape_f32")
-                if recorded.value:
-                    ctx.tape = tape
-                    ctx.tape_lib = L                              # the adjoint must read this tape with the library that wrote it
-                else:                                             # another kernel ran (residency, a knob): no tape -- the forward is
-                    tape = None                                   # repeated below WITH the activation record that kernel can write
-        if tape is not None:
-            return _OCflowTrain._forward_tail(ctx, L, dev, net, prob, tspan, nt, stepper, alph, n_total, group, n, sums, s_all, z_out)
-        s_all = torch.empty(nt * nstage, n, d + 1, device=dev)
-        with torch.cuda.device(dev):
-            # activation record (wide two-layer networks on the split-role kernel): the forward keeps u0, tanh(o), tanh(q), a and grad Phi
-            # of every evaluation -- autograd's saved tensors, 2.9 GB for swarm50 -- and the adjoint loads them instead of re-running
-            # grad Phi's forward sweep (NOCF_ACT_REC=0: recompute, as for every other shape)
-            ctx.mid_rows = int(L.nocf_mid_grad_rows(int(d), int(net.m), int(net.nTh), int(phi_st.r), int(prob_st.n_agents), int(n))) \
-                if hasattr(L, "nocf_rollout_bwd_mid_f32") else 0
-            nact = 0 if os.environ.get("NOCF_ACT_REC", "1") in ("0", "") else int(
-                L.nocf_activation_record_floats(int(d), int(net.m), int(net.nTh), int(n), int(nt), _STEPPERS[stepper]))
-            act = None
-            if nact:
-                try:
-                    act = torch.empty(nact, device=dev)
-                except torch.OutOfMemoryError:                     # the record is an optimisation: without it the adjoint recomputes
-                    act = None
-            recorded = C.c_int32(0)
-            rc = L.nocf_rollout_record_act_f32(
-                                                    C.byref(phi_st), C.byref(prob_st), _lib.ptr(x), n,
-                                                    float(tspan[0]), float(tspan[1]), int(nt), _STEPPERS[stepper], alph_c,
-                                                    _lib.ptr(z_out), _lib.ptr(persample), _lib.ptr(sums), _lib.ptr(s_all),
-                                                    _lib.ptr(act), C.byref(recorded),
-                                                    _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-        _lib.check(rc, "nocf_rollout_record_act_f32")
-        ctx.act = act if recorded.value else None
-        return _OCflowTrain._forward_tail(ctx, L, dev, net, prob, tspan, nt, stepper, alph, n_total, group, n, sums, s_all, z_out)
+            _lib.check(rc, "nocf_rollout_tape_f32")
+            if recorded.value:
+                ctx.tape = tape
+                ctx.tape_lib = L                              # the adjoint must read this tape with the library that wrote it
+                return _OCflowTrain._forward_tail(ctx, L, dev, net, prob, tspan, nt, stepper, alph, n_total, group, n, sums, s_all, z_out)
+            # another kernel ran (residency, a knob): no tape -- the forward is repeated WITH the activation record that kernel can write
+            tape = None
+        # activation record (wide two-layer networks on the split-role kernel): the forward keeps u0, tanh(o), tanh(q), a and grad Phi
+        # of every evaluation -- autograd's saved tensors, 2.9 GB for swarm50 -- and the adjoint loads them instead of re-running
+        # grad Phi's forward sweep (NOCF_ACT_REC=0: recompute, as for every other shape)
+        return _record_forward(ctx, S, "nocf_rollout_record_act_f32", "OCflow", x, (), net, prob, tspan, nt, stepper, alph, n_total, group)
 
     @staticmethod
     def _forward_tail(ctx, L, dev, net, prob, tspan, nt, stepper, alph, n_total, group, n, sums, s_all, z_out):
@@ -258,24 +235,12 @@ class _OCflowTrain(torch.autograd.Function):
         lib = _lib.lib_for(net.d, net.m, net.nTh, phi_st.r, prob_st.n_agents)
         lamW = ()                                                   # the joint entries take lamW right behind lam0; the existing ones nothing
         if want_w:
-            joint = _joint_entries(lib)
-            if joint is None:                              # a per-shape library cached by an older build: the shipped library has the entries
-                lib = _lib.lib()
-                joint = _joint_entries(lib)
-            if joint is None:
-                raise RuntimeError("minmax_ocflow_train: the HIP library does not export nocf_rollout_bwd_small_w_f32 / _mid_w_f32 / _act_w_f32; "
-                                   "rebuild it")
+            lib, joint = _lib.entry_for(lib, _JOINT, "minmax_ocflow_train")
             ctx.lamW = torch.empty(int(nt), n, d, device=dev)
             lamW = (_lib.ptr(ctx.lamW),)
         inv_n = 1.0 / float(ctx.n_total)                            # the cotangent seed: one scalar, or (weighted entries) one weight per row
         if wrow is not None:
-            weighted = _weighted_entries(lib)
-            if weighted is None:                           # a per-shape library cached by an older build: the shipped library has the entries
-                lib = _lib.lib()
-                weighted = _weighted_entries(lib)
-            if weighted is None:
-                raise RuntimeError("weighted_ocflow_train: the HIP library does not export nocf_rollout_bwd_small_rw_f32 / _mid_rw_f32 / "
-                                   "_act_rw_f32; rebuild it")
+            lib, weighted = _lib.entry_for(lib, _WEIGHTED, "weighted_ocflow_train")
             inv_n = _lib.ptr(wrow)
         f_small, f_mid, f_act = joint if want_w else (weighted if wrow is not None else (
             lib.nocf_rollout_bwd_small_f32, getattr(lib, "nocf_rollout_bwd_mid_f32", None), lib.nocf_rollout_bwd_act_f32))
@@ -451,47 +416,10 @@ class _OCflowTrainDisturbed(torch.autograd.Function):
         ctx.x_needs_grad = bool(x.requires_grad)
         x = _lib.require_device_f32(x.detach(), "x")
         W = _lib.require_device_f32(W.detach(), "W")
-        n, d = x.shape
-        dev = x.device
-        phi_st, keep1, ws = net._c_struct(n)
-        prob_st, keep2 = prob._c_struct(dev)
-        nstage = 4 if stepper == "rk4" else 1
-        persample = torch.empty(n, 7, device=dev)
-        sums = torch.empty(8, device=dev)
-        z_out = torch.empty(n, d + 4, device=dev)
-        s_all = torch.empty(nt * nstage, n, d + 1, device=dev)
-        alph_c = (C.c_float * 6)(*[float(a) for a in alph[:6]])
-        _lib.check_errors()
-        ctx.tape = None
-        with torch.cuda.device(dev):
-            L = _lib.lib_for(net.d, net.m, net.nTh, phi_st.r, prob_st.n_agents, fwd=prob_st.kind != _lib.PROB_QUADCOPTER)
-            f = _disturbed_entry(L)
-            if f is None:                                  # a per-shape library cached by an older build: the shipped library has the entry
-                L = _lib.lib()
-                f = _disturbed_entry(L)
-            if f is None:
-                raise RuntimeError("disturbed_ocflow_train: the HIP library does not export nocf_rollout_record_disturbed_f32; rebuild it")
-            ctx.mid_rows = int(L.nocf_mid_grad_rows(int(d), int(net.m), int(net.nTh), int(phi_st.r), int(prob_st.n_agents), int(n))) \
-                if hasattr(L, "nocf_rollout_bwd_mid_f32") else 0
-            # the activation record is the one-CU kernel's here (m <= 128): the split-role kernel, whose record nocf_activation_record_floats
-            # also sizes (2.9 GB for swarm50), never runs a disturbed call -- m = 512 records on the per-tile kernel and its adjoint recomputes
-            nact = 0 if (os.environ.get("NOCF_ACT_REC", "1") in ("0", "") or net.m > 128) else int(
-                L.nocf_activation_record_floats(int(d), int(net.m), int(net.nTh), int(n), int(nt), _STEPPERS[stepper]))
-            act = None
-            if nact:
-                try:
-                    act = torch.empty(nact, device=dev)
-                except torch.OutOfMemoryError:                     # the record is an optimisation: without it the adjoint recomputes
-                    act = None
-            recorded = C.c_int32(0)
-            rc = f(C.byref(phi_st), C.byref(prob_st), _lib.ptr(x), _lib.ptr(W), n,
-                   float(tspan[0]), float(tspan[1]), int(nt), _STEPPERS[stepper], alph_c,
-                   _lib.ptr(z_out), _lib.ptr(persample), _lib.ptr(sums), _lib.ptr(s_all), _lib.ptr(act), C.byref(recorded),
-                   _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-        _lib.check(rc, "nocf_rollout_record_disturbed_f32")
-        ctx.act = act if recorded.value else None
-        ctx.persample = persample                          # (the [n, 7] table: risk._OCflowTrainWeighted forms the per-sample costs from it)
-        return _OCflowTrain._forward_tail(ctx, L, dev, net, prob, tspan, nt, stepper, alph, n_total, group, n, sums, s_all, z_out)
+        # the activation record is the one-CU kernel's here (m <= 128): the split-role kernel, whose record nocf_activation_record_floats
+        # also sizes (2.9 GB for swarm50), never runs a disturbed call -- m = 512 records on the per-tile kernel and its adjoint recomputes
+        return _record_forward(ctx, _structs(x, net, prob), "nocf_rollout_record_disturbed_f32", "disturbed_ocflow_train", x, (_lib.ptr(W),),
+                               net, prob, tspan, nt, stepper, alph, n_total, group, one_cu_only=True)
 
     @staticmethod
     @once_differentiable
@@ -499,67 +427,75 @@ class _OCflowTrainDisturbed(torch.autograd.Function):
         return _OCflowTrain._adjoint(ctx, gJ)
 
 
-_DISTURBED_ARGTYPES = [C.POINTER(_lib.NocfPhi), C.POINTER(_lib.NocfProb), C.c_void_p, C.c_void_p, C.c_int64,
-                       C.c_double, C.c_double, C.c_int32, C.c_int32, _lib.fp,
-                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
-                       C.c_void_p, C.c_size_t, C.c_void_p]
+def _structs(x, net, prob):
+    """what a recording forward on x calls its entry with: (NocfPhi, NocfProb, workspace, the shape's library, keep-alive lists)"""
+    phi_st, keep1, ws = net._c_struct(x.shape[0])
+    prob_st, keep2 = prob._c_struct(x.device)
+    L = _lib.lib_for(net.d, net.m, net.nTh, phi_st.r, prob_st.n_agents, fwd=prob_st.kind != _lib.PROB_QUADCOPTER)
+    return phi_st, prob_st, ws, L, (keep1, keep2)
 
 
-_JOINT_HEAD = [C.POINTER(_lib.NocfPhi), C.POINTER(_lib.NocfProb), C.c_int64, C.c_int32, C.c_int32, C.c_double,
-               _lib.fp, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
-_JOINT_ARGTYPES = {"nocf_rollout_bwd_small_w_f32": _JOINT_HEAD + [C.c_void_p] * 4,
-                   "nocf_rollout_bwd_mid_w_f32": _JOINT_HEAD + [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
-                                                                C.c_void_p, C.c_size_t, C.c_void_p],
-                   "nocf_rollout_bwd_act_w_f32": _JOINT_HEAD + [C.c_void_p] * 13 + [C.c_void_p, C.c_size_t, C.c_void_p]}
+def _activation_record(L, net, n, nt, stepper, dev, one_cu_only=False):
+    """the tensor a recording forward writes its activation record into (nocf_activation_record_floats of them), or None: NOCF_ACT_REC=0, a
+    shape that records nothing, no memory for it -- the record is an optimisation: without it the adjoint recomputes -- and, one_cu_only (the
+    disturbed calls, which never run the split-role kernel: only the one-CU kernel records there), m > 128"""
+    if os.environ.get("NOCF_ACT_REC", "1") in ("0", "") or (one_cu_only and net.m > 128):
+        return None
+    nact = int(L.nocf_activation_record_floats(int(net.d), int(net.m), int(net.nTh), int(n), int(nt), _STEPPERS[stepper]))
+    try:
+        return torch.empty(nact, device=dev) if nact else None
+    except torch.OutOfMemoryError:
+        return None
 
 
-_WEIGHTED_HEAD = [C.POINTER(_lib.NocfPhi), C.POINTER(_lib.NocfProb), C.c_int64, C.c_int32, C.c_int32, C.c_double,
-                  _lib.fp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-_WEIGHTED_ARGTYPES = {"nocf_rollout_bwd_small_rw_f32": _WEIGHTED_HEAD + [C.c_void_p] * 3,
-                      "nocf_rollout_bwd_mid_rw_f32": _WEIGHTED_HEAD + [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                                                       C.c_void_p, C.c_size_t, C.c_void_p],
-                      "nocf_rollout_bwd_act_rw_f32": _WEIGHTED_HEAD + [C.c_void_p] * 12 + [C.c_void_p, C.c_size_t, C.c_void_p]}
+def _record_forward(ctx, S, name, what, x, extra, net, prob, tspan, nt, stepper, alph, n_total, group, one_cu_only=False):
+    """the recording forward through entry `name` (nocf_rollout_record_act_f32 or a sibling that takes `extra` between x and n), on the
+    structs S = _structs(x, net, prob): saves on ctx what _OCflowTrain._adjoint reads and goes on to _forward_tail"""
+    phi_st, prob_st, ws, L = S[:4]
+    n, d = x.shape
+    dev = x.device
+    nstage = 4 if stepper == "rk4" else 1
+    persample = torch.empty(n, 7, device=dev)
+    sums = torch.empty(8, device=dev)
+    z_out = torch.empty(n, d + 4, device=dev)
+    s_all = torch.empty(nt * nstage, n, d + 1, device=dev)
+    alph_c = (C.c_float * 6)(*[float(a) for a in alph[:6]])
+    _lib.check_errors()
+    ctx.tape = None
+    with torch.cuda.device(dev):
+        L, (f,) = _lib.entry_for(L, (name,), what)
+        ctx.mid_rows = int(L.nocf_mid_grad_rows(int(d), int(net.m), int(net.nTh), int(phi_st.r), int(prob_st.n_agents), int(n))) \
+            if hasattr(L, "nocf_rollout_bwd_mid_f32") else 0
+        act = _activation_record(L, net, n, nt, stepper, dev, one_cu_only)
+        recorded = C.c_int32(0)
+        rc = f(C.byref(phi_st), C.byref(prob_st), _lib.ptr(x), *extra, n,
+               float(tspan[0]), float(tspan[1]), int(nt), _STEPPERS[stepper], alph_c,
+               _lib.ptr(z_out), _lib.ptr(persample), _lib.ptr(sums), _lib.ptr(s_all), _lib.ptr(act), C.byref(recorded),
+               _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+    _lib.check(rc, name)
+    ctx.act = act if recorded.value else None
+    ctx.persample = persample                              # (the [n, 7] table: risk._OCflowTrainWeighted forms the per-sample costs from it)
+    return _OCflowTrain._forward_tail(ctx, L, dev, net, prob, tspan, nt, stepper, alph, n_total, group, n, sums, s_all, z_out)
+
+
+_JOINT = ("nocf_rollout_bwd_small_w_f32", "nocf_rollout_bwd_mid_w_f32", "nocf_rollout_bwd_act_w_f32")
+_WEIGHTED = ("nocf_rollout_bwd_small_rw_f32", "nocf_rollout_bwd_mid_rw_f32", "nocf_rollout_bwd_act_rw_f32")
 
 
 def _weighted_entries(L):
-    """(nocf_rollout_bwd_small_rw_f32, nocf_rollout_bwd_mid_rw_f32, nocf_rollout_bwd_act_rw_f32) of library L with their prototypes set --
-    the existing adjoint entries with `const float* wrow` in place of `double inv_n` --, or None when L lacks one of them"""
-    out = []
-    for name, argtypes in _WEIGHTED_ARGTYPES.items():
-        if not hasattr(L, name):
-            return None
-        f = getattr(L, name)
-        if f.argtypes is None:
-            f.restype = C.c_int
-            f.argtypes = argtypes
-        out.append(f)
-    return tuple(out)
+    """the existing adjoint entries with `const float* wrow` in place of `double inv_n` (_WEIGHTED) of library L, or None when L lacks one"""
+    return _lib.entries(L, _WEIGHTED)
 
 
 def _joint_entries(L):
-    """(nocf_rollout_bwd_small_w_f32, nocf_rollout_bwd_mid_w_f32, nocf_rollout_bwd_act_w_f32) of library L with their prototypes set --
-    the existing adjoint entries with `float* lamW` behind lam0 --, or None when L lacks one of them"""
-    out = []
-    for name, argtypes in _JOINT_ARGTYPES.items():
-        if not hasattr(L, name):
-            return None
-        f = getattr(L, name)
-        if f.argtypes is None:
-            f.restype = C.c_int
-            f.argtypes = argtypes
-        out.append(f)
-    return tuple(out)
+    """the existing adjoint entries with `float* lamW` behind lam0 (_JOINT) of library L, or None when L lacks one"""
+    return _lib.entries(L, _JOINT)
 
 
 def _disturbed_entry(L):
-    """nocf_rollout_record_disturbed_f32 of library L with its prototype set, or None when L does not export it"""
-    if not hasattr(L, "nocf_rollout_record_disturbed_f32"):
-        return None
-    f = L.nocf_rollout_record_disturbed_f32
-    if f.argtypes is None:
-        f.restype = C.c_int
-        f.argtypes = _DISTURBED_ARGTYPES
-    return f
+    """nocf_rollout_record_disturbed_f32 of library L, or None when L does not export it"""
+    f = _lib.entries(L, ("nocf_rollout_record_disturbed_f32",))
+    return f and f[0]
 
 
 class _OCflowTrain64(torch.autograd.Function):

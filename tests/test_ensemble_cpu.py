@@ -105,9 +105,9 @@ def test_prototypes_are_in_the_header():
         args = mt.group(1)
         assert "int32_t members" in args and "const float* alph" in args and extra in args, name
         assert ("int64_t x_member_stride" in args) == (name != "nocf_rollout_bwd_small_ensemble_f32")
-    assert set(ensemble._ARGTYPES) == {"nocf_rollout_ensemble_f32", "nocf_rollout_record_ensemble_f32", "nocf_rollout_bwd_small_ensemble_f32"}
+    assert set(ensemble._LANE) == {"nocf_rollout_ensemble_f32", "nocf_rollout_record_ensemble_f32", "nocf_rollout_bwd_small_ensemble_f32"}
     # the ctypes prototypes have the header's argument counts
-    for name, argtypes in ensemble._ARGTYPES.items():
+    for name, argtypes in ((name, _lib.PROTOTYPES[name][1]) for name in ensemble._LANE):
         args = re.search(r"int " + name + r"\(([^;]*)\);", flat).group(1)
         assert len(argtypes) == len(args.split(",")), name
 

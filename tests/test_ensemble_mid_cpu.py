@@ -174,16 +174,16 @@ def test_prototypes_are_in_the_header():
                                                     "int32_t* recorded, void* workspace, size_t workspace_bytes, void* stream",
             "nocf_rollout_bwd_mid_ensemble_f32": "const float* act_rec, float* gpart, int64_t gpart_rows, float* lam0, void* workspace, "
                                                  "size_t workspace_bytes, void* stream"}
-    assert set(ensemble._ARGTYPES_MID) == set(want)
+    assert set(ensemble._MID) == set(want)
     for name, tail in want.items():
         mt = re.search(r"int " + name + r"\(([^;]*)\);", flat)
         assert mt, name
         args = mt.group(1)
         assert "int32_t members" in args and "const float* alph" in args and args.endswith(tail), name
         assert ("int64_t x_member_stride" in args) == (name != "nocf_rollout_bwd_mid_ensemble_f32")
-        assert len(ensemble._ARGTYPES_MID[name]) == len(args.split(",")), name          # the ctypes prototypes have the header's argument counts
+        assert len(_lib.PROTOTYPES[name][1]) == len(args.split(",")), name          # the ctypes prototypes have the header's argument counts
     # the lane family's three entries are what they were
-    assert set(ensemble._ARGTYPES) == {"nocf_rollout_ensemble_f32", "nocf_rollout_record_ensemble_f32", "nocf_rollout_bwd_small_ensemble_f32"}
+    assert set(ensemble._LANE) == {"nocf_rollout_ensemble_f32", "nocf_rollout_record_ensemble_f32", "nocf_rollout_bwd_small_ensemble_f32"}
 
 
 def test_the_eligibility_mirror_agrees_with_the_one_cu_sweep():

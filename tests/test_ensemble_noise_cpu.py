@@ -145,7 +145,7 @@ def test_prototypes_are_in_the_header_and_the_library_exports_them():
                "nocf_rollout_noisy_mid_ensemble_f32": "nocf_rollout_mid_ensemble_f32",
                "nocf_rollout_record_noisy_mid_ensemble_f32": "nocf_rollout_record_mid_ensemble_f32"}
     assert list(sibling) == SYMBOLS
-    protos = {name: argtypes for fam in ensemble_noise._ARGTYPES.values() for name, argtypes in fam.items()}
+    protos = {name: _lib.PROTOTYPES[name][1] for name in ensemble_noise.SYMBOLS}
     assert list(protos) == SYMBOLS
     extra = "const float* scale, const uint64_t* seeds, int64_t row0, "
     for name, sib in sibling.items():

@@ -280,7 +280,7 @@ def test_symbols_are_exported_and_declared(L):
     for family, name, sib in zip(("lane", "mid"), SYMBOLS, SIBLINGS):
         assert hasattr(L, name), name
         f = ensemble.weighted_entry(L, family)
-        old = (ensemble._ARGTYPES if family == "lane" else ensemble._ARGTYPES_MID)[sib]
+        old = _lib.PROTOTYPES[sib][1]
         # the sibling's argument list with a pointer where `double inv_n` stands (argument 8)
         assert f.restype is C.c_int and len(f.argtypes) == len(old)
         assert old[8] is C.c_double and f.argtypes[8] is C.c_void_p

@@ -80,7 +80,7 @@ def test_statistics_of_the_grid():
 def _fill(L):
     f = L.nocf_noise_fill_f32
     f.restype = C.c_int
-    f.argtypes = noise._FILL_ARGTYPES
+    f.argtypes = _lib.PROTOTYPES["nocf_noise_fill_f32"][1]
     return f
 
 
