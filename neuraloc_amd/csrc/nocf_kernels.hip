@@ -1700,6 +1700,307 @@ static CallState& call_state() {
 #define g_prof_on (call_state().prof_on)
 static unsigned long long* g_stamp_buf = nullptr;     // diagnostic builds only (nocf_debug_set_stamp_buffer)
 
+// ---- variant tables and launchers of the six rollout kernel families ("Host dispatch").  A family's table is the one
+// place that spells its instantiations: per shape, rows of (key = the template arguments that vary, all int; the kernel as a typed pointer;
+// the name nocf_last_rollout_kernel reports).  Its launcher takes the filled argument structs and a key: row, dynamic LDS, NOCF_DEBUG line,
+// then launch_row.  The callers keep what differs between them: the argument checks, the argument structs and the cost-sum epilogue.
+template <class Row, size_t N, class Key>
+static const Row* find_variant(const Row (&rows)[N], const Key& key) {
+    for (const Row& r : rows) if (memcmp(&r.key, &key, sizeof(Key)) == 0) return &r;
+    return nullptr;
+}
+
+// what every launcher ends on: the HIP event pair of an open profile window (nocf_profile_begin) around the launch through the row's
+// typed pointer -- the compiler checks the argument list --, then the row's name into the call state
+template <class Row, class... Args>
+static int launch_row(const Row& row, dim3 grid, dim3 block, size_t ldsBytes, hipStream_t st, const Args&... args) {
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    if (g_prof_on) {
+        if (hipEventCreate(&ev0) || hipEventCreate(&ev1)) return (int)hipErrorUnknown;
+        (void)hipEventRecord(ev0, st);
+    }
+    hipLaunchKernelGGL(row.fn, grid, block, ldsBytes, st, args...);
+    const hipError_t e = hipGetLastError();
+    if (e) return (int)e;
+    if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
+    g_last_kernel = row.name;
+    g_last_errp = nullptr;
+    return 0;
+}
+
+#define LANE_SHAPES(X) X(16, 8) X(16, 16) X(16, 32) X(32, 8) X(32, 16) X(32, 32)      // (MP, DP): m and d + 1 padded up to an instantiated width
+
+// ---- lane forward (nocf_lane.inc)
+struct LaneFwdKey { int rec, one, dist, ens, hold; };       // REC, ONE, DIST, ENS, HOLD
+struct LaneFwdRow { LaneFwdKey key; void (*fn)(LaneArgs, DevProb, RollArgs, EnsArgs, EnsNoiseArgs, HoldArgs); const char* name; };
+
+template <int MP, int DP>
+static const LaneFwdRow* lane_fwd_variant(const LaneFwdKey& key) {
+#define NOCF_ROW(REC, ONE, DIST, ENS, HOLD, NAME) {{REC, ONE, DIST, ENS, HOLD}, rollout_lane_kernel<MP, DP, REC, ONE, DIST, ENS, HOLD>, NAME}
+    static const LaneFwdRow rows[] = {
+        NOCF_ROW(false, false, 0, false, false, "rollout_lane_kernel"),
+        NOCF_ROW(true, false, 0, false, false, "rollout_lane_kernel"),
+        NOCF_ROW(false, true, 0, false, false, "rollout_lane_kernel"),               // (one launch per call: NOCF_LANE_ONE)
+        NOCF_ROW(false, false, 1, false, false, "rollout_lane_kernel<dist>"),
+        NOCF_ROW(true, false, 1, false, false, "rollout_lane_kernel<dist>"),
+        NOCF_ROW(false, false, 2, false, false, "rollout_lane_kernel<noise>"),
+        NOCF_ROW(true, false, 2, false, false, "rollout_lane_kernel<noise>"),
+        NOCF_ROW(false, false, 3, false, false, "rollout_lane_kernel<noise-corr>"),
+        NOCF_ROW(true, false, 3, false, false, "rollout_lane_kernel<noise-corr>"),
+        NOCF_ROW(false, false, 0, false, true, "rollout_lane_kernel<hold>"),
+        NOCF_ROW(false, false, 1, false, true, "rollout_lane_kernel<hold,dist>"),
+        NOCF_ROW(false, false, 0, true, false, "rollout_lane_kernel<ens>"),
+        NOCF_ROW(true, false, 0, true, false, "rollout_lane_kernel<ens>"),
+        NOCF_ROW(false, false, 1, true, false, "rollout_lane_kernel<ens,disturbed>"),
+        NOCF_ROW(true, false, 1, true, false, "rollout_lane_kernel<ens,disturbed>"),
+        NOCF_ROW(false, false, 2, true, false, "rollout_lane_kernel<ens,noisy>"),
+        NOCF_ROW(true, false, 2, true, false, "rollout_lane_kernel<ens,noisy>"),
+    };
+#undef NOCF_ROW
+    return find_variant(rows, key);
+}
+
+static int launch_lane_fwd(const LaneArgs& la, const DevProb& pb, const RollArgs& ra, const EnsArgs& ea, const EnsNoiseArgs& nz, HoldArgs hd,
+                           const LaneFwdKey& key, int grid, hipStream_t st) {
+    const int MP = la.m <= 16 ? 16 : 32, DP = la.d + 1 <= 8 ? 8 : (la.d + 1 <= 16 ? 16 : 32);
+    const LaneFwdRow* row = nullptr;
+#define NOCF_PICK(MP_, DP_) if (MP == MP_ && DP == DP_) row = lane_fwd_variant<MP_, DP_>(key);
+    LANE_SHAPES(NOCF_PICK)
+#undef NOCF_PICK
+    if (!row) return NOCF_E_SHAPE;
+    const size_t ldsBytes = key.one ? (size_t)(256 * 7 * 8 + 16) : 0;      // (the last-workgroup reduction's scratch: only with a ticket)
+    return launch_row(*row, dim3(grid), dim3(256), ldsBytes, st, la, pb, ra, ea, nz, hd);
+}
+
+// ---- lane adjoint (nocf_lane_bwd.inc)
+struct LaneBwdKey { int states, ens, rw; };                 // STATES (1: state-only, 2: joint), ENS, RW
+struct LaneBwdRow { LaneBwdKey key; void (*fn)(LaneBwdArgs, DevProb, EnsArgs); const char* name; };
+
+template <int MP, int DP>
+static const LaneBwdRow* lane_bwd_variant(const LaneBwdKey& key) {
+#define NOCF_ROW(STATES, ENS, RW, NAME) {{STATES, ENS, RW}, rollout_lane_bwd_kernel<MP, DP, STATES, ENS, RW>, NAME}
+    static const LaneBwdRow rows[] = {
+        NOCF_ROW(0, false, false, "rollout_lane_bwd_kernel"),
+        NOCF_ROW(1, false, false, "rollout_lane_bwd_kernel<states>"),
+        NOCF_ROW(2, false, false, "rollout_lane_bwd_kernel<joint>"),
+        NOCF_ROW(0, false, true, "rollout_lane_bwd_kernel<weighted>"),
+        NOCF_ROW(0, true, false, "rollout_lane_bwd_kernel<ens>"),
+        NOCF_ROW(1, true, false, "rollout_lane_bwd_kernel<ens,states>"),
+        NOCF_ROW(2, true, false, "rollout_lane_bwd_kernel<ens,joint>"),
+        NOCF_ROW(0, true, true, "rollout_lane_bwd_kernel<ens,weighted>"),
+    };
+#undef NOCF_ROW
+    return find_variant(rows, key);
+}
+
+static int launch_lane_bwd(const LaneBwdArgs& la, const DevProb& pb, const EnsArgs& ea, const LaneBwdKey& key, int grid, hipStream_t st) {
+    const int MP = la.m <= 16 ? 16 : 32, DP = la.d + 1 <= 8 ? 8 : (la.d + 1 <= 16 ? 16 : 32);
+    const LaneBwdRow* row = nullptr;
+#define NOCF_PICK(MP_, DP_) if (MP == MP_ && DP == DP_) row = lane_bwd_variant<MP_, DP_>(key);
+    LANE_SHAPES(NOCF_PICK)
+#undef NOCF_PICK
+    if (!row) return NOCF_E_SHAPE;
+    if (env_int("NOCF_DEBUG", 0)) fprintf(stderr, "[nocf] lane adjoint kernel\n");
+    return launch_row(*row, dim3(grid), dim3(256), 0, st, la, pb, ea);
+}
+
+// ---- one-CU forward (nocf_mono.inc), on MONO_SHAPES
+struct MonoFwdKey { int rec, dist, ens, hold; };            // REC, DIST, ENS, HOLD
+struct MonoFwdRow { MonoFwdKey key; void (*fn)(const MonoPlan*, DevProb, float*, RollArgs, MonoEnsArgs, EnsNoiseArgs, HoldArgs); const char* name; };
+
+template <int KBM, int KBD>
+static const MonoFwdRow* mono_fwd_variant(const MonoFwdKey& key) {
+#define NOCF_ROW(REC, DIST, ENS, HOLD, NAME) {{REC, DIST, ENS, HOLD}, rollout_mono_kernel<KBM, KBD, REC, DIST, ENS, HOLD>, NAME}
+    static const MonoFwdRow rows[] = {
+        NOCF_ROW(false, 0, false, false, "rollout_mono_kernel"),
+        NOCF_ROW(true, 0, false, false, "rollout_mono_kernel"),
+        NOCF_ROW(false, 1, false, false, "rollout_mono_kernel<dist>"),
+        NOCF_ROW(true, 1, false, false, "rollout_mono_kernel<dist>"),
+        NOCF_ROW(false, 2, false, false, "rollout_mono_kernel<noise>"),
+        NOCF_ROW(true, 2, false, false, "rollout_mono_kernel<noise>"),
+        NOCF_ROW(false, 3, false, false, "rollout_mono_kernel<noise-corr>"),
+        NOCF_ROW(true, 3, false, false, "rollout_mono_kernel<noise-corr>"),
+        NOCF_ROW(false, 0, false, true, "rollout_mono_kernel<hold>"),
+        NOCF_ROW(false, 1, false, true, "rollout_mono_kernel<hold,dist>"),
+#ifndef NOCF_JIT_ONLY                                       // (a per-shape library carries no one-CU ensembles)
+        NOCF_ROW(false, 0, true, false, "rollout_mono_kernel<ens>"),
+        NOCF_ROW(true, 0, true, false, "rollout_mono_kernel<ens>"),
+        NOCF_ROW(false, 1, true, false, "rollout_mono_kernel<ens,disturbed>"),
+        NOCF_ROW(true, 1, true, false, "rollout_mono_kernel<ens,disturbed>"),
+        NOCF_ROW(false, 2, true, false, "rollout_mono_kernel<ens,noisy>"),
+        NOCF_ROW(true, 2, true, false, "rollout_mono_kernel<ens,noisy>"),
+#endif
+    };
+#undef NOCF_ROW
+    return find_variant(rows, key);
+}
+
+static int launch_mono_fwd(const MonoPlan& mpl, float* ws, const DevProb& pb, const RollArgs& ra, const MonoEnsArgs& en, const EnsNoiseArgs& nz,
+                           HoldArgs hd, const MonoFwdKey& key, unsigned grid, hipStream_t st) {
+    const MonoFwdRow* row = nullptr;
+#define NOCF_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) row = mono_fwd_variant<M_, D_>(key);
+    MONO_SHAPES(NOCF_PICK)
+#undef NOCF_PICK
+    if (!row) return NOCF_E_SHAPE;
+    const size_t ldsBytes = (size_t)mpl.pp.ldsFloats * 4;
+    const hipError_t e = set_lds(row->fn, ldsBytes);
+    if (e) return (int)e;
+    if (env_int("NOCF_DEBUG", 0)) fprintf(stderr, "[nocf] mono kernel: %d hidden / %d input k-blocks, LDS %zu B/workgroup\n", mpl.KBM, mpl.KBD, ldsBytes);
+    return launch_row(*row, dim3(grid), dim3(256), ldsBytes, st, reinterpret_cast<const MonoPlan*>(ws + mpl.pp.oPlan), pb, ws, ra, en, nz, hd);
+}
+
+#ifndef NOCF_JIT_ONLY
+// ---- one-CU adjoint (nocf_mono_bwd.inc), on the MONO_SHAPES of 4 hidden k-blocks and up (m <= 32 is the lane family's: nocf_mid_grad_rows)
+struct MonoBwdKey { int states, ens, rw; };                 // STATES (1: state-only, 2: joint), ENS, RW
+struct MonoBwdRow { MonoBwdKey key; void (*fn)(const MonoPlan*, DevProb, const float*, BwdArgs, MonoEnsArgs); const char* name; };
+
+template <int KBM, int KBD>
+static const MonoBwdRow* mono_bwd_variant(const MonoBwdKey& key) {
+    if constexpr (KBM < 4) return nullptr;
+    else {
+#define NOCF_ROW(STATES, ENS, RW, NAME) {{STATES, ENS, RW}, rollout_mono_bwd_kernel<KBM, KBD, STATES, ENS, RW>, NAME}
+        static const MonoBwdRow rows[] = {
+            NOCF_ROW(0, false, false, "rollout_mono_bwd_kernel"),
+            NOCF_ROW(1, false, false, "rollout_mono_bwd_kernel<states>"),
+            NOCF_ROW(2, false, false, "rollout_mono_bwd_kernel<joint>"),
+            NOCF_ROW(0, false, true, "rollout_mono_bwd_kernel<weighted>"),
+            NOCF_ROW(0, true, false, "rollout_mono_bwd_kernel<ens>"),
+            NOCF_ROW(1, true, false, "rollout_mono_bwd_kernel<ens,states>"),
+            NOCF_ROW(2, true, false, "rollout_mono_bwd_kernel<ens,joint>"),
+            NOCF_ROW(0, true, true, "rollout_mono_bwd_kernel<ens,weighted>"),
+        };
+#undef NOCF_ROW
+        return find_variant(rows, key);
+    }
+}
+
+static int launch_mono_bwd(const MonoPlan& mpl, const float* ws, const DevProb& pb, const BwdArgs& ba, const MonoEnsArgs& en, const MonoBwdKey& key,
+                           unsigned grid, hipStream_t st) {
+    const MonoBwdRow* row = nullptr;
+#define NOCF_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) row = mono_bwd_variant<M_, D_>(key);
+    MONO_SHAPES(NOCF_PICK)
+#undef NOCF_PICK
+    if (!row) return NOCF_E_SHAPE;
+    const size_t ldsBytes = (size_t)mpl.pp.ldsFloats * 4;
+    const hipError_t e = set_lds(row->fn, ldsBytes);
+    if (e) return (int)e;
+    if (env_int("NOCF_DEBUG", 0)) fprintf(stderr, "[nocf] mono adjoint kernel: %d hidden k-blocks, LDS %zu B/workgroup\n", mpl.KBM, ldsBytes);
+    return launch_row(*row, dim3(grid), dim3(256), ldsBytes, st, reinterpret_cast<const MonoPlan*>(ws + mpl.pp.oPlan), pb, ws, ba, en);
+}
+#endif
+
+// ---- per-tile forward (rollout_kernel): DIST, on the generic plan (S sub-tiles) or a shape-specialised one.  The FIXED_SHAPES and
+// FIXED_SHAPES_EXTRA shapes carry every DIST; the training-only shapes (TRAIN) carry the undisturbed one, for the recording forward
+struct TileFwdRow { int key; void (*fn)(const DevPlan*, DevProb, const float*, RollArgs); const char* name; };
+
+template <int S, class SP, bool TRAIN = false>
+static const TileFwdRow* tile_fwd_variant(int dist) {
+#define NOCF_ROW(DIST, TAIL) {DIST, rollout_kernel<S, SP, DIST>, SP::fixed ? "rollout_kernel<shape-specialised" TAIL : "rollout_kernel<generic" TAIL}
+    if constexpr (TRAIN) {
+        static const TileFwdRow rows[] = {NOCF_ROW(0, ">")};
+        return find_variant(rows, dist);
+    } else {
+        static const TileFwdRow rows[] = {NOCF_ROW(0, ">"), NOCF_ROW(1, ", dist>"), NOCF_ROW(2, ", noise>"), NOCF_ROW(3, ", noise-corr>")};
+        return find_variant(rows, dist);
+    }
+#undef NOCF_ROW
+}
+
+// the shape-specialised row of a run-time plan: taken only when the plan equals the compile-time one bit for bit, so the environment knobs
+// and odd shapes always get the generic kernel.  *fixed: 0 no such shape, 1 a FIXED_SHAPES / FIXED_SHAPES_EXTRA shape, 2 a training-only
+// one (those are the lane kernel's: they come here under NOCF_LANE=0 alone; anything but the undisturbed recording forward, `rec`, then
+// takes the generic instantiation)
+static const TileFwdRow* tile_fwd_fixed(const DevPlan& pl, int dist, bool rec, int* fixed) {
+    *fixed = 0;
+#define NOCF_PICK(D, M, NTH, R, NAG) \
+    if (plan_is<FixedPlan<D, M, NTH, R, NAG, 0>>(pl)) { *fixed = 1; return tile_fwd_variant<1, FixedPlan<D, M, NTH, R, NAG, 0>>(dist); }
+    FIXED_SHAPES(NOCF_PICK)
+    FIXED_SHAPES_EXTRA(NOCF_PICK)
+#undef NOCF_PICK
+#define NOCF_PICK(D, M, NTH, R, NAG) \
+    if (plan_is<FixedPlan<D, M, NTH, R, NAG, 0>>(pl)) { *fixed = 2; return rec ? tile_fwd_variant<1, FixedPlan<D, M, NTH, R, NAG, 0>, true>(dist) : nullptr; }
+    FIXED_SHAPES_TRAIN(NOCF_PICK)
+#undef NOCF_PICK
+    return nullptr;
+}
+
+static int launch_tile_fwd(const DevPlan& pl, int skCap, size_t ldsBytes, const DevPlan* plp, const DevProb& pb, const float* ws, const RollArgs& ra,
+                           int dist, int grid, hipStream_t st) {
+    int fixed = 0;
+    const TileFwdRow* row = (pl.T == 4 && env_int("NOCF_FIXED", 1)) ? tile_fwd_fixed(pl, dist, ra.sAll != nullptr, &fixed) : nullptr;
+    const bool specialised = row != nullptr;
+    if (!row) switch (pl.T / 4) {
+        case 1: row = tile_fwd_variant<1, DynPlan>(dist); break;
+        case 2: row = tile_fwd_variant<2, DynPlan>(dist); break;
+        default: row = tile_fwd_variant<4, DynPlan>(dist); break;
+    }
+    if (!row) return NOCF_E_SHAPE;
+    const hipError_t e = set_lds(row->fn, ldsBytes);
+    if (e) return (int)e;
+    if (env_int("NOCF_DEBUG", 0)) {
+        if (specialised) fprintf(stderr, "[nocf] shape-specialised rollout kernel\n");
+        else fprintf(stderr, "[nocf] generic rollout kernel: T %d, %d waves, SK1/SK6/SKm %d/%d/%d, cap %d, LDS %zu B/workgroup\n",
+                     pl.T, pl.nwaves, pl.SK1, pl.SK6, pl.SKm, skCap, ldsBytes);
+    }
+    return launch_row(*row, dim3(grid), dim3(pl.nwaves * 64), ldsBytes, st, plp, pb, ws, ra);
+}
+
+// ---- per-tile adjoint (nocf_bwd.inc): STATES (1: state-only, 2: joint), RW, on the generic plan or a shape-specialised one.  The
+// FIXED_SHAPES and FIXED_SHAPES_EXTRA shapes carry every variant (the shapes whose disturbed forward is specialised too); the training-only
+// shapes (TRAIN) are the lane kernel's and carry the plain adjoint
+struct TileBwdKey { int states, rw; };
+struct TileBwdRow { TileBwdKey key; void (*fn)(const DevPlan*, DevProb, const float*, BwdArgs); const char* name; };
+
+template <class SP, bool TRAIN = false>
+static const TileBwdRow* tile_bwd_variant(const TileBwdKey& key) {
+#define NOCF_ROW(STATES, RW, NAME) {{STATES, RW}, rollout_bwd_kernel<1, SP, STATES, RW>, NAME}
+    if constexpr (TRAIN) {
+        static const TileBwdRow rows[] = {NOCF_ROW(0, false, "rollout_bwd_kernel")};
+        return find_variant(rows, key);
+    } else {
+        static const TileBwdRow rows[] = {
+            NOCF_ROW(0, false, "rollout_bwd_kernel"),
+            NOCF_ROW(1, false, "rollout_bwd_kernel<states>"),
+            NOCF_ROW(2, false, "rollout_bwd_kernel<joint>"),
+            NOCF_ROW(0, true, "rollout_bwd_kernel<weighted>"),
+        };
+        return find_variant(rows, key);
+    }
+#undef NOCF_ROW
+}
+
+// the shape-specialised row of a run-time adjoint plan, and *fixed, under tile_fwd_fixed's rule
+static const TileBwdRow* tile_bwd_fixed(const DevPlan& pl, const TileBwdKey& key, int* fixed) {
+    *fixed = 0;
+#define NOCF_PICK(D, M, NTH, R, NAG) \
+    if (plan_is<FixedPlan<D, M, NTH, R, NAG, 1>>(pl)) { *fixed = 1; return tile_bwd_variant<FixedPlan<D, M, NTH, R, NAG, 1>>(key); }
+    FIXED_SHAPES(NOCF_PICK)
+    FIXED_SHAPES_EXTRA(NOCF_PICK)
+#undef NOCF_PICK
+#define NOCF_PICK(D, M, NTH, R, NAG) \
+    if (plan_is<FixedPlan<D, M, NTH, R, NAG, 1>>(pl)) { *fixed = 2; return tile_bwd_variant<FixedPlan<D, M, NTH, R, NAG, 1>, true>(key); }
+    FIXED_SHAPES_TRAIN(NOCF_PICK)
+#undef NOCF_PICK
+    return nullptr;
+}
+
+static int launch_tile_bwd(const DevPlan& pl, int skCap, const DevPlan* plp, const DevProb& pb, const float* ws, const BwdArgs& ba,
+                           const TileBwdKey& key, int grid, hipStream_t st) {
+    int fixed = 0;
+    const TileBwdRow* row = env_int("NOCF_FIXED", 1) ? tile_bwd_fixed(pl, key, &fixed) : nullptr;
+    const bool specialised = row != nullptr;
+    if (!row) row = tile_bwd_variant<DynPlan>(key);
+    if (!row) return NOCF_E_SHAPE;
+    const size_t ldsBytes = (size_t)pl.ldsFloats * 4;
+    const hipError_t e = set_lds(row->fn, ldsBytes);
+    if (e) return (int)e;
+    if (env_int("NOCF_DEBUG", 0))
+        fprintf(stderr, "[nocf] %s rollout adjoint kernel: T %d, %d waves, SK1/SK6/SKm %d/%d/%d, cap %d, LDS %zu B/workgroup, activations %s\n",
+                specialised ? "specialised" : "generic", pl.T, pl.nwaves, pl.SK1, pl.SK6, pl.SKm, skCap, ldsBytes,
+                ba.act ? "from the record" : "recomputed");
+    return launch_row(*row, dim3(grid), dim3(pl.nwaves * 64), ldsBytes, st, plp, pb, ws, ba);
+}
+
 extern "C" {
 
 int nocf_version(void) { return NOCF_VERSION; }
@@ -1728,15 +2029,7 @@ int nocf_debug_tile_plan(int32_t d, int32_t m, int32_t nTh, int32_t r, int32_t n
     if (rc) return rc;
     // 1: the plan of a FIXED_SHAPES instantiation (evaluation, record and adjoint); 2: of a training-only one (record and adjoint)
     int fixed = 0;
-#define NOCF_IS_FIXED(D, M, NTH, R, NAG) \
-    if (!fixed && (bwd ? plan_is<FixedPlan<D, M, NTH, R, NAG, 1>>(pl) : plan_is<FixedPlan<D, M, NTH, R, NAG, 0>>(pl))) fixed = 1;
-    FIXED_SHAPES(NOCF_IS_FIXED)
-    FIXED_SHAPES_EXTRA(NOCF_IS_FIXED)
-#undef NOCF_IS_FIXED
-#define NOCF_IS_FIXED(D, M, NTH, R, NAG) \
-    if (!fixed && (bwd ? plan_is<FixedPlan<D, M, NTH, R, NAG, 1>>(pl) : plan_is<FixedPlan<D, M, NTH, R, NAG, 0>>(pl))) fixed = 2;
-    FIXED_SHAPES_TRAIN(NOCF_IS_FIXED)
-#undef NOCF_IS_FIXED
+    if (bwd) (void)tile_bwd_fixed(pl, TileBwdKey{0, false}, &fixed); else (void)tile_fwd_fixed(pl, 0, false, &fixed);
     const int v[12] = {pl.T, pl.nwaves, pl.MB, pl.DB, pl.KQ1, pl.KQm, pl.SK1, pl.SK6, pl.SKm, cap, pl.ldsFloats, fixed};
     for (int i = 0; i < 12; ++i) out[i] = v[i];
     return 0;
@@ -1797,28 +2090,7 @@ static int bwd_small_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n, i
     la.t1 = (float)t1; la.a0 = alph[0]; la.a3 = alph[3]; la.a4 = alph[4]; la.a5 = alph[5]; la.inv_n = (float)inv_n;
     la.gpart = gpart; la.P_total = nocf_small_grad_floats(phi->d, phi->m); la.lam0 = lam0; la.lamW = (mode == 1 || mode == 2) ? lamW : nullptr;
     la.wrow = mode == 3 ? wrow : nullptr;
-    hipStream_t st = (hipStream_t)stream;
-    const int grid = (int)((n + 3) / 4);
-    const int MPsel = phi->m <= 16 ? 16 : 32;
-    const int DPsel = phi->d + 1 <= 8 ? 8 : (phi->d + 1 <= 16 ? 16 : 32);
-    if (env_int("NOCF_DEBUG", 0)) fprintf(stderr, "[nocf] lane adjoint kernel\n");
-#define NOCF_LANEB_LAUNCH(MPV, DPV) do { if (mode == 1) hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV, 1>), dim3(grid), dim3(256), 0, st, la, pb, EnsArgs{}); \
-                                          else if (mode == 2) hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV, 2>), dim3(grid), dim3(256), 0, st, la, pb, EnsArgs{}); \
-                                          else if (mode == 3) hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV, 0, false, true>), dim3(grid), dim3(256), 0, st, la, pb, EnsArgs{}); \
-                                          else hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV>), dim3(grid), dim3(256), 0, st, la, pb, EnsArgs{}); } while (0)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (g_prof_on) {
-        if (hipEventCreate(&ev0) || hipEventCreate(&ev1)) return (int)hipErrorUnknown;
-        (void)hipEventRecord(ev0, st);
-    }
-    if (MPsel == 16) { if (DPsel == 8) { NOCF_LANEB_LAUNCH(16, 8); } else if (DPsel == 16) { NOCF_LANEB_LAUNCH(16, 16); } else { NOCF_LANEB_LAUNCH(16, 32); } }
-    else             { if (DPsel == 8) { NOCF_LANEB_LAUNCH(32, 8); } else if (DPsel == 16) { NOCF_LANEB_LAUNCH(32, 16); } else { NOCF_LANEB_LAUNCH(32, 32); } }
-#undef NOCF_LANEB_LAUNCH
-    if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
-    g_last_kernel = mode == 1 ? "rollout_lane_bwd_kernel<states>" : (mode == 2 ? "rollout_lane_bwd_kernel<joint>" :
-                    (mode == 3 ? "rollout_lane_bwd_kernel<weighted>" : "rollout_lane_bwd_kernel"));
-    g_last_errp = nullptr;
-    return (int)hipGetLastError();
+    return launch_lane_bwd(la, pb, EnsArgs{}, LaneBwdKey{mode == 1 || mode == 2 ? mode : 0, false, mode == 3}, (int)((n + 3) / 4), (hipStream_t)stream);
 }
 
 int nocf_rollout_bwd_small_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t nt, int32_t stepper, double t1,
@@ -1895,31 +2167,12 @@ static int rollout_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, const
     const EnsArgs ea{(unsigned)n, (long)x_member_stride, alph};
     const EnsNoiseArgs nz{noise ? noise->scale : nullptr, noise ? reinterpret_cast<const unsigned long long*>(noise->seeds) : nullptr,
                           dist ? (long)dist->stride : 0l};
-    const int grid = (int)((rows + 3) / 4);
-    const int MPsel = phi->m <= 16 ? 16 : 32;
-    const int DPsel = phi->d + 1 <= 8 ? 8 : (phi->d + 1 <= 16 ? 16 : 32);
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (g_prof_on) {
-        if (hipEventCreate(&ev0) || hipEventCreate(&ev1)) return (int)hipErrorUnknown;
-        (void)hipEventRecord(ev0, st);
-    }
-#define NOCF_LANE_ENS_LAUNCH(MPV, DPV) do { if (dist && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 1, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz, HoldArgs{}); \
-                                             else if (dist) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 1, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz, HoldArgs{}); \
-                                             else if (noise && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 2, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz, HoldArgs{}); \
-                                             else if (noise) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 2, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz, HoldArgs{}); \
-                                             else if (s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 0, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz, HoldArgs{}); \
-                                             else hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 0, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, ea, nz, HoldArgs{}); } while (0)
-    if (MPsel == 16) { if (DPsel == 8) { NOCF_LANE_ENS_LAUNCH(16, 8); } else if (DPsel == 16) { NOCF_LANE_ENS_LAUNCH(16, 16); } else { NOCF_LANE_ENS_LAUNCH(16, 32); } }
-    else             { if (DPsel == 8) { NOCF_LANE_ENS_LAUNCH(32, 8); } else if (DPsel == 16) { NOCF_LANE_ENS_LAUNCH(32, 16); } else { NOCF_LANE_ENS_LAUNCH(32, 32); } }
-#undef NOCF_LANE_ENS_LAUNCH
-    hipError_t e = hipGetLastError();
-    if (e) return (int)e;
-    g_last_kernel = dist ? "rollout_lane_kernel<ens,disturbed>" : noise ? "rollout_lane_kernel<ens,noisy>" : "rollout_lane_kernel<ens>";
-    g_last_errp = nullptr;
-    if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
+    const int lrc = launch_lane_fwd(la, pb, ra, ea, nz, HoldArgs{}, LaneFwdKey{s_all != nullptr, false, dist ? 1 : noise ? 2 : 0, true, false},
+                                    (int)((rows + 3) / 4), st);
+    if (lrc) return lrc;
     if (cost_sums) {
         hipLaunchKernelGGL(cost_sum_ens_kernel, dim3(members), dim3(256), 0, st, persample, (long)n, cost_sums, cost_means, alph);
-        e = hipGetLastError();
+        const hipError_t e = hipGetLastError();
         if (e) return (int)e;
     }
     return 0;
@@ -2016,27 +2269,8 @@ static int bwd_small_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, int
     la.t1 = (float)t1; la.inv_n = (float)inv_n;
     la.gpart = gpart; la.P_total = nocf_small_grad_floats(phi->d, phi->m); la.lam0 = lam0; la.lamW = mode != 0 ? lamW : nullptr; la.wrow = weighted ? wrow : nullptr;
     const EnsArgs ea{(unsigned)n, 0l, alph};
-    hipStream_t st = (hipStream_t)stream;
-    const int grid = (int)((rows + 3) / 4);
-    const int MPsel = phi->m <= 16 ? 16 : 32;
-    const int DPsel = phi->d + 1 <= 8 ? 8 : (phi->d + 1 <= 16 ? 16 : 32);
-#define NOCF_LANEB_ENS_LAUNCH(MPV, DPV) do { if (mode == 2) hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV, 2, true>), dim3(grid), dim3(256), 0, st, la, pb, ea); \
-                                              else if (mode == 1) hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV, 1, true>), dim3(grid), dim3(256), 0, st, la, pb, ea); \
-                                              else if (weighted) hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV, 0, true, true>), dim3(grid), dim3(256), 0, st, la, pb, ea); \
-                                              else hipLaunchKernelGGL((rollout_lane_bwd_kernel<MPV, DPV, 0, true>), dim3(grid), dim3(256), 0, st, la, pb, ea); } while (0)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (g_prof_on) {
-        if (hipEventCreate(&ev0) || hipEventCreate(&ev1)) return (int)hipErrorUnknown;
-        (void)hipEventRecord(ev0, st);
-    }
-    if (MPsel == 16) { if (DPsel == 8) { NOCF_LANEB_ENS_LAUNCH(16, 8); } else if (DPsel == 16) { NOCF_LANEB_ENS_LAUNCH(16, 16); } else { NOCF_LANEB_ENS_LAUNCH(16, 32); } }
-    else             { if (DPsel == 8) { NOCF_LANEB_ENS_LAUNCH(32, 8); } else if (DPsel == 16) { NOCF_LANEB_ENS_LAUNCH(32, 16); } else { NOCF_LANEB_ENS_LAUNCH(32, 32); } }
-#undef NOCF_LANEB_ENS_LAUNCH
-    if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
-    g_last_kernel = mode == 2 ? "rollout_lane_bwd_kernel<ens,joint>" : mode == 1 ? "rollout_lane_bwd_kernel<ens,states>" :
-                    (weighted ? "rollout_lane_bwd_kernel<ens,weighted>" : "rollout_lane_bwd_kernel<ens>");
-    g_last_errp = nullptr;
-    return (int)hipGetLastError();
+    return launch_lane_bwd(la, pb, ea, LaneBwdKey{mode == 1 || mode == 2 ? mode : 0, true, mode != 1 && mode != 2 && weighted}, (int)((rows + 3) / 4),
+                           (hipStream_t)stream);
 }
 
 int nocf_rollout_bwd_small_ensemble_f32(const NocfPhi* phi, const NocfProb* prob, int64_t n, int32_t members, int32_t nt, int32_t stepper, double t1,
@@ -2269,9 +2503,12 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
     ra.dist = distW;                              // (disturbed rollouts: lane, then one-CU, then per-tile; never the split-role kernel)
     ra.nzScale = noise ? noise->scale : nullptr; ra.nzSeed = noise ? noise->seed : 0ull; ra.nzRow0 = noise ? (long)noise->row0 : 0l;
     ra.nzScale1 = noise ? noise->scale1 : nullptr; ra.nzRho = noise ? noise->rho : nullptr;
-    hipError_t e;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     const unsigned* errp = nullptr;
+    // the epilogue of every family but the segments: the 8 cost sums (and the means) of the per-sample table, NaN under a set error word
+    auto sum_costs = [&]() {
+        hipLaunchKernelGGL(cost_sum_kernel, dim3(1), dim3(256), 0, st, persample, (long)n, cost_sums, errp, mean_args);
+        return (int)hipGetLastError();
+    };
     if (seg) {                                    // segments run on the one-CU kernel only: decided before anything is enqueued or reset
         MonoPlan probe;
         if (env_int("NOCF_MONO", 1) == 0 || make_mono_plan(pl, pb.nAgents, &probe) != 0 || workspace_bytes < mono_ws_bytes(probe))
@@ -2298,43 +2535,17 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
         unsigned* ticket = (cost_sums && !s_all && !dist && !hold && env_int("NOCF_LANE_ONE", 0) != 0) ? lane_ticket(st) : nullptr;
         la.sums = ticket ? cost_sums : nullptr; la.ticket = ticket;
         la.means = mean_args.means; la.a0 = mean_args.a0; la.a3 = mean_args.a3; la.a4 = mean_args.a4; la.a5 = mean_args.a5;
-        const int grid = (int)((n + 3) / 4);
-        const int MPsel = phi->m <= 16 ? 16 : 32;
-        const int DPsel = phi->d + 1 <= 8 ? 8 : (phi->d + 1 <= 16 ? 16 : 32);
-        if (g_prof_on) {
-            if (hipEventCreate(&ev0) || hipEventCreate(&ev1)) return (int)hipErrorUnknown;
-            (void)hipEventRecord(ev0, st);
-        }
-        const size_t laneLds = ticket ? (size_t)(256 * 7 * 8 + 16) : 0;      // (the last-workgroup reduction's scratch: only with a ticket)
-#define NOCF_LANE_LAUNCH(MPV, DPV) do { if (hold && dist) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 1, false, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}, HoldArgs{hold}); \
-                                         else if (hold) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 0, false, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}, HoldArgs{hold}); \
-                                         else if (dmode == 3 && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 3>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}, HoldArgs{}); \
-                                         else if (dmode == 3) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 3>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}, HoldArgs{}); \
-                                         else if (dmode == 2 && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 2>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}, HoldArgs{}); \
-                                         else if (dmode == 2) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 2>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}, HoldArgs{}); \
-                                         else if (dist && s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true, false, 1>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}, HoldArgs{}); \
-                                         else if (dist) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, false, 1>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}, HoldArgs{}); \
-                                         else if (s_all) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, true>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}, HoldArgs{}); \
-                                         else if (ticket) hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false, true>), dim3(grid), dim3(256), laneLds, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}, HoldArgs{}); \
-                                         else hipLaunchKernelGGL((rollout_lane_kernel<MPV, DPV, false>), dim3(grid), dim3(256), 0, st, la, pb, ra, EnsArgs{}, EnsNoiseArgs{}, HoldArgs{}); } while (0)
-        if (MPsel == 16) { if (DPsel == 8) { NOCF_LANE_LAUNCH(16, 8); } else if (DPsel == 16) { NOCF_LANE_LAUNCH(16, 16); } else { NOCF_LANE_LAUNCH(16, 32); } }
-        else             { if (DPsel == 8) { NOCF_LANE_LAUNCH(32, 8); } else if (DPsel == 16) { NOCF_LANE_LAUNCH(32, 16); } else { NOCF_LANE_LAUNCH(32, 32); } }
-#undef NOCF_LANE_LAUNCH
-        e = hipGetLastError();
-        if (e) return (int)e;
-        g_last_kernel = hold ? (dist ? "rollout_lane_kernel<hold,dist>" : "rollout_lane_kernel<hold>") : dmode == 3 ? "rollout_lane_kernel<noise-corr>" : dmode == 2 ? "rollout_lane_kernel<noise>" : dist ? "rollout_lane_kernel<dist>" : "rollout_lane_kernel";
-        if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
-        if (cost_sums && !ticket) {
-            hipLaunchKernelGGL(cost_sum_kernel, dim3(1), dim3(256), 0, st, persample, (long)n, cost_sums, errp, mean_args);
-            e = hipGetLastError();
-            if (e) return (int)e;
-        }
-        return 0;
+        // (a held call records nothing, takes no ticket and W from memory at most: decided above)
+        rc = launch_lane_fwd(la, pb, ra, EnsArgs{}, EnsNoiseArgs{}, HoldArgs{hold}, LaneFwdKey{s_all != nullptr, ticket != nullptr, dmode, false, hold != 0},
+                             (int)((n + 3) / 4), st);
+        if (rc) return rc;
+        return cost_sums && !ticket ? sum_costs() : 0;
     }
 #ifndef NOCF_JIT_ONLY
     // split-role weight-stationary kernel (nocf_duo.hip): wide two-layer networks (m = 512) on point-agent problems, any batch
     // size (chunks of 2048 rows), evaluation and the recording forward of training
     if (env_int("NOCF_DUO", 1) != 0 && !seg && !dist && !hold) {
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;          // (created here, recorded by duo_launch)
         if (g_prof_on) {
             if (hipEventCreate(&ev0) || hipEventCreate(&ev1)) return (int)hipErrorUnknown;
         }
@@ -2348,9 +2559,8 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
             g_last_errp = errp;
             if (g_prof_on) g_prof_events.emplace_back(ev0, ev1);
             if (cost_sums) {
-                hipLaunchKernelGGL(cost_sum_kernel, dim3(1), dim3(256), 0, st, persample, (long)n, cost_sums, errp, mean_args);
-                e = hipGetLastError();
-                if (e) return (int)e;
+                rc = sum_costs();
+                if (rc) return rc;
             }
             // a timed-out exchange: every other output the caller asked for becomes NaN too (one tiny launch each; they return at once
             // when the error word is clear)
@@ -2359,7 +2569,7 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
             if (ctrlFull) hipLaunchKernelGGL(poison_kernel, dim3(1024), dim3(256), 0, st, ctrlFull, (long)(nt + 1) * n * ra.cdim, errp);
             return 0;
         }
-        if (g_prof_on) { (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1); ev0 = ev1 = nullptr; }
+        if (g_prof_on) { (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1); }
         if (rc != 1) return rc;
     }
 #endif
@@ -2375,132 +2585,31 @@ static int rollout_impl(const NocfPhi* phi, const NocfProb* prob, const float* x
         mpl.pp.cb = phi->cb;
         DevPhi P{phi->K0, phi->b0, phi->K, phi->b, phi->w, phi->A, phi->cw, phi->cb_dev};
         hipLaunchKernelGGL(mono_pack_kernel, dim3(64), dim3(256), 0, st, mpl, P, ws);
-        const size_t ldsBytes = (size_t)mpl.pp.ldsFloats * 4;
-        const void* fk = nullptr;
-#define NOCF_MONO_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) fk = hold ? (dist ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 1, false, true>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 0, false, true>)) : dmode == 3 ? (s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, 3>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 3>)) : dmode == 2 ? (s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, 2>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 2>)) : dist ? (s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, 1>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 1>)) : s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true>) : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false>);
-        MONO_SHAPES(NOCF_MONO_PICK)
-#undef NOCF_MONO_PICK
-        e = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes); if (e) return (int)e;
-        if (env_int("NOCF_DEBUG", 0)) fprintf(stderr, "[nocf] mono kernel: %d hidden / %d input k-blocks, LDS %zu B/workgroup\n", mpl.KBM, mpl.KBD, ldsBytes);
-        if (g_prof_on) {
-            if (hipEventCreate(&ev0) || hipEventCreate(&ev1)) return (int)hipErrorUnknown;
-            (void)hipEventRecord(ev0, st);
-        }
-        const MonoPlan* mpp = reinterpret_cast<const MonoPlan*>(ws + mpl.pp.oPlan);
         // activation record: the one-CU kernel writes it too, for the widths nocf_activation_record_floats sizes a record for
         const bool mono_rec = act && s_all && !tapeSc && (phi->m % 16) == 0 && phi->m > 32;
         if (mono_rec) { ra.act = act; ra.actRows = (long)nt * ((stepper == NOCF_RK4) ? 4 : 1) * n; }
         MonoEnsArgs noEns;                            // (read by the ENS instantiations only: nocf_rollout_mid_ensemble_f32)
         memset(&noEns, 0, sizeof(noEns));
-        EnsNoiseArgs noNz{nullptr, nullptr};          // (read by the noisy ENS instantiations only: nocf_rollout_noisy_mid_ensemble_f32)
-        HoldArgs hda{hold};                           // (read by the HOLD instantiations only: nocf_rollout_held_f32)
-        void* args[] = {(void*)&mpp, (void*)&pb, (void*)&ws, (void*)&ra, (void*)&noEns, (void*)&noNz, (void*)&hda};
-        e = hipLaunchKernel(fk, dim3((int)((n + 15) / 16)), dim3(256), args, ldsBytes, st); if (e) return (int)e;
-        ra.act = nullptr; ra.actRows = 0;
+        // (EnsNoiseArgs: read by the noisy ENS instantiations only; a held call records nothing and takes W from memory at most: decided above)
+        rc = launch_mono_fwd(mpl, ws, pb, ra, noEns, EnsNoiseArgs{}, HoldArgs{hold}, MonoFwdKey{s_all != nullptr, dmode, false, hold != 0},
+                             (unsigned)((n + 15) / 16), st);
+        if (rc) return rc;
         if (mono_rec && act_recorded) *act_recorded = 1;
-        g_last_kernel = hold ? (dist ? "rollout_mono_kernel<hold,dist>" : "rollout_mono_kernel<hold>") : dmode == 3 ? "rollout_mono_kernel<noise-corr>" : dmode == 2 ? "rollout_mono_kernel<noise>" : dist ? "rollout_mono_kernel<dist>" : "rollout_mono_kernel";
-        e = hipGetLastError();
-        if (e) return (int)e;
-        if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
         if (cost_sums && seg) {                       // one row of 8 sums per segment
             for (int k = 0; k < seg->n; ++k) {
                 const long r0 = (long)k * seg->rows, rn = std::min<long>(seg->rows, (long)n - r0);
                 if (rn <= 0) break;
                 hipLaunchKernelGGL(cost_sum_kernel, dim3(1), dim3(256), 0, st, persample + r0 * 7, rn, cost_sums + 8 * k, errp);
             }
-            e = hipGetLastError();
-            if (e) return (int)e;
-        } else if (cost_sums) {
-            hipLaunchKernelGGL(cost_sum_kernel, dim3(1), dim3(256), 0, st, persample, (long)n, cost_sums, errp, mean_args);
-            e = hipGetLastError();
-            if (e) return (int)e;
+            return (int)hipGetLastError();
         }
-        return 0;
+        return cost_sums ? sum_costs() : 0;
     }
     if (hold) return NOCF_E_SHAPE;                    // (held: decided above; not reached)
     if (seg) return NOCF_E_SHAPE;                     // (segments: no one-CU instantiation for this shape -- the caller launches them one by one)
-    {
-        const size_t ldsBytes = (size_t)pl.ldsFloats * 4 + corrLds;
-        const int grid = (int)((n + pl.T - 1) / pl.T);
-        const int block = pl.nwaves * 64;
-        if (g_prof_on) {
-            if (hipEventCreate(&ev0) || hipEventCreate(&ev1)) return (int)hipErrorUnknown;
-            (void)hipEventRecord(ev0, st);
-        }
-        bool launched = false;
-        if (pl.T == 4 && env_int("NOCF_FIXED", 1)) {
-            // shape-specialised instantiations (FIXED_SHAPES): taken only when the run-time plan equals the
-            // compile-time one bit for bit, so the environment knobs and odd shapes always get the generic kernel
-            const void* fk = nullptr;
-#define NOCF_TRY_FIXED(D, M, NTH, R, NAG) \
-            if (!fk && plan_is<FixedPlan<D, M, NTH, R, NAG, 0>>(pl)) fk = dmode == 3 ? reinterpret_cast<const void*>(rollout_kernel<1, FixedPlan<D, M, NTH, R, NAG, 0>, 3>) \
-                                                                   : dmode == 2 ? reinterpret_cast<const void*>(rollout_kernel<1, FixedPlan<D, M, NTH, R, NAG, 0>, 2>) \
-                                                                   : dist ? reinterpret_cast<const void*>(rollout_kernel<1, FixedPlan<D, M, NTH, R, NAG, 0>, 1>) \
-                                                                              : reinterpret_cast<const void*>(rollout_kernel<1, FixedPlan<D, M, NTH, R, NAG, 0>>);
-            FIXED_SHAPES(NOCF_TRY_FIXED)
-            FIXED_SHAPES_EXTRA(NOCF_TRY_FIXED)
-#undef NOCF_TRY_FIXED
-#define NOCF_TRY_FIXED(D, M, NTH, R, NAG) \
-            if (!fk && plan_is<FixedPlan<D, M, NTH, R, NAG, 0>>(pl)) fk = reinterpret_cast<const void*>(rollout_kernel<1, FixedPlan<D, M, NTH, R, NAG, 0>>);
-            // (the training-only shapes are the lane kernel's: they come here under NOCF_LANE=0 alone, and a disturbed call then takes the
-            // generic instantiation, the only one of theirs that reads W)
-            if (s_all && !dist) { FIXED_SHAPES_TRAIN(NOCF_TRY_FIXED) }
-#undef NOCF_TRY_FIXED
-            if (fk) {
-                e = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes); if (e) return (int)e;
-                void* args[] = {(void*)&plp, (void*)&pb, (void*)&ws, (void*)&ra};
-                e = hipLaunchKernel(fk, dim3(grid), dim3(block), args, ldsBytes, st); if (e) return (int)e;
-                launched = true;
-                g_last_kernel = dmode == 3 ? "rollout_kernel<shape-specialised, noise-corr>" : dmode == 2 ? "rollout_kernel<shape-specialised, noise>" : dist ? "rollout_kernel<shape-specialised, dist>" : "rollout_kernel<shape-specialised>";
-                if (env_int("NOCF_DEBUG", 0)) fprintf(stderr, "[nocf] shape-specialised rollout kernel\n");
-            }
-        }
-        if (!launched) g_last_kernel = dmode == 3 ? "rollout_kernel<generic, noise-corr>" : dmode == 2 ? "rollout_kernel<generic, noise>" : dist ? "rollout_kernel<generic, dist>" : "rollout_kernel<generic>";
-        if (!launched && env_int("NOCF_DEBUG", 0))
-            fprintf(stderr, "[nocf] generic rollout kernel: T %d, %d waves, SK1/SK6/SKm %d/%d/%d, cap %d, LDS %zu B/workgroup\n",
-                    pl.T, pl.nwaves, pl.SK1, pl.SK6, pl.SKm, skCap, ldsBytes);
-        if (!launched && dmode == 3) switch (pl.T / 4) {
-            case 1: e = set_lds(rollout_kernel<1, DynPlan, 3>, ldsBytes); if (e) return (int)e;
-                    hipLaunchKernelGGL((rollout_kernel<1, DynPlan, 3>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
-            case 2: e = set_lds(rollout_kernel<2, DynPlan, 3>, ldsBytes); if (e) return (int)e;
-                    hipLaunchKernelGGL((rollout_kernel<2, DynPlan, 3>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
-            default: e = set_lds(rollout_kernel<4, DynPlan, 3>, ldsBytes); if (e) return (int)e;
-                    hipLaunchKernelGGL((rollout_kernel<4, DynPlan, 3>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
-        }
-        else if (!launched && dmode == 2) switch (pl.T / 4) {
-            case 1: e = set_lds(rollout_kernel<1, DynPlan, 2>, ldsBytes); if (e) return (int)e;
-                    hipLaunchKernelGGL((rollout_kernel<1, DynPlan, 2>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
-            case 2: e = set_lds(rollout_kernel<2, DynPlan, 2>, ldsBytes); if (e) return (int)e;
-                    hipLaunchKernelGGL((rollout_kernel<2, DynPlan, 2>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
-            default: e = set_lds(rollout_kernel<4, DynPlan, 2>, ldsBytes); if (e) return (int)e;
-                    hipLaunchKernelGGL((rollout_kernel<4, DynPlan, 2>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
-        }
-        else if (!launched && dist) switch (pl.T / 4) {
-            case 1: e = set_lds(rollout_kernel<1, DynPlan, 1>, ldsBytes); if (e) return (int)e;
-                    hipLaunchKernelGGL((rollout_kernel<1, DynPlan, 1>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
-            case 2: e = set_lds(rollout_kernel<2, DynPlan, 1>, ldsBytes); if (e) return (int)e;
-                    hipLaunchKernelGGL((rollout_kernel<2, DynPlan, 1>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
-            default: e = set_lds(rollout_kernel<4, DynPlan, 1>, ldsBytes); if (e) return (int)e;
-                    hipLaunchKernelGGL((rollout_kernel<4, DynPlan, 1>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
-        }
-        else if (!launched) switch (pl.T / 4) {
-            case 1: e = set_lds(rollout_kernel<1, DynPlan>, ldsBytes); if (e) return (int)e;
-                    hipLaunchKernelGGL((rollout_kernel<1, DynPlan>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
-            case 2: e = set_lds(rollout_kernel<2, DynPlan>, ldsBytes); if (e) return (int)e;
-                    hipLaunchKernelGGL((rollout_kernel<2, DynPlan>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
-            default: e = set_lds(rollout_kernel<4, DynPlan>, ldsBytes); if (e) return (int)e;
-                    hipLaunchKernelGGL((rollout_kernel<4, DynPlan>), dim3(grid), dim3(block), ldsBytes, st, plp, pb, ws, ra); break;
-        }
-    }
-    e = hipGetLastError();
-    if (e) return (int)e;
-    if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
-    if (cost_sums) {
-        hipLaunchKernelGGL(cost_sum_kernel, dim3(1), dim3(256), 0, st, persample, (long)n, cost_sums, errp, mean_args);
-        e = hipGetLastError();
-        if (e) return (int)e;
-    }
-    return 0;
+    rc = launch_tile_fwd(pl, skCap, (size_t)pl.ldsFloats * 4 + corrLds, plp, pb, ws, ra, dmode, (int)((n + pl.T - 1) / pl.T), st);
+    if (rc) return rc;
+    return cost_sums ? sum_costs() : 0;
 }
 
 int nocf_rollout_f32(const NocfPhi* phi, const NocfProb* prob, const float* x, int64_t n,
@@ -2920,61 +3029,7 @@ static int rollout_bwd_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n,
     ba.act = (act_rec && phi->nTh == 2) ? act_rec : nullptr; ba.actRows = (long)nt * ba.nstage * n;
     ba.lstride = ((long)nt * ba.nstage + 2) * n * phi->m;
     ba.gpart = nullptr; ba.gstride = 0;
-    const size_t ldsBytes = (size_t)pl.ldsFloats * 4;
-    const void* fk = nullptr;
-    if (states && env_int("NOCF_FIXED", 1)) {
-        // (the shapes whose disturbed forward is specialised too; the training-only shapes are the lane kernel's and take the generic one here)
-#define NOCF_TRY_FIXED(D, M, NTH, R, NAG) \
-        if (!fk && plan_is<FixedPlan<D, M, NTH, R, NAG, 1>>(pl)) fk = reinterpret_cast<const void*>(rollout_bwd_kernel<1, FixedPlan<D, M, NTH, R, NAG, 1>, true>);
-        FIXED_SHAPES(NOCF_TRY_FIXED)
-        FIXED_SHAPES_EXTRA(NOCF_TRY_FIXED)
-#undef NOCF_TRY_FIXED
-    } else if (mode == 2 && env_int("NOCF_FIXED", 1)) {
-#define NOCF_TRY_FIXED(D, M, NTH, R, NAG) \
-        if (!fk && plan_is<FixedPlan<D, M, NTH, R, NAG, 1>>(pl)) fk = reinterpret_cast<const void*>(rollout_bwd_kernel<1, FixedPlan<D, M, NTH, R, NAG, 1>, 2>);
-        FIXED_SHAPES(NOCF_TRY_FIXED)
-        FIXED_SHAPES_EXTRA(NOCF_TRY_FIXED)
-#undef NOCF_TRY_FIXED
-    } else if (mode == 3 && env_int("NOCF_FIXED", 1)) {
-        // (the shapes of the joint one: a weighted call follows a disturbed or noisy recording forward)
-#define NOCF_TRY_FIXED(D, M, NTH, R, NAG) \
-        if (!fk && plan_is<FixedPlan<D, M, NTH, R, NAG, 1>>(pl)) fk = reinterpret_cast<const void*>(rollout_bwd_kernel<1, FixedPlan<D, M, NTH, R, NAG, 1>, 0, true>);
-        FIXED_SHAPES(NOCF_TRY_FIXED)
-        FIXED_SHAPES_EXTRA(NOCF_TRY_FIXED)
-#undef NOCF_TRY_FIXED
-    } else if (env_int("NOCF_FIXED", 1)) {
-#define NOCF_TRY_FIXED(D, M, NTH, R, NAG) \
-        if (!fk && plan_is<FixedPlan<D, M, NTH, R, NAG, 1>>(pl)) fk = reinterpret_cast<const void*>(rollout_bwd_kernel<1, FixedPlan<D, M, NTH, R, NAG, 1>>);
-        FIXED_SHAPES(NOCF_TRY_FIXED)
-        FIXED_SHAPES_EXTRA(NOCF_TRY_FIXED)
-        FIXED_SHAPES_TRAIN(NOCF_TRY_FIXED)
-#undef NOCF_TRY_FIXED
-    }
-    const bool specialised = fk != nullptr;
-    if (!fk) fk = states ? reinterpret_cast<const void*>(rollout_bwd_kernel<1, DynPlan, true>)
-                  : (mode == 2 ? reinterpret_cast<const void*>(rollout_bwd_kernel<1, DynPlan, 2>)
-                  : (mode == 3 ? reinterpret_cast<const void*>(rollout_bwd_kernel<1, DynPlan, 0, true>) : reinterpret_cast<const void*>(rollout_bwd_kernel<1, DynPlan>)));
-    if (env_int("NOCF_DEBUG", 0))
-        fprintf(stderr, "[nocf] %s rollout adjoint kernel: T %d, %d waves, SK1/SK6/SKm %d/%d/%d, cap %d, LDS %zu B/workgroup, activations %s\n",
-                specialised ? "specialised" : "generic", pl.T, pl.nwaves, pl.SK1, pl.SK6, pl.SKm, skCap, ldsBytes,
-                ba.act ? "from the record" : "recomputed");
-    hipError_t e = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes);
-    if (e) return (int)e;
-    {
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        if (g_prof_on) {
-            if (hipEventCreate(&ev0) || hipEventCreate(&ev1)) return (int)hipErrorUnknown;
-            (void)hipEventRecord(ev0, st);
-        }
-        void* args[] = {(void*)&plp, (void*)&pb, (void*)&ws, (void*)&ba};
-        e = hipLaunchKernel(fk, dim3((int)((n + 3) / 4)), dim3(pl.nwaves * 64), args, ldsBytes, st);
-        if (e) return (int)e;
-        if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
-        g_last_kernel = states ? "rollout_bwd_kernel<states>" : (mode == 2 ? "rollout_bwd_kernel<joint>" :
-                        (mode == 3 ? "rollout_bwd_kernel<weighted>" : "rollout_bwd_kernel"));
-        g_last_errp = nullptr;
-    }
-    return (int)hipGetLastError();
+    return launch_tile_bwd(pl, skCap, plp, pb, ws, ba, TileBwdKey{mode == 1 || mode == 2 ? mode : 0, mode == 3}, (int)((n + 3) / 4), st);
 }
 
 // ---- the adjoint on the one-CU weight-stationary layout (nocf_mono_bwd.inc): medium two-layer networks, every problem class
@@ -3041,35 +3096,9 @@ static int bwd_mid_impl(const NocfPhi* phi, const NocfProb* prob, int64_t n, int
     ba.lam0 = lam0; ba.lamW = (mode == 1 || mode == 2) ? lamW : nullptr; ba.wrow = mode == 3 ? wrow : nullptr;
     ba.gpart = gpart; ba.gstride = nocf_small_grad_floats(phi->d, phi->m);
     ba.act = (act_rec && (phi->m % 16) == 0) ? act_rec : nullptr; ba.actRows = (long)nt * ba.nstage * n;
-    const size_t ldsBytes = (size_t)mpl.pp.ldsFloats * 4;
-    const void* fk = nullptr;
-#define NOCF_MBW_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) fk = states ? reinterpret_cast<const void*>(rollout_mono_bwd_kernel<M_, D_, true>) \
-                                                                       : (mode == 2 ? reinterpret_cast<const void*>(rollout_mono_bwd_kernel<M_, D_, 2>) \
-                                                                       : (mode == 3 ? reinterpret_cast<const void*>(rollout_mono_bwd_kernel<M_, D_, 0, false, true>) \
-                                                                                    : reinterpret_cast<const void*>(rollout_mono_bwd_kernel<M_, D_>)));
-    NOCF_MBW_PICK(8, 1) NOCF_MBW_PICK(6, 1) NOCF_MBW_PICK(4, 1) NOCF_MBW_PICK(8, 2) NOCF_MBW_PICK(6, 2) NOCF_MBW_PICK(4, 2)
-#undef NOCF_MBW_PICK
-    if (!fk) return NOCF_E_SHAPE;
-    hipError_t e = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes);
-    if (e) return (int)e;
-    if (env_int("NOCF_DEBUG", 0)) fprintf(stderr, "[nocf] mono adjoint kernel: %d hidden k-blocks, LDS %zu B/workgroup\n", mpl.KBM, ldsBytes);
-    const MonoPlan* mpp = reinterpret_cast<const MonoPlan*>(ws + mpl.pp.oPlan);
-    const float* wsc = ws;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (g_prof_on) {
-        if (hipEventCreate(&ev0) || hipEventCreate(&ev1)) return (int)hipErrorUnknown;
-        (void)hipEventRecord(ev0, st);
-    }
     MonoEnsArgs noEns;                                // (read by the ENS instantiations only: nocf_rollout_bwd_mid_ensemble_f32)
     memset(&noEns, 0, sizeof(noEns));
-    void* args[] = {(void*)&mpp, (void*)&pb, (void*)&wsc, (void*)&ba, (void*)&noEns};
-    e = hipLaunchKernel(fk, dim3((unsigned)rows), dim3(256), args, ldsBytes, st);
-    if (e) return (int)e;
-    if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
-    g_last_kernel = states ? "rollout_mono_bwd_kernel<states>" : (mode == 2 ? "rollout_mono_bwd_kernel<joint>" :
-                    (mode == 3 ? "rollout_mono_bwd_kernel<weighted>" : "rollout_mono_bwd_kernel"));
-    g_last_errp = nullptr;
-    return (int)hipGetLastError();
+    return launch_mono_bwd(mpl, ws, pb, ba, noEns, MonoBwdKey{mode == 1 || mode == 2 ? mode : 0, false, mode == 3}, (unsigned)rows, st);
 #endif
 }
 
@@ -3176,39 +3205,13 @@ static int rollout_mid_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, c
     en.alph = alph;
     en.zfs = (long)(nt + 1) * n * (phi->d + 4); en.cfs = (long)(nt + 1) * n * ra.cdim; en.sas = (long)nt * nstage * n * (phi->d + 1);
     en.acts = (long)mono_ens_act_stride(phi, n, nt, stepper);
-    const size_t ldsBytes = (size_t)mpl.pp.ldsFloats * 4;
-    const void* fk = nullptr;
-#define NOCF_MONO_ENS_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) fk = dist ? (s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, 1, true>) \
-                                                                                                : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 1, true>)) \
-                                                                                 : noise ? (s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, 2, true>) \
-                                                                                                 : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 2, true>)) \
-                                                                                 : s_all ? reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, true, 0, true>) \
-                                                                                         : reinterpret_cast<const void*>(rollout_mono_kernel<M_, D_, false, 0, true>);
-    MONO_SHAPES(NOCF_MONO_ENS_PICK)
-#undef NOCF_MONO_ENS_PICK
-    if (!fk) return NOCF_E_SHAPE;
-    hipError_t e = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes);
-    if (e) return (int)e;
-    if (env_int("NOCF_DEBUG", 0)) fprintf(stderr, "[nocf] mono kernel: %d hidden / %d input k-blocks, LDS %zu B/workgroup\n", mpl.KBM, mpl.KBD, ldsBytes);
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (g_prof_on) {
-        if (hipEventCreate(&ev0) || hipEventCreate(&ev1)) return (int)hipErrorUnknown;
-        (void)hipEventRecord(ev0, st);
-    }
-    const MonoPlan* mpp = reinterpret_cast<const MonoPlan*>(ws + mpl.pp.oPlan);
-    HoldArgs noHold{};                                // (read by the HOLD instantiations only: nocf_rollout_held_f32)
-    void* args[] = {(void*)&mpp, (void*)&pb, (void*)&ws, (void*)&ra, (void*)&en, (void*)&nz, (void*)&noHold};
-    e = hipLaunchKernel(fk, dim3((unsigned)((long)members * en.tiles)), dim3(256), args, ldsBytes, st);
-    if (e) return (int)e;
+    rc = launch_mono_fwd(mpl, ws, pb, ra, en, nz, HoldArgs{}, MonoFwdKey{s_all != nullptr, dist ? 1 : noise ? 2 : 0, true, false},
+                         (unsigned)((long)members * en.tiles), st);
+    if (rc) return rc;
     if (mono_rec && act_recorded) *act_recorded = 1;
-    g_last_kernel = dist ? "rollout_mono_kernel<ens,disturbed>" : noise ? "rollout_mono_kernel<ens,noisy>" : "rollout_mono_kernel<ens>";
-    g_last_errp = nullptr;
-    e = hipGetLastError();
-    if (e) return (int)e;
-    if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
     if (cost_sums) {                                      // (persample is member-contiguous: the lane ensemble's reduction as it is)
         hipLaunchKernelGGL(cost_sum_ens_kernel, dim3(members), dim3(256), 0, st, persample, (long)n, cost_sums, cost_means, alph);
-        e = hipGetLastError();
+        const hipError_t e = hipGetLastError();
         if (e) return (int)e;
     }
     return 0;
@@ -3379,33 +3382,8 @@ static int bwd_mid_ensemble_impl(const NocfPhi* phi, const NocfProb* prob, int64
     memset(&en, 0, sizeof(en));
     en.n = (unsigned)n; en.tiles = (unsigned)rows; en.wss = (long)(mono_ens_ws_stride(mpl) / 4); en.alph = alph;
     en.sas = (long)nt * ba.nstage * n * (phi->d + 1); en.acts = (long)mono_ens_act_stride(phi, n, nt, stepper);
-    const size_t ldsBytes = (size_t)mpl.pp.ldsFloats * 4;
-    const void* fk = nullptr;
-#define NOCF_MBW_ENS_PICK(M_, D_) if (mpl.KBM == M_ && mpl.KBD == D_) fk = mode == 2 ? reinterpret_cast<const void*>(rollout_mono_bwd_kernel<M_, D_, 2, true>) \
-                                                                           : mode == 1 ? reinterpret_cast<const void*>(rollout_mono_bwd_kernel<M_, D_, 1, true>) \
-                                                                           : weighted ? reinterpret_cast<const void*>(rollout_mono_bwd_kernel<M_, D_, 0, true, true>) \
-                                                                                     : reinterpret_cast<const void*>(rollout_mono_bwd_kernel<M_, D_, 0, true>);
-    NOCF_MBW_ENS_PICK(8, 1) NOCF_MBW_ENS_PICK(6, 1) NOCF_MBW_ENS_PICK(4, 1) NOCF_MBW_ENS_PICK(8, 2) NOCF_MBW_ENS_PICK(6, 2) NOCF_MBW_ENS_PICK(4, 2)
-#undef NOCF_MBW_ENS_PICK
-    if (!fk) return NOCF_E_SHAPE;
-    hipError_t e = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes);
-    if (e) return (int)e;
-    if (env_int("NOCF_DEBUG", 0)) fprintf(stderr, "[nocf] mono adjoint kernel: %d hidden k-blocks, LDS %zu B/workgroup\n", mpl.KBM, ldsBytes);
-    const MonoPlan* mpp = reinterpret_cast<const MonoPlan*>(ws + mpl.pp.oPlan);
-    const float* wsc = ws;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (g_prof_on) {
-        if (hipEventCreate(&ev0) || hipEventCreate(&ev1)) return (int)hipErrorUnknown;
-        (void)hipEventRecord(ev0, st);
-    }
-    void* args[] = {(void*)&mpp, (void*)&pb, (void*)&wsc, (void*)&ba, (void*)&en};
-    e = hipLaunchKernel(fk, dim3((unsigned)((long)members * rows)), dim3(256), args, ldsBytes, st);
-    if (e) return (int)e;
-    if (g_prof_on) { (void)hipEventRecord(ev1, st); g_prof_events.emplace_back(ev0, ev1); }
-    g_last_kernel = mode == 2 ? "rollout_mono_bwd_kernel<ens,joint>" : mode == 1 ? "rollout_mono_bwd_kernel<ens,states>" :
-                    (weighted ? "rollout_mono_bwd_kernel<ens,weighted>" : "rollout_mono_bwd_kernel<ens>");
-    g_last_errp = nullptr;
-    return (int)hipGetLastError();
+    return launch_mono_bwd(mpl, ws, pb, ba, en, MonoBwdKey{mode == 1 || mode == 2 ? mode : 0, true, mode != 1 && mode != 2 && weighted},
+                           (unsigned)((long)members * rows), st);
 #endif
 }
 
